@@ -40,6 +40,11 @@ in the same process, a few steps each under the same timing rules (value,
 ms_per_step, dominant kernel, frac / executed_frac per configuration;
 ``--no-secondary`` skips them, ``--secondary-steps`` sets their length).
 
+Outputs. ``--dump-outputs DIR`` writes what the last timed step returned to its
+caller (stats, the updated policy's parameters, a seeded sample of the final
+observations) as ``DIR/<name>.npy`` (``dump_outputs``): same arguments, same
+inputs, so two builds can be compared output for output.
+
 Besides the contract's fields, the JSON line carries
   roofline      the kernel the timed region spends most time in (whichever it is
                 in this run -- with the defaults one of the three tower kernels:
@@ -258,6 +263,10 @@ def parse_args(argv: None | list[str] = None) -> argparse.Namespace:
     p.add_argument("--no-secondary", dest="secondary", action="store_false")
     p.add_argument("--secondary-steps", type=int, default=3)
     p.add_argument("--secondary-warmup", type=int, default=1)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps: write what the last timed collect()+step() returned to its caller (the"
+                        " CollectStats and StepStats numbers, the policy's parameters, a fixed sample of the observations"
+                        " the next collect() starts from) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     return p.parse_args(argv)
 
 
@@ -626,6 +635,9 @@ def measure(args: argparse.Namespace, world: int, backend: None | str) -> dict:
     barrier()
     elapsed = time.perf_counter() - t0
     hip.timer.enabled = False
+    dumped = None
+    if getattr(args, "dump_outputs", None) and args.steps > 0 and (world == 1 or dist.get_rank() == 0):
+        dumped = dump_outputs(args.dump_outputs, algo, c, s)
     # The same loop without the per-kernel HIP-event pairs (~127 timed ABI calls per step above), same process, same
     # barriers: what the instrumentation costs shows as the difference.
     plain_elapsed = None
@@ -771,6 +783,7 @@ def measure(args: argparse.Namespace, world: int, backend: None | str) -> dict:
         "num_minibatches": algo.hparams.num_minibatches, "collectives": algo.shards.collectives,
         "piecewise": dict(piecewise_mlp.stats) if args.towers == "piecewise" else None,
         "max_memory_allocated_GB": round(torch.cuda.max_memory_allocated() / 1e9, 2),
+        "dumped": dumped,
     }
     # release everything the configuration held on the device (the next one may need most of it)
     algo._release_step_caches()
@@ -779,6 +792,44 @@ def measure(args: argparse.Namespace, world: int, backend: None | str) -> dict:
     torch.cuda.empty_cache()
     torch.cuda.reset_peak_memory_stats()
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_OBS_ROWS = 4096
+
+
+def dump_outputs(directory: str, algo, collect_stats: dict, step_stats: dict) -> dict:
+    """Write what the last timed ``collect(); step()`` handed its caller to ``directory`` as ``<name>.npy``: every
+    CollectStats / StepStats number (float64, ``collect.<key>`` / ``step.<key>``, the ``profiling/`` timings left out),
+    the policy's parameters after the update (float32, ``param.<name>``) and the observations the next ``collect()``
+    starts from for a fixed, seeded sample of environments (``obs_final.npy`` and their indices ``obs_final_envs.npy``;
+    the full slab can pass the size limit).  Nothing here draws from torch's generators, so the runs after it see the
+    same numbers as without the dump."""
+    import numpy as np
+    import torch
+
+    from rl8_amd.data import DataKeys
+
+    arrays: dict[str, np.ndarray] = {}
+    for prefix, stats in (("collect", collect_stats), ("step", step_stats)):
+        for key in sorted(stats):
+            if not key.startswith("profiling/"):
+                arrays[f"{prefix}.{key.replace('/', '.')}"] = np.array([float(stats[key])], dtype=np.float64)
+    for name, p in algo.policy.model.named_parameters():
+        arrays[f"param.{name}"] = p.detach().to(torch.float32).cpu().numpy()
+    final_obs = algo.buffer[DataKeys.OBS][:, -1]
+    n = int(final_obs.shape[0])
+    envs = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_OBS_ROWS), replace=False))
+    rows = final_obs[torch.from_numpy(envs).to(final_obs.device)].cpu()
+    arrays["obs_final"] = rows.numpy().astype(np.float32 if rows.is_floating_point() else np.float64)
+    arrays["obs_final_envs"] = envs.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a))
+    return {"dir": directory, "files": len(arrays), "bytes": total}
 
 
 def roofline_of(kernels: dict, steps: int) -> tuple[None | dict, str, str]:
@@ -962,6 +1013,8 @@ def headline(args: argparse.Namespace, m: dict, world: int, backend: None | str)
     }
     if m["piecewise"] is not None:
         line["piecewise"] = m["piecewise"]
+    if m["dumped"] is not None:
+        line["dump_outputs"] = m["dumped"]
     return line
 
 
@@ -987,7 +1040,7 @@ def secondary_lines(args: argparse.Namespace, world: int, backend: None | str) -
         a = argparse.Namespace(**{**vars(args), "env": "discrete", "distribution": "default", "recurrent": False,
                                   "minibatches": 1, "towers": "matrix", "scaling": "weak",
                                   "steps": args.secondary_steps, "warmup": args.secondary_warmup,
-                                  "uninstrumented_steps": args.secondary_steps, **overrides})
+                                  "uninstrumented_steps": args.secondary_steps, "dump_outputs": None, **overrides})
         t0 = time.perf_counter()
         try:
             m = measure(a, world, backend)

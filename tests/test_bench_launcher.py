@@ -80,6 +80,40 @@ def test_strong_and_weak_arguments():
     assert bench.parse_args([]).scaling == "weak" and bench.parse_args([]).gpus == 1
 
 
+def test_dump_outputs_writes_the_last_steps_results(tmp_path):
+    """--dump-outputs: stats (timings left out) as float64, parameters as float32, a seeded sample of the final
+    observations; two dumps of the same state are identical file for file."""
+    import numpy as np
+    import torch
+
+    class Algo:
+        pass
+
+    algo = Algo()
+    algo.policy = Algo()
+    algo.policy.model = torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.Linear(4, 2))
+    obs = torch.arange(10000 * 5 * 3, dtype=torch.float32).reshape(10000, 5, 3)   # [N, H + 1, obs]
+    algo.buffer = {"obs": obs}
+    collect = {"returns/mean": 1.5, "env/steps": 40000, "profiling/collect_ms": 3.0}
+    step = {"losses/total": 0.25, "profiling/step_ms": 7.0}
+    assert bench.parse_args(["--dump-outputs", str(tmp_path / "a")]).dump_outputs == str(tmp_path / "a")
+    rec = bench.dump_outputs(str(tmp_path / "a"), algo, collect, step)
+    bench.dump_outputs(str(tmp_path / "b"), algo, collect, step)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and rec["files"] == len(names)
+    assert "collect.returns.mean.npy" in names and "step.losses.total.npy" in names
+    assert not any("profiling" in n for n in names)
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "collect.returns.mean.npy").tolist() == [1.5]
+    assert np.array_equal(np.load(tmp_path / "a" / "param.1.weight.npy"), algo.policy.model[1].weight.detach().numpy())
+    envs = np.load(tmp_path / "a" / "obs_final_envs.npy").astype(np.int64)
+    assert len(envs) == bench.DUMP_OBS_ROWS and len(set(envs.tolist())) == len(envs)
+    assert np.array_equal(np.load(tmp_path / "a" / "obs_final.npy"), obs[envs, -1].numpy())
+    assert rec["bytes"] <= bench.DUMP_LIMIT_BYTES
+
+
 def test_self_launched_ranks_rendezvous_then_stop_at_no_hip_device():
     import torch
 
