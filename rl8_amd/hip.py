@@ -897,6 +897,12 @@ def mlp_backward_f16_supports(d_in: int, n_out: int) -> bool:
     return bool(load().rl8_mlp_backward_f16_supports(int(d_in), int(n_out)))
 
 
+def mlp_gates_on() -> bool:
+    """Whether the towers' rank-one gate kernels may run: ``RL8_WGRAD_GATE_OFF=1`` turns them off (A/B runs).
+    Read on every call."""
+    return not int(os.environ.get("RL8_WGRAD_GATE_OFF", "0") or 0)
+
+
 def mlp_pack_w2_f16(w2: torch.Tensor, *, transposed: bool = False) -> torch.Tensor:
     """[256, 256] nn.Linear weight -> two fp16 planes of 2^e * w (hi = fp16(v),
     lo = fp16(v - hi)) in fragment order, followed by {2^e, 2^-e} (uint8)."""
@@ -1003,6 +1009,7 @@ def mlp_tower_backward(
     w1: None | torch.Tensor = None, b1: None | torch.Tensor = None, *, wgrad_split: bool = False,
     gate2: None | torch.Tensor = None, gate_pack=None, w2: None | torch.Tensor = None, b2: None | torch.Tensor = None,
     h2_fn=None, info: None | dict = None, assume_general: bool = False, assume_pair: bool = False,
+    gates_on: None | bool = None,
 ) -> dict[str, torch.Tensor]:
     """Gradients of one tower's parameters given ``dout`` [M, n_out] and the
     activations saved by the forward pass. Returns ``w1, b1, w2, b2, w3, b3``.
@@ -1022,16 +1029,16 @@ def mlp_tower_backward(
     ``info`` (a dict) receives ``rank_one``: whether the gate kernels ran.  ``assume_general`` (with ``h2``): a
     two-output head already known not to be a pair skips the check of ``dout`` (a pass over it and a host read per
     call) and runs the general kernels, which are right for any ``dout``.  ``assume_pair``: ``dout`` [M, 2] is an exact
-    pair by construction (the caller vouches: the two-class loss kernel's own output) -- no check either."""
+    pair by construction (the caller vouches: the two-class loss kernel's own output) -- no check either.
+    ``gates_on``: whether the gate kernels may run at all (default ``mlp_gates_on()``)."""
     m, d_in = x.shape
     n_out = w3.shape[0]
-    split = w2t_packed.dtype == torch.uint8
-    f16 = split
-    if split and w2t_packed.numel() != int(load().rl8_mlp_f16_packed_bytes()):
+    planes = w2t_packed.dtype == torch.uint8
+    if planes and w2t_packed.numel() != int(load().rl8_mlp_f16_packed_bytes()):
         raise ValueError("w2t_packed: a uint8 pack must come from mlp_pack_w2_f16(..., transposed=True)")
-    if f16 and gate2 is None:
+    if planes and gate2 is None:
         raise ValueError("the fp16-plane backward needs gate2 (mlp_tower_forward_split(save_gate=True))")
-    if h1 is None and not split:
+    if h1 is None and not planes:
         raise ValueError("h1 may be omitted only on the fp16-plane path")
     for name, t, numel in (("x", x, m * d_in), ("h1", h1, m * MLP_HIDDEN), ("h2", h2, m * MLP_HIDDEN),
                            ("dout", dout, m * n_out)):
@@ -1048,75 +1055,53 @@ def mlp_tower_backward(
     partials = torch.empty(max_rows, width, dtype=torch.float32, device=x.device)
     rows = C.c_int(0)
     dw2 = None
-    if split:
+    if planes:
         # fused: the data-gradient kernel stores no dZ2; the weight-gradient kernel
         # re-forms it (and h1) and accumulates the head gradients
         if w1 is None or b1 is None:
             raise ValueError("the fp16-plane backward needs w1 and b1")
         w1p, b1p = _ptr(_dense(w1.detach(), torch.float32, "w1")), _ptr(_dense(b1.detach(), torch.float32, "b1"))
-        # two outputs with exactly opposite gradients (a two-way categorical head): the weight
-        # gradient can take the gate-plane kernel; checked on the data, the answer read back
-        # behind the data-gradient launch so that the GPU has work while the host waits
-        gates_on = not int(os.environ.get("RL8_WGRAD_GATE_OFF", "0") or 0)
-        pair_flag, pair = None, False
-        if n_out == 2 and gates_on and assume_pair:
-            pair = True
-        elif n_out == 2 and gates_on and not (assume_general and h2 is not None):
+        w3p = _ptr(w3.detach())
+        if gates_on is None:
+            gates_on = mlp_gates_on()
+        # two outputs with exactly opposite gradients (a two-way categorical head) are rank-one too: checked on the
+        # data, the answer read back behind the data-gradient launch so that the GPU has work while the host waits
+        pair = n_out == 2 and gates_on and assume_pair
+        pair_flag = None
+        if n_out == 2 and gates_on and not pair and not (assume_general and h2 is not None):
             pair_flag = _pair_flag(x.device)
             _check(lib.rl8_mlp_dout_pair_check(_ptr(dout), m, _ptr(pair_flag), _stream()), "rl8_mlp_dout_pair_check")
-            if f16 and (gate_pack is not None or h2 is None):  # needed before the data gradient: read it now (a short bubble)
-                pair = int(pair_flag[0].item()) == 0
-                pair_flag = None
-        if h2 is None and not (f16 and gates_on and (n_out == 1 or pair) and w2 is not None and b2 is not None):
+            if gate_pack is not None or h2 is None:  # needed before the data gradient: read it now (a short bubble)
+                pair, pair_flag = int(pair_flag[0].item()) == 0, None
+        rank_one = gates_on and (n_out == 1 or pair)
+        if h2 is None and not (rank_one and w2 is not None and b2 is not None):
             if h2_fn is None:
                 raise ValueError("h2=None needs a rank-one head on the fp16-plane path (with w2, b2) or h2_fn")
             h2 = h2_fn()  # not a rank-one head after all: the forward is re-run for h2
-        gate_dgrad = f16 and gate_pack is not None and gates_on and (n_out == 1 or pair)
+        # data gradient: gate mode (B operand w2 * w3e) for rank-one heads, general mode (w2^T and w3) otherwise
+        gate_dgrad = gate_pack is not None and rank_one
         with _timed("mlp_tower_backward_gate" if gate_dgrad else "mlp_tower_backward", m):
-            if gate_dgrad:
-                _check(
-                    lib.rl8_mlp_tower_backward_gate_f16_f32(
-                        _ptr(x), w1p, b1p, _ptr(dout), m, d_in, _ptr(gate_pack()), n_out,
-                        _ptr(partials), C.byref(rows), _ptr(gate2), _stream()),
-                    "rl8_mlp_tower_backward_gate_f16_f32",
-                )
-            else:
-                _check(
-                    lib.rl8_mlp_tower_backward_f16_f32(
-                        _ptr(x), w1p, b1p, _ptr(dout), m, d_in, _ptr(w2t_packed), _ptr(w3.detach()), n_out,
-                        _ptr(partials), C.byref(rows), _ptr(gate2), _stream()),
-                    "rl8_mlp_tower_backward_f16_f32",
-                )
+            name, b_args = (("rl8_mlp_tower_backward_gate_f16_f32", (_ptr(gate_pack()),)) if gate_dgrad
+                            else ("rl8_mlp_tower_backward_f16_f32", (_ptr(w2t_packed), w3p)))
+            _check(getattr(lib, name)(_ptr(x), w1p, b1p, _ptr(dout), m, d_in, *b_args, n_out, _ptr(partials),
+                                      C.byref(rows), _ptr(gate2), _stream()), name)
         dw2 = torch.empty(MLP_HIDDEN, MLP_HIDDEN, dtype=torch.float32, device=x.device)
-        # (bf16 planes for both generations: see rl8_mlp_tower_backward_f16_f32; single-output towers
-        # run the gate-plane kernel -- three plane products instead of six -- timed under its own name)
-        gate_kernel = n_out == 1 and gates_on
         pair = pair or (pair_flag is not None and int(pair_flag[0].item()) == 0)
+        rank_one = gates_on and (n_out == 1 or pair)
         if info is not None:
-            info["rank_one"] = bool(gate_kernel or pair)
-        with _timed("mlp_wgrad_gate" if gate_kernel or pair else "mlp_wgrad", m):
-            if h2 is None:  # rank-one head, gate bits only: dW3 from the weight-gradient sums
-                _check(
-                    lib.rl8_mlp_wgrad_gate_bits_f32(
-                        _ptr(gate2), _ptr(dout), _ptr(x), w1p, b1p, _ptr(_dense(w2.detach(), torch.float32, "w2")),
-                        _ptr(_dense(b2.detach(), torch.float32, "b2")), _ptr(w3.detach()), m, d_in, n_out,
-                        _ptr(_wgrad_workspace(x.device)), _ptr(dw2), _ptr(partials), _stream()),
-                    "rl8_mlp_wgrad_gate_bits_f32",
-                )
-            elif pair:
-                _check(
-                    lib.rl8_mlp_wgrad_fused_pair_f32(
-                        _ptr(h2), _ptr(dout), _ptr(x), w1p, b1p, _ptr(w3.detach()), m, d_in,
-                        _ptr(_wgrad_workspace(x.device)), _ptr(dw2), _ptr(partials), _stream()),
-                    "rl8_mlp_wgrad_fused_pair_f32",
-                )
-            else:
-                _check(
-                    lib.rl8_mlp_wgrad_fused_split_f32(
-                        _ptr(h2), _ptr(dout), _ptr(x), w1p, b1p, _ptr(w3.detach()), m, d_in, n_out,
-                        _ptr(_wgrad_workspace(x.device)), _ptr(dw2), _ptr(partials), _stream()),
-                    "rl8_mlp_wgrad_fused_split_f32",
-                )
+            info["rank_one"] = rank_one
+        # weight gradient: a rank-one head with gate bits only takes dW3 from the weight-gradient sums, a pair the pair
+        # kernel, anything else the general entry (which runs the gate-plane kernel itself for one output)
+        with _timed("mlp_wgrad_gate" if rank_one else "mlp_wgrad", m):
+            name, args = (
+                ("rl8_mlp_wgrad_gate_bits_f32", (_ptr(gate2), _ptr(dout), _ptr(x), w1p, b1p,
+                                                 _ptr(_dense(w2.detach(), torch.float32, "w2")),
+                                                 _ptr(_dense(b2.detach(), torch.float32, "b2")), w3p, m, d_in, n_out))
+                if h2 is None else
+                ("rl8_mlp_wgrad_fused_pair_f32", (_ptr(h2), _ptr(dout), _ptr(x), w1p, b1p, w3p, m, d_in)) if pair else
+                ("rl8_mlp_wgrad_fused_split_f32", (_ptr(h2), _ptr(dout), _ptr(x), w1p, b1p, w3p, m, d_in, n_out)))
+            _check(getattr(lib, name)(*args, _ptr(_wgrad_workspace(x.device)), _ptr(dw2), _ptr(partials), _stream()),
+                   name)
     else:
         dz2 = torch.empty(m, MLP_HIDDEN, dtype=torch.float32, device=x.device)
         with _timed("mlp_tower_backward", m):
@@ -1134,8 +1119,8 @@ def mlp_tower_backward(
         "b2": small[o1 + MLP_HIDDEN : o1 + 2 * MLP_HIDDEN],
         "w3": small[o1 + 2 * MLP_HIDDEN : o1 + 2 * MLP_HIDDEN + n_out * MLP_HIDDEN].view(n_out, MLP_HIDDEN),
         # (the fused plane backward leaves db3 -- a column sum of dout -- to the caller)
-        "b3": _column_sums(dout) if split else small[o1 + 2 * MLP_HIDDEN + n_out * MLP_HIDDEN :],
-        "w2": dw2 if split else (mlp_wgrad_split(dz2, x, w1, b1) if wgrad_split else mlp_wgrad(dz2, h1)),
+        "b3": _column_sums(dout) if planes else small[o1 + 2 * MLP_HIDDEN + n_out * MLP_HIDDEN :],
+        "w2": dw2 if planes else (mlp_wgrad_split(dz2, x, w1, b1) if wgrad_split else mlp_wgrad(dz2, h1)),
     }
     return grads
 

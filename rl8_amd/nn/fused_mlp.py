@@ -2,16 +2,17 @@
 
 ``Linear(d_in, 256) -> ReLU -> Linear(256, 256) -> ReLU -> Linear(256, n_out)``
 (``src/rl8/models/_feedforward.py:336-362`` of the reference) runs as one forward
-kernel and two backward kernels, in fp32 on the matrix cores, instead of ~8
-(forward) / ~20 (backward) eager launches whose 256-wide activations each make
-an HBM round trip. Parameters stay ordinary
-``torch.nn.Linear`` weights; this module only changes how the tower is evaluated.
+kernel and two backward kernels on the matrix cores -- fp16-plane products at fp32
+accuracy where a plane kernel serves the width, fp32 MFMA elsewhere (``_plan`` decides
+per call) -- instead of ~8 (forward) / ~20 (backward) eager launches whose 256-wide
+activations each make an HBM round trip. Parameters stay ordinary ``torch.nn.Linear``
+weights; this module only changes how the tower is evaluated.
 
 ``tower_forward`` falls back to the module's own eager path whenever the tower
 is not exactly that shape (other widths, activations, norm layers, non-HIP or
 non-fp32 inputs), so custom models are unaffected.
 
-Under ``enable_amp`` (torch autocast) the fused towers still run, in fp32: that is
+Under ``enable_amp`` (torch autocast) the fused towers still run, at fp32 accuracy: that is
 at least the precision autocast asks for, and on MI355X it is also ~5x faster than
 the autocast path of the same modules (37 vs 8 M transitions/s on the headline
 config), whose casts and elementwise launches dominate at this width.
@@ -20,6 +21,8 @@ config), whose casts and elementwise launches dominate at this width.
 
 from __future__ import annotations
 
+import dataclasses
+import functools
 import os
 from typing import Sequence
 
@@ -37,33 +40,31 @@ ENABLED = True
 #: split into two fp16 planes, three plane products per 16 k on the fp16 matrix
 #: pipe, fp32 accumulate (fp32 accuracy: same fp64 bars as the others);
 #: "f32" = v_mfma_f32_32x32x2_f32 (2.7x slower; also what widths without a plane
-#: kernel run).  (The six-product bf16-plane forward / data-gradient kernels of rounds 1-2,
-#: "split", were removed in round 3.)  ``RL8_AMD_TOWER_GEMM`` /
-#: ``RL8_AMD_TOWER_FORWARD_GEMM`` / ``RL8_AMD_TOWER_BACKWARD_GEMM`` override.
+#: kernel run).  ``RL8_AMD_TOWER_GEMM`` / ``RL8_AMD_TOWER_FORWARD_GEMM`` /
+#: ``RL8_AMD_TOWER_BACKWARD_GEMM`` override.  Read on every call (``_plan``): tests
+#: and ``bench.py`` change them at run time.
 FORWARD_GEMM = os.environ.get("RL8_AMD_TOWER_FORWARD_GEMM", os.environ.get("RL8_AMD_TOWER_GEMM", "f16"))
 #: Same choice for the data-gradient product of the backward pass (the weight
 #: gradient runs on fp16 planes scaled per output column, ``hip`` / mlp_split_kernels.hip).
 BACKWARD_GEMM = os.environ.get("RL8_AMD_TOWER_BACKWARD_GEMM", os.environ.get("RL8_AMD_TOWER_GEMM", "f16"))
 for _name, _value in (("forward", FORWARD_GEMM), ("backward", BACKWARD_GEMM)):
     if _value not in ("f16", "f32"):
-        # ("split", the bf16-plane forward / data-gradient generation, was removed in round 3: say so instead of
-        # silently running the fp32-MFMA kernels -- ADVICE r3)
         raise ValueError(f"RL8_AMD_TOWER_GEMM / RL8_AMD_TOWER_{_name.upper()}_GEMM = {_value!r}: the towers' {_name} product"
                          " runs as 'f16' (fp16 planes, default) or 'f32' (fp32 MFMA); 'split' no longer exists")
 
 
-def _packed(layer: nn.Linear, transposed: bool, split: bool | str = False) -> torch.Tensor:
-    """MFMA-fragment-ordered copy of ``layer.weight``, cached ON the layer and
-    re-made when the optimizer has changed the weight (version counter) or the
-    weight tensor has been replaced / moved."""
+def _packed(layer: nn.Linear, transposed: bool, planes: bool) -> torch.Tensor:
+    """MFMA-fragment-ordered copy of ``layer.weight`` (fp16 planes or fp32), cached ON
+    the layer and re-made when the optimizer has changed the weight (version counter)
+    or the weight tensor has been replaced / moved."""
     w2 = layer.weight
     cache = layer.__dict__.setdefault("_rl8_w2_packs", {})
-    hit = cache.get((transposed, split))
+    hit = cache.get((transposed, planes))
     if hit is not None and hit[0] == w2._version and hit[1] == w2.data_ptr():
         return hit[2]
-    pack = hip.mlp_pack_w2_f16 if split == "f16" else hip.mlp_pack_w2
+    pack = hip.mlp_pack_w2_f16 if planes else hip.mlp_pack_w2
     packed = pack(w2, transposed=transposed)
-    cache[(transposed, split)] = (w2._version, w2.data_ptr(), packed)
+    cache[(transposed, planes)] = (w2._version, w2.data_ptr(), packed)
     return packed
 
 
@@ -83,8 +84,55 @@ def _packed_gate(layer: nn.Linear, w3: torch.Tensor, w3_key: tuple) -> torch.Ten
     return packed
 
 
-def _gates_off() -> bool:
-    return bool(int(os.environ.get("RL8_WGRAD_GATE_OFF", "0") or 0))
+@functools.lru_cache(maxsize=None)
+def _planes_supported(d_in: int, n_out: int) -> tuple[bool, bool]:
+    """(plane forward, plane backward) compiled for this width: fixed by the build, asked once per width."""
+    return hip.mlp_forward_f16_supports(d_in, n_out), hip.mlp_backward_f16_supports(d_in, n_out)
+
+
+@dataclasses.dataclass(frozen=True)
+class _TowerPlan:
+    """The kernels one tower call runs, forward and backward: made once by ``_plan`` and saved on ``ctx`` so that the
+    backward runs what its forward prepared for."""
+
+    #: forward on fp16 planes (saves the gate bits of h2); else fp32 MFMA (saves h1 and h2)
+    forward_planes: bool
+    #: data gradient on fp16 planes (reads the plane forward's gate bits, recomputes h1); else fp32 MFMA
+    backward_planes: bool
+    #: dW2 on fp16 planes -- the fused weight-gradient kernel, or ``mlp_wgrad_split`` behind the fp32 data gradient
+    wgrad_planes: bool
+    #: the rank-one gate kernels may run (``hip.mlp_gates_on``)
+    gates: bool
+    #: one output, or two with the pair hint, and gates on: the backward is expected to take the gate kernels
+    rank_one: bool
+
+    @property
+    def keep_h1(self) -> bool:
+        """The plane forward stores h1: only the fp32 data gradient reads it."""
+        return not self.backward_planes
+
+    @property
+    def gate_only(self) -> bool:
+        """The forward keeps the gate bits of h2 alone (no h2 store, no h2 read)."""
+        return self.backward_planes and self.rank_one
+
+    @property
+    def recordable(self) -> bool:
+        """Planes both ways: the rollout record / replay path."""
+        return self.backward_planes
+
+
+def _plan(d_in: int, n_out: int, pair: bool) -> _TowerPlan:
+    """The one place the tower routes are decided; reads the switches as they are now."""
+    fwd_ok, bwd_ok = _planes_supported(d_in, n_out)
+    forward_planes = FORWARD_GEMM == "f16" and fwd_ok
+    gates = hip.mlp_gates_on()
+    return _TowerPlan(forward_planes=forward_planes,
+                      # (the plane data gradient reads the gate bits only the plane forward saves)
+                      backward_planes=forward_planes and BACKWARD_GEMM == "f16" and bwd_ok,
+                      wgrad_planes=BACKWARD_GEMM == "f16",
+                      gates=gates,
+                      rank_one=gates and (n_out == 1 or (n_out == 2 and pair)))
 
 
 _PAIR_HINT = False
@@ -140,32 +188,26 @@ def _trusted_pair(g: torch.Tensor) -> bool:
 
 class _FusedTower(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, w3, b3, layer2, grad_mode, pair, w3_key):  # type: ignore[override]
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3, layer2, grad_mode, plan, w3_key):  # type: ignore[override]
         # needs_input_grad reflects the parameters' requires_grad even when the
         # caller runs under no_grad (rollouts), and inside forward() grad mode is
         # always off: the caller's grad mode comes in as an argument, so that
         # activations are kept only when a backward can follow.
         need_grad = grad_mode and any(ctx.needs_input_grad[1:7])
-        if FORWARD_GEMM == "f16" and hip.mlp_forward_f16_supports(x.shape[1], w3.shape[0]):
-            # h1 is stored only if a backward kernel will read it (the plane kernels recompute it)
-            keep_h1 = not (BACKWARD_GEMM == "f16" and hip.mlp_backward_f16_supports(x.shape[1], w3.shape[0]))
-            f16 = True
+        if plan.forward_planes:
             # Rank-one heads (one output; two outputs with exactly opposite gradients, as the last backward of
             # this tower found them) need only the gate bits of h2 in the backward pass: no h2 store, no h2
             # read.  Should a two-output head stop being rank-one, its backward re-runs this forward for h2.
-            n_out = w3.shape[0]
-            gate_only = (need_grad and f16 and not keep_h1 and BACKWARD_GEMM == "f16"
-                         and hip.mlp_backward_f16_supports(x.shape[1], n_out) and not _gates_off()
-                         and (n_out == 1 or (n_out == 2 and pair)))
-            out, h1, h2, gate = hip.mlp_tower_forward_split(x, w1, b1, _packed(layer2, False, "f16"),
-                                                            b2, w3, b3, save=need_grad, save_h1=keep_h1, save_gate=True,
-                                                            save_h2=not gate_only)
+            out, h1, h2, gate = hip.mlp_tower_forward_split(x, w1, b1, _packed(layer2, False, True), b2, w3, b3,
+                                                            save=need_grad, save_h1=plan.keep_h1, save_gate=True,
+                                                            save_h2=not plan.gate_only)
         else:
-            out, h1, h2 = hip.mlp_tower_forward(x, w1, b1, _packed(layer2, False), b2, w3, b3, save=need_grad)
+            out, h1, h2 = hip.mlp_tower_forward(x, w1, b1, _packed(layer2, False, False), b2, w3, b3, save=need_grad)
             gate = None
         if need_grad:
             ctx.layer2 = layer2
             ctx.w3_key = w3_key
+            ctx.plan = plan
             # (w2 is saved although the kernels read its packed copies: autograd's version check then refuses a
             # backward after an in-place change of the weight, as it would for the eager modules)
             ctx.save_for_backward(x, h1, h2, w3, w1, b1, gate, b2, b3, w2)
@@ -173,34 +215,34 @@ class _FusedTower(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):  # type: ignore[override]
-        return _tower_backward(ctx, dout)
+        return _tower_backward(ctx, dout) + (None,) * 4
 
 
 def _tower_backward(ctx, dout):
-    """Backward of ``_FusedTower`` and of ``_ReplayedTower`` (same saved tensors, same kernels)."""
+    """Backward of ``_FusedTower`` and of ``_ReplayedTower`` (same saved tensors, same kernels, the forward's
+    ``ctx.plan``): gradients of x (none) and of the six tower parameters."""
     x, h1, h2, w3, w1, b1, gate, b2, b3, w2 = ctx.saved_tensors
-    split: bool | str = False
-    if BACKWARD_GEMM == "f16" and gate is not None and hip.mlp_backward_f16_supports(x.shape[1], w3.shape[0]):
-        split = "f16"
+    plan: _TowerPlan = ctx.plan
+    planes = plan.backward_planes
     layer2 = ctx.layer2
     w3_key = ctx.w3_key
-    gate_pack = (lambda: _packed_gate(layer2, w3, w3_key)) if split == "f16" and w3.shape[0] <= 2 else None
+    gate_pack = (lambda: _packed_gate(layer2, w3, w3_key)) if planes and w3.shape[0] <= 2 else None
 
     def h2_again():  # (a two-output head that is not rank-one after all: the forward once more, with h2)
-        return hip.mlp_tower_forward_split(x, w1, b1, _packed(layer2, False, "f16"), b2, w3, b3, save=True,
+        return hip.mlp_tower_forward_split(x, w1, b1, _packed(layer2, False, True), b2, w3, b3, save=True,
                                            save_h1=False, save_gate=True)[2]
 
     info: dict = {}
     # (a two-output head an earlier backward found NOT to be a pair -- mean / log_std of a normal -- is not asked again)
     known_general = w3.shape[0] == 2 and layer2.__dict__.get("_rl8_rank_one") is False
     known_pair = w3.shape[0] == 2 and dout.dtype == torch.float32 and dout.is_contiguous() and _trusted_pair(dout)
-    g = hip.mlp_tower_backward(x, h1, h2, dout.contiguous().float(), _packed(layer2, True, split), w3,
-                               w1, b1, wgrad_split=BACKWARD_GEMM == "f16", gate2=gate if split else None,
+    g = hip.mlp_tower_backward(x, h1, h2, dout.contiguous().float(), _packed(layer2, True, planes), w3,
+                               w1, b1, wgrad_split=plan.wgrad_planes, gate2=gate if planes else None,
                                gate_pack=gate_pack, w2=w2, b2=b2, h2_fn=h2_again, info=info, assume_general=known_general,
-                               assume_pair=known_pair)
+                               assume_pair=known_pair, gates_on=plan.gates)
     if w3.shape[0] == 2:  # what this backward found, for callers that give no hint (see tower_forward)
         layer2.__dict__["_rl8_rank_one"] = bool(info.get("rank_one", False))
-    return None, g["w1"], g["b1"], g["w2"], g["b2"], g["w3"], g["b3"], None, None, None, None
+    return None, g["w1"], g["b1"], g["w2"], g["b2"], g["w3"], g["b3"]
 
 
 # --------------------------------------------------------------------------- #
@@ -403,15 +445,16 @@ class _ReplayedTower(torch.autograd.Function):
     recorded gate bits / h2 for the same backward kernels."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, w3, b3, layer2, w3_key, out, gate, h2):  # type: ignore[override]
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3, layer2, plan, w3_key, out, gate, h2):  # type: ignore[override]
         ctx.layer2 = layer2
         ctx.w3_key = w3_key
+        ctx.plan = plan
         ctx.save_for_backward(x, None, h2, w3, w1, b1, gate, b2, b3, w2)
         return out.detach()
 
     @staticmethod
     def backward(ctx, dout):  # type: ignore[override]
-        return _tower_backward(ctx, dout) + (None,)
+        return _tower_backward(ctx, dout) + (None,) * 6
 
 
 def _tower_params(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear]) -> list[torch.Tensor]:
@@ -468,14 +511,12 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
     if pair_gradients is None:
         pair_gradients = bool(l2.__dict__.get("_rl8_rank_one", False))
     w3_key = tuple((h.weight._version, h.weight.data_ptr()) for h in heads)
-    n_out, d_in = w3.shape[0], x.shape[1]
-    plane_path = (FORWARD_GEMM == "f16" and BACKWARD_GEMM == "f16" and hip.mlp_forward_f16_supports(d_in, n_out)
-                  and hip.mlp_backward_f16_supports(d_in, n_out))
-    if _RECORDING is not None and not torch.is_grad_enabled() and plane_path and x.shape[0] == _RECORDING.rows_per_step:
+    n_out = w3.shape[0]
+    plan = _plan(x.shape[1], n_out, bool(pair_gradients))
+    if _RECORDING is not None and not torch.is_grad_enabled() and plan.recordable and x.shape[0] == _RECORDING.rows_per_step:
         rec = _RECORDING
-        gate_only = not _gates_off() and (n_out == 1 or (n_out == 2 and bool(pair_gradients)))
         params = _tower_params(l1, l2, heads)
-        tr = rec._tower(l2, params, n_out, gate_only, x.device)
+        tr = rec._tower(l2, params, n_out, plan.gate_only, x.device)
         if tr is not None:
             key = tr.current_key()
             if tr.key != key:
@@ -485,27 +526,27 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
             if rec.t in tr.seen:  # second evaluation in this timestep's context: the slab rows of t would be overwritten
                 tr.spoiled = True
                 return _FusedTower.apply(x.contiguous(), l1.weight, l1.bias, l2.weight, l2.bias, w3, b3, l2,
-                                         torch.is_grad_enabled(), bool(pair_gradients), w3_key)
+                                         torch.is_grad_enabled(), plan, w3_key)
             tr.inputs[rec.t] = x.data_ptr()
             lo = rec.t * rec.rows_per_step
             sl = slice(lo, lo + rec.rows_per_step)
             out = hip.mlp_tower_forward_split(
-                x.contiguous(), l1.weight, l1.bias, _packed(l2, False, "f16"), l2.bias, w3, b3, save=True,
-                save_h1=False, save_gate=True, save_h2=not gate_only, out=tr.out[sl], gate_out=tr.gate[sl],
-                h2_out=None if gate_only else tr.h2[sl], timer_name="mlp_tower_forward_record")[0]
+                x.contiguous(), l1.weight, l1.bias, _packed(l2, False, True), l2.bias, w3, b3, save=True,
+                save_h1=False, save_gate=True, save_h2=not plan.gate_only, out=tr.out[sl], gate_out=tr.gate[sl],
+                h2_out=None if plan.gate_only else tr.h2[sl], timer_name="mlp_tower_forward_record")[0]
             tr.seen.add(rec.t)
             replay_stats["recorded_rows"] += rec.rows_per_step
             return out
-    if _REPLAY is not None and torch.is_grad_enabled() and plane_path:
+    if _REPLAY is not None and torch.is_grad_enabled() and plan.recordable:
         rows, expect = _REPLAY
         hit = rows.get(id(l2))
         if (hit is not None and x.data_ptr() == expect.data_ptr() and x.shape == expect.shape and x.is_contiguous()
                 and hit[0] == tuple((p._version, p.data_ptr()) for p in _tower_params(l1, l2, heads))
                 and hit[1].shape == (x.shape[0], n_out)
-                and (hit[3] is not None or n_out == 1 or (n_out == 2 and bool(pair_gradients)))):
+                and (hit[3] is not None or plan.gate_only)):  # (a record without h2 serves rank-one calls)
             replay_stats["replayed_towers"] += 1
             replay_stats["replayed_rows"] += x.shape[0]
-            return _ReplayedTower.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, w3, b3, l2, w3_key,
+            return _ReplayedTower.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, w3, b3, l2, plan, w3_key,
                                         hit[1], hit[2], hit[3])
     return _FusedTower.apply(x.contiguous(), l1.weight, l1.bias, l2.weight, l2.bias, w3, b3, l2,
-                             torch.is_grad_enabled(), bool(pair_gradients), w3_key)
+                             torch.is_grad_enabled(), plan, w3_key)
