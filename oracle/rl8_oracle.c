@@ -399,6 +399,10 @@ static inline void cat_normalise(const float *x, int k, float *nl, float *p, int
   for (int j = 0; j < k; ++j) p[j] = p[j] / s2;
 }
 
+/* Categorical.entropy clamps the normalised logits to finfo.min before the
+ * product with p: a masked class (logit -inf, p = 0) then adds 0, not NaN. */
+static inline float ent_logit(float nl) { return fmaxf(nl, -3.40282346638528859812e+38f); }
+
 #define ORACLE_MAX_CLASSES 64
 
 /* Categorical.sample (distributions.py:121-122 -> torch.multinomial, 1 draw):
@@ -578,7 +582,7 @@ ORACLE_API void oracle_ppo_loss_categorical(
       float l = nl[actions[i * a + d]];
       logp = d == 0 ? l : logp + l;
       float e = 0.0f;
-      for (int j = 0; j < k; ++j) e += nl[j] * p[j]; /* Categorical.entropy */
+      for (int j = 0; j < k; ++j) e += ent_logit(nl[j]) * p[j]; /* Categorical.entropy */
       ent = d == 0 ? -e : ent + (-e);
     }
     float term, dterm, klt, vterm, dv;
@@ -590,14 +594,14 @@ ORACLE_API void oracle_ppo_loss_categorical(
       for (int d = 0; d < a; ++d) {
         cat_normalise(logits + (i * a + d) * k, k, nl, p, 0);
         float h = 0.0f;
-        for (int j = 0; j < k; ++j) h += nl[j] * p[j];
+        for (int j = 0; j < k; ++j) h += ent_logit(nl[j]) * p[j];
         h = -h;
         const int64_t act = actions[i * a + d];
         for (int j = 0; j < k; ++j) {
           float dlogp = (j == act ? 1.0f : 0.0f) - p[j];
           float g = -dterm * dlogp; /* total = ... - policy */
           if (hp->entropy_coeff != 0.0f) {
-            float dent = -p[j] * (nl[j] + h); /* dH/dx_j */
+            float dent = -p[j] * (ent_logit(nl[j]) + h); /* dH/dx_j */
             g -= hp->entropy_coeff * dent;
           }
           grad_logits[(i * a + d) * k + j] = gscale * g;

@@ -156,6 +156,12 @@ __device__ __forceinline__ void categorical_normalise_fast(const float (&x)[K], 
   }
 }
 
+// A normalised logit as Categorical.entropy uses it: clamped to the lowest finite
+// float, so that a masked class (logit -inf, p = 0) adds 0 * -FLT_MAX = 0 to the
+// entropy and to its gradient instead of 0 * -inf = NaN.  One v_max, no branch.
+constexpr float kF32Lowest = -3.40282346638528859812e+38f;
+__device__ __forceinline__ float entropy_logit(float nl) { return fmaxf(nl, kF32Lowest); }
+
 // Runtime-K variant (K <= RL8_MAX_CLASSES) for the generic kernels.
 template <bool CR>
 __device__ __forceinline__ void categorical_normalise_dyn(const float *x, int k, float *nl,

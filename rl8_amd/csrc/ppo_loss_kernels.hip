@@ -114,7 +114,7 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_categorical_kernel(
       if (with_entropy) {
         float e = 0.0f;
 #pragma unroll
-        for (int j = 0; j < K; ++j) e += nl[j] * p[j];
+        for (int j = 0; j < K; ++j) e += entropy_logit(nl[j]) * p[j];
         ent = -e;
       }
       const PolicyTerm pt = ppo_policy_term(logp, lo[s], ad[s], hp);
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_categorical_kernel(
         for (int j = 0; j < K; ++j) {
           const float dlogp = (act[s] == j ? 1.0f : 0.0f) - p[j];
           float gj = -pt.dterm_dlogp * dlogp;
-          if (with_entropy) gj -= hp.entropy_coeff * (-p[j] * (nl[j] + ent));
+          if (with_entropy) gj -= hp.entropy_coeff * (-p[j] * (entropy_logit(nl[j]) + ent));
           gx[s * K + j] = hp.grad_scale * gj;
         }
         if constexpr (K == 2) {
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_categorical_generic_kernel(
       logp = d == 0 ? l : logp + l;
       if (with_entropy) {
         float e = 0.0f;
-        for (int j = 0; j < k; ++j) e += nl[j] * p[j];
+        for (int j = 0; j < k; ++j) e += entropy_logit(nl[j]) * p[j];
         ent = d == 0 ? -e : ent + (-e);
       }
     }
@@ -211,14 +211,14 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_categorical_generic_kernel(
         categorical_normalise_dyn<false>(logits + (i * a + d) * k, k, nl, p);
         float hd = 0.0f;
         if (with_entropy) {
-          for (int j = 0; j < k; ++j) hd += nl[j] * p[j];
+          for (int j = 0; j < k; ++j) hd += entropy_logit(nl[j]) * p[j];
           hd = -hd;
         }
         const int64_t act = action[i * a + d];
         for (int j = 0; j < k; ++j) {
           const float dlogp = (j == act ? 1.0f : 0.0f) - p[j];
           float gj = -pt.dterm_dlogp * dlogp;
-          if (with_entropy) gj -= hp.entropy_coeff * (-p[j] * (nl[j] + hd));
+          if (with_entropy) gj -= hp.entropy_coeff * (-p[j] * (entropy_logit(nl[j]) + hd));
           grad_logits[(i * a + d) * k + j] = hp.grad_scale * gj;
         }
         if (k == 2) {  // exact antisymmetry of a two-way categorical's gradients (see the K = 2 kernel above)
@@ -418,7 +418,8 @@ static int vec_loss_grid(int64_t m) {
   if (cap > 0) {
     const int64_t gg = (groups + kBlock - 1) / kBlock;
     grid = (int)(gg < cap ? gg : cap);
-    if (grid > RL8_MAX_PARTIALS) grid = RL8_MAX_PARTIALS;
+    // (the m % 4 tail publishes row `grid`: one row of the scratch stays free for it)
+    if (grid > RL8_MAX_PARTIALS - 1) grid = RL8_MAX_PARTIALS - 1;
     if (grid < 1) grid = 1;
   }
   return grid;

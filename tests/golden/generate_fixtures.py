@@ -125,6 +125,57 @@ def gen_gae() -> None:
 #     (src/rl8/nn/functional.py:259-363, algorithms/_feedforward.py:552-559,
 #      distributions.py:113-170)
 # --------------------------------------------------------------------------- #
+def record_ppo_case(arrays, cases, name, dist, actions, logp_old, adv, returns, values, feats, hp):
+    """Runs the reference's ``ppo_losses`` + ``total.backward()`` on one case and stores inputs, losses (entropy,
+    policy, vf, total, approximate KL) and the autograd gradients under ``{name}_*``."""
+    m = actions.shape[0]
+    buffer_batch = TensorDict(
+        {
+            DataKeys.ACTIONS: actions,
+            DataKeys.LOGP: logp_old,
+            DataKeys.ADVANTAGES: adv,
+            DataKeys.RETURNS: returns,
+        },
+        batch_size=[m],
+    )
+    sample_batch = TensorDict({DataKeys.VALUES: values}, batch_size=[m])
+    losses = ppo_losses(buffer_batch, sample_batch, dist, **hp)
+    losses["total"].backward()
+    with torch.no_grad():
+        lr = dist.logp(actions) - logp_old
+        kl = torch.mean((torch.exp(lr) - 1) - lr)
+    arrays[f"{name}_actions"] = actions
+    arrays[f"{name}_logp_old"] = logp_old
+    arrays[f"{name}_advantages"] = adv
+    arrays[f"{name}_returns"] = returns
+    arrays[f"{name}_values"] = values
+    arrays[f"{name}_grad_values"] = values.grad
+    for k, f in feats.items():
+        arrays[f"{name}_feat_{k}"] = f
+        arrays[f"{name}_grad_{k}"] = f.grad
+    arrays[f"{name}_losses"] = np.array(
+        [
+            float(losses["entropy"].reshape(-1)[0]),
+            float(losses["policy"]),
+            float(losses["vf"]),
+            float(losses["total"].reshape(-1)[0]),
+            float(kl),
+        ],
+        np.float64,
+    )
+    arrays[f"{name}_hparams"] = np.array(
+        [
+            hp["clip_param"],
+            hp["dual_clip_param"] if hp["dual_clip_param"] else 0.0,
+            hp["entropy_coeff"],
+            hp["vf_clip_param"],
+            hp["vf_coeff"],
+        ],
+        np.float64,
+    )
+    cases.append(name)
+
+
 def gen_ppo_losses() -> None:
     arrays = {}
     cases = []
@@ -136,53 +187,6 @@ def gen_ppo_losses() -> None:
         returns = torch.randn(m, 1, generator=g) * 3
         values = (returns + torch.randn(m, 1, generator=g) * 2).requires_grad_(True)
         return adv, returns, values
-
-    def finish(name, dist, actions, logp_old, adv, returns, values, feats, hp):
-        buffer_batch = TensorDict(
-            {
-                DataKeys.ACTIONS: actions,
-                DataKeys.LOGP: logp_old,
-                DataKeys.ADVANTAGES: adv,
-                DataKeys.RETURNS: returns,
-            },
-            batch_size=[m],
-        )
-        sample_batch = TensorDict({DataKeys.VALUES: values}, batch_size=[m])
-        losses = ppo_losses(buffer_batch, sample_batch, dist, **hp)
-        losses["total"].backward()
-        with torch.no_grad():
-            lr = dist.logp(actions) - logp_old
-            kl = torch.mean((torch.exp(lr) - 1) - lr)
-        arrays[f"{name}_actions"] = actions
-        arrays[f"{name}_logp_old"] = logp_old
-        arrays[f"{name}_advantages"] = adv
-        arrays[f"{name}_returns"] = returns
-        arrays[f"{name}_values"] = values
-        arrays[f"{name}_grad_values"] = values.grad
-        for k, f in feats.items():
-            arrays[f"{name}_feat_{k}"] = f
-            arrays[f"{name}_grad_{k}"] = f.grad
-        arrays[f"{name}_losses"] = np.array(
-            [
-                float(losses["entropy"].reshape(-1)[0]),
-                float(losses["policy"]),
-                float(losses["vf"]),
-                float(losses["total"].reshape(-1)[0]),
-                float(kl),
-            ],
-            np.float64,
-        )
-        arrays[f"{name}_hparams"] = np.array(
-            [
-                hp["clip_param"],
-                hp["dual_clip_param"] if hp["dual_clip_param"] else 0.0,
-                hp["entropy_coeff"],
-                hp["vf_clip_param"],
-                hp["vf_coeff"],
-            ],
-            np.float64,
-        )
-        cases.append(name)
 
     hps = {
         "p0": dict(clip_param=0.2, dual_clip_param=None, entropy_coeff=0.0, vf_clip_param=5.0, vf_coeff=1.0),
@@ -198,7 +202,8 @@ def gen_ppo_losses() -> None:
             dist = Categorical(TensorDict({"logits": logits}, batch_size=[m]), None)
             with torch.no_grad():
                 logp_old = dist.logp(actions) + torch.randn(m, 1, generator=g) * 0.4
-            finish(f"cat{ncls}_{hname}", dist, actions, logp_old, adv, returns, values, {"logits": logits}, hp)
+            record_ppo_case(arrays, cases, f"cat{ncls}_{hname}", dist, actions, logp_old, adv, returns, values,
+                            {"logits": logits}, hp)
     for dname, dcls in (("normal", Normal), ("squashed", SquashedNormal)):
         for hname, hp in hps.items():
             if dname == "squashed" and hp["entropy_coeff"] != 0:
@@ -215,12 +220,121 @@ def gen_ppo_losses() -> None:
                         # exercise the clamp branch too
                         actions[:4] = torch.tensor([[1.0] * adim, [-1.0] * adim, [0.0] * adim, [0.9999999] * adim])
                     logp_old = dist.logp(actions) + torch.randn(m, 1, generator=g) * 0.4
-                finish(
-                    f"{dname}{adim}_{hname}", dist, actions, logp_old, adv, returns,
+                record_ppo_case(
+                    arrays, cases, f"{dname}{adim}_{hname}", dist, actions, logp_old, adv, returns,
                     values, {"mean": mean, "log_std": log_std}, hp,
                 )
     arrays["cases"] = np.array(cases)
     save("ppo_losses.npz", **arrays)
+
+
+def save_reproducible(name: str, **arrays) -> None:
+    """``save`` with fixed zip member timestamps: the same arrays give the same bytes on every run."""
+    import io
+    import zipfile
+
+    path = os.path.join(HERE, name)
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for k, v in arrays.items():
+            if torch.is_tensor(v):
+                v = v.detach().cpu().numpy()
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            zf.writestr(info, buf.getvalue())
+    print(f"wrote {name}: {os.path.getsize(path)} bytes, {len(arrays)} arrays")
+
+
+def gen_ppo_loss_edges() -> None:
+    """F2b: the loss at its edges -- masked categorical logits (-inf and finfo.min, never on the taken action) with
+    and without the entropy bonus, ratios far beyond the clip and the dual clip, values at the Huber kink, at the
+    value-clip boundary and fully clipped, extreme log_std, squashed actions at +-1 / +-(1 - eps) and rows where the
+    -100 clamp of the squashed log-prob engages.  Every draw, sampled actions included, comes from one seeded
+    generator, and the file is written with fixed timestamps, so a rerun reproduces it byte for byte."""
+    arrays = {}
+    cases = []
+    g = torch.Generator().manual_seed(11)
+    m = 96
+    f32 = torch.finfo(torch.float32)
+
+    def common(kind):
+        adv = torch.randn(m, 1, generator=g) * 2
+        returns = torch.randn(m, 1, generator=g) * 3
+        if kind == "vf":  # |value - return| on both sides of the Huber kink (1) and of vf_clip (2: l = 2 at |d| = 2.5)
+            d = torch.tensor([0.5, 0.999, 1.0, 1.001, 1.5, 2.4, 2.4999, 2.5001, 2.6, 1e3, 1e6])
+            d = d[torch.randint(0, d.numel(), (m, 1), generator=g)] * torch.sign(torch.randn(m, 1, generator=g))
+        else:
+            d = torch.randn(m, 1, generator=g) * 2
+        values = (returns + d).requires_grad_(True)
+        return adv, returns, values
+
+    def log_ratio(kind):
+        if kind == "wide":  # ratios from e^-20 to e^20: past the clip and the dual clip on both signs of the advantage
+            return (torch.rand(m, 1, generator=g) * 40 - 20)
+        return torch.randn(m, 1, generator=g) * 0.4
+
+    cat_hps = {
+        "ent": dict(clip_param=0.2, dual_clip_param=3.0, entropy_coeff=1e-2, vf_clip_param=2.0, vf_coeff=0.5),
+        "noent": dict(clip_param=0.2, dual_clip_param=None, entropy_coeff=0.0, vf_clip_param=2.0, vf_coeff=0.5),
+    }
+    for k, adim, kind in ((5, 1, "masked"), (3, 1, "masked"), (7, 2, "masked"), (3, 1, "wide")):
+        for hname, hp in cat_hps.items():
+            adv, returns, values = common("vf" if kind == "wide" else "plain")
+            logits = torch.randn(m, adim, k, generator=g) * 1.5
+            probs = torch.softmax(logits, -1)
+            actions = torch.multinomial(probs.reshape(-1, k), 1, generator=g).reshape(m, adim)
+            if kind == "masked":  # mask about a third of the other classes, half with -inf, half with finfo.min
+                r = torch.rand(m, adim, k, generator=g)
+                taken = torch.nn.functional.one_hot(actions, k).bool()
+                logits = torch.where((r < 1 / 6) & ~taken, torch.tensor(-float("inf")), logits)
+                logits = torch.where((r >= 1 / 6) & (r < 1 / 3) & ~taken, torch.tensor(f32.min), logits)
+            logits.requires_grad_(True)
+            dist = Categorical(TensorDict({"logits": logits}, batch_size=[m]), None)
+            with torch.no_grad():
+                logp_old = dist.logp(actions) - log_ratio(kind)
+            record_ppo_case(arrays, cases, f"cat{k}a{adim}_{kind}_{hname}", dist, actions, logp_old, adv, returns,
+                            values, {"logits": logits}, hp)
+
+    cont_hps = {
+        "dual": dict(clip_param=0.2, dual_clip_param=3.0, entropy_coeff=0.0, vf_clip_param=2.0, vf_coeff=1.0),
+        "ent": dict(clip_param=0.3, dual_clip_param=None, entropy_coeff=1e-2, vf_clip_param=2.0, vf_coeff=0.5),
+    }
+    eps = f32.eps
+    edge_actions = torch.tensor([1.0, -1.0, 1 - eps, -(1 - eps), 1 - 2 * eps, -(1 - 2 * eps), 0.0])
+    for dname, dcls, adim, kind in (("squashed", SquashedNormal, 1, "clamp"), ("squashed", SquashedNormal, 3, "clamp"),
+                                    ("normal", Normal, 2, "wide"), ("normal", Normal, 1, "wide")):
+        for hname, hp in cont_hps.items():
+            if dname == "squashed" and hp["entropy_coeff"] != 0:
+                continue
+            adv, returns, values = common("vf")
+            if kind == "clamp":
+                # saturated means (|mean| >= 10) and small std next to ordinary rows
+                mean = torch.randn(m, adim, generator=g) * 2
+                mean[: m // 4] = torch.sign(mean[: m // 4]) * (10 + torch.rand(m // 4, adim, generator=g) * 5)
+                log_std = torch.rand(m, adim, generator=g) * 3 - 2.5
+                log_std[m // 4: m // 2] = -6 + torch.rand(m // 4, adim, generator=g)
+            else:
+                mean = torch.randn(m, adim, generator=g)
+                log_std = torch.rand(m, adim, generator=g) * 25 - 20  # [-20, 5]
+            with torch.no_grad():
+                raw = mean + torch.exp(log_std) * torch.randn(m, adim, generator=g)
+                actions = torch.tanh(raw) if dname == "squashed" else raw
+                if dname == "squashed":
+                    pick = torch.randint(0, edge_actions.numel(), (m // 3, adim), generator=g)
+                    actions[m // 2: m // 2 + m // 3] = edge_actions[pick]
+            mean.requires_grad_(True)
+            log_std.requires_grad_(True)
+            feats = TensorDict({"mean": mean, "log_std": log_std}, batch_size=[m])
+            dist = dcls(feats, None)
+            with torch.no_grad():
+                logp_old = dist.logp(actions) - log_ratio("wide" if kind == "wide" else "plain")
+            record_ppo_case(arrays, cases, f"{dname}{adim}_{kind}_{hname}", dist, actions, logp_old, adv, returns,
+                            values, {"mean": mean, "log_std": log_std}, hp)
+    for k, v in arrays.items():
+        assert np.isfinite(np.asarray(v.detach() if torch.is_tensor(v) else v)).all() or k.endswith("feat_logits"), k
+    arrays["cases"] = np.array(cases)
+    save_reproducible("ppo_loss_edges.npz", **arrays)
 
 
 # --------------------------------------------------------------------------- #
@@ -1009,6 +1123,9 @@ def gen_early_stop() -> None:
 
 
 def main() -> None:
+    if len(sys.argv) > 1 and sys.argv[1] == "ppo_loss_edges":
+        gen_ppo_loss_edges()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "first_updates":
         gen_first_updates()
         gen_early_stop()
@@ -1044,6 +1161,7 @@ def main() -> None:
         return
     gen_gae()
     gen_ppo_losses()
+    gen_ppo_loss_edges()
     gen_env_steps()
     gen_classic_env_steps()
     gen_views()

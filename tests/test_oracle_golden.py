@@ -220,3 +220,37 @@ def test_gather_rows():
     perm = oracle.permutation(1000, 7, 3)
     assert sorted(perm.tolist()) == list(range(1000))
     assert not np.array_equal(perm, oracle.permutation(1000, 7, 4))
+
+
+def test_ppo_loss_edges_match_reference_autograd(golden):
+    """ppo_loss_edges.npz: masked logits (-inf, finfo.min) with and without the entropy bonus, ratios e^-20..e^20
+    past both clips, the Huber kink and the vf_clip boundary, log_std in [-20, 5], squashed actions at +-1 and rows
+    whose -100 clamp engages; at the kernel's bars (tests/test_hip_kernels.py::test_ppo_loss_matches_reference_autograd)."""
+    g = golden("ppo_loss_edges.npz")
+    for case in g["cases"]:
+        hp = _hp(g[f"{case}_hparams"])
+        common = (g[f"{case}_values"], g[f"{case}_actions"], g[f"{case}_logp_old"],
+                  g[f"{case}_advantages"], g[f"{case}_returns"])
+        if case.startswith("cat"):
+            logits = g[f"{case}_feat_logits"]
+            losses, g_logits, g_values = oracle.ppo_loss_categorical(logits, *common, hp)
+            want = g[f"{case}_grad_logits"]
+            np.testing.assert_allclose(g_logits, want, rtol=2e-5, atol=1e-8, err_msg=case)
+            masked = logits < -1e38
+            assert masked.any() == ("masked" in case), case
+            assert (g_logits[masked] == 0).all() and (want[masked] == 0).all(), case
+        else:
+            losses, g_mean, g_ls, g_values = oracle.ppo_loss_normal(
+                g[f"{case}_feat_mean"], g[f"{case}_feat_log_std"], *common, hp,
+                squashed=case.startswith("squashed"),
+            )
+            for got, name in ((g_mean, "grad_mean"), (g_ls, "grad_log_std")):
+                want = g[f"{case}_{name}"]
+                np.testing.assert_allclose(got, want, rtol=2e-5, atol=1e-6 * float(np.abs(want).max()),
+                                           err_msg=f"{case} {name}")
+                if case.startswith("squashed"):  # the -100 clamp engaged: no policy gradient through mean / log_std
+                    assert ((want == 0) == (got == 0)).all() and (want == 0).sum() >= 8, (case, name)
+        np.testing.assert_allclose(g_values, g[f"{case}_grad_values"], rtol=2e-5, atol=1e-9, err_msg=case)
+        assert (g_values[np.abs(g[f"{case}_values"] - g[f"{case}_returns"]) > 100] == 0).all(), case
+        for i, k in enumerate(oracle.LOSS_KEYS):
+            assert losses[k] == pytest.approx(g[f"{case}_losses"][i], rel=1e-5, abs=1e-7), (case, k)
