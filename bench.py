@@ -3,6 +3,7 @@
 all ``AlgorithmConfig`` defaults (BASELINE.json configs[1]).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --full                        # + uninstrumented steps, secondary configs, CPU baseline
     python bench.py --gpus 8                      # starts its own 8 ranks (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
@@ -32,8 +33,16 @@ conventions under ``config.scaling_conventions``.  Either way the environments
 are sharded and the only traffic between ranks is the RCCL all-reduce of moments
 and of [gradient | loss sums] per optimizer step.
 
-Secondary configurations. With the headline configuration on one GPU (the
-defaults) the line also carries ``secondary``: BASELINE configs[2..4] --
+Plain and full runs. A plain run does what the headline figure needs and no
+more: set up, ``--warmup`` untimed steps, ``--steps`` timed steps, the outputs
+of ``--dump-outputs``, the JSON line (its ``roofline`` and ``kernels`` come from
+the timers of the timed steps themselves). ``--full`` measures the rest as well,
+after the timed region in the same process (``resolve_extras``): 10 more steps
+with the kernel timers off (``value_uninstrumented``), the secondary
+configurations and the CPU baseline.
+
+Secondary configurations. With ``--full`` and the headline configuration on one
+GPU (the defaults) the line also carries ``secondary``: BASELINE configs[2..4] --
 CartPole 2^18 x 128, ContinuousDummyEnv + SquashedNormal 2^20 x 32, the
 recurrent algorithm at 2^16 x 256 -- measured after the headline's timed region
 in the same process, a few steps each under the same timing rules (value,
@@ -55,7 +64,7 @@ Besides the contract's fields, the JSON line carries
   kernels       the same for every hand kernel that ran;
   cpu_baseline  the CPU restatement (oracle/, kind "port") of the same algorithm
                 on the host cores, best of a thread-count sweep, on a bounded
-                sample (rank 0, N=1 only);
+                sample (``--full``, rank 0, N=1 only);
   world_size / backend / collectives_per_step   as ``torch.distributed`` saw them;
   rank_ms_per_step       every rank's own time per step (min / max / list): a
                          straggler shows here, ``ms_per_step`` is the max.
@@ -251,15 +260,20 @@ def parse_args(argv: None | list[str] = None) -> argparse.Namespace:
                    help="matrix (default, the product): the MFMA tower kernels.  piecewise: OPT-IN round-4 prototype for scalar"
                         " observations only (rl8_amd/nn/piecewise_mlp.py: each tower as an exact piecewise-linear table) -- a"
                         " labelled extra line, never the headline")
-    p.add_argument("--uninstrumented-steps", type=int, default=10,
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: --uninstrumented-steps more steps with the"
+                        " kernel timers off, the secondary configurations and the CPU baseline (see resolve_extras). Without"
+                        " it a run sets up, warms up, times --steps, writes --dump-outputs and prints the line")
+    p.add_argument("--uninstrumented-steps", type=int, default=None,
                    help="after the timed region: this many more steps with the per-kernel HIP-event timers OFF, reported as"
-                        " value_uninstrumented / ms_per_step_uninstrumented beside the headline (0: skip)")
+                        " value_uninstrumented / ms_per_step_uninstrumented beside the headline (default: 10 with --full,"
+                        " else 0 = skip)")
     p.add_argument("--cpu-baseline-seconds", type=float, default=120.0,
                    help="cap on the CPU baseline's wall time (3 sweep points + 10 timed iterations take ~65 s on the GPU hosts)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--secondary", dest="secondary", action="store_true", default=None,
                    help="after the headline (N = 1): BASELINE configs[2..4] on this one device, a few steps each, under the"
-                        " line's `secondary` key (default: on when the run IS the headline configuration)")
+                        " line's `secondary` key (default: on with --full when the run IS the headline configuration)")
     p.add_argument("--no-secondary", dest="secondary", action="store_false")
     p.add_argument("--secondary-steps", type=int, default=3)
     p.add_argument("--secondary-warmup", type=int, default=1)
@@ -510,6 +524,22 @@ def main() -> None:
     run(args)
 
 
+def resolve_extras(args: argparse.Namespace, world: int) -> None:
+    """Decide what the run measures besides the headline.  A plain run measures nothing else: set-up, ``--warmup``
+    untimed and ``--steps`` timed steps, ``--dump-outputs``, the line.  ``--full`` adds ``--uninstrumented-steps``
+    (10) more steps with the kernel timers off, the secondary configurations when the run is the headline
+    configuration, and the CPU baseline (unless ``--no-cpu-baseline``); the last two on one device only.  An explicit
+    ``--uninstrumented-steps`` / ``--secondary`` holds with or without ``--full``."""
+    if args.uninstrumented_steps is None:
+        args.uninstrumented_steps = 10 if args.full else 0
+    if args.secondary is None:
+        args.secondary = (args.full and args.env == "discrete" and args.distribution == "default" and not args.recurrent
+                          and args.num_envs == 1 << 20 and args.horizon == 32 and args.minibatches == 1
+                          and args.towers == "matrix")
+    args.secondary = world == 1 and args.secondary
+    args.cpu_baseline = world == 1 and args.full and not args.no_cpu_baseline
+
+
 def run(args: argparse.Namespace) -> None:
     import torch
     import torch.distributed as dist
@@ -550,16 +580,13 @@ def run(args: argparse.Namespace) -> None:
               f"{os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY')}", file=sys.stderr, flush=True)
     # no HIP device / no librl8_amd.so: AlgorithmConfig.build() raises HipExtensionError below
 
-    if args.secondary is None:  # default: with the headline configuration itself, on one device
-        args.secondary = (world == 1 and args.env == "discrete" and args.distribution == "default" and not args.recurrent
-                          and args.num_envs == 1 << 20 and args.horizon == 32 and args.minibatches == 1
-                          and args.towers == "matrix")
+    resolve_extras(args, world)
     m = measure(args, world, backend)
     if rank == 0:
         line = headline(args, m, world, backend)
-        if world == 1 and args.secondary:
+        if args.secondary:
             line["secondary"] = secondary_lines(args, world, backend)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_baseline_seconds)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -80,6 +80,60 @@ def test_strong_and_weak_arguments():
     assert bench.parse_args([]).scaling == "weak" and bench.parse_args([]).gpus == 1
 
 
+def test_plain_run_resolves_no_extras_and_full_run_all_of_them():
+    def extras(argv, world=1):
+        a = bench.parse_args(argv)
+        bench.resolve_extras(a, world)
+        return a.uninstrumented_steps, a.secondary, a.cpu_baseline
+
+    assert not bench.parse_args([]).full
+    assert extras([]) == (0, False, False)
+    assert extras(["--steps", "20", "--warmup", "5"]) == (0, False, False)
+    assert extras(["--full"]) == (10, True, True)
+    assert extras(["--full", "--no-secondary", "--no-cpu-baseline"]) == (10, False, False)
+    assert extras(["--full", "--env", "cartpole", "--num-envs", "262144", "--horizon", "128"]) == (10, False, True)
+    assert extras(["--full", "--gpus", "2"], world=2) == (10, False, False)   # secondary and CPU baseline: N = 1 only
+    assert extras(["--uninstrumented-steps", "3"]) == (3, False, False)       # explicit options hold either way
+    assert extras(["--full", "--uninstrumented-steps", "0"]) == (0, True, True)
+    assert extras(["--secondary"]) == (0, True, False)
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_plain_run_measures_only_the_headline(monkeypatch, capsys, full):
+    """A plain run measures the headline configuration once, with no steps after the timed ones, and prints its line
+    without the secondary block or the CPU baseline; --full adds all three as before."""
+    import torch
+
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)   # (run() itself touches no device then)
+    calls = []
+
+    def measure(args, world, backend):
+        calls.append((args.steps, args.warmup, args.uninstrumented_steps))
+        hbm = {"bound": "hbm", "launches": 4, "avg_ms": 0.25, "total_ms": 1.0, "algorithmic_bytes_per_launch": 1e9,
+               "achieved_GBps": 4000.0, "frac_of_8TBps": 0.5, "pmc_traffic_bytes_per_launch": None}
+        return {"kernels": {"ppo_loss_categorical": hbm}, "elapsed": 2.0,
+                "plain_elapsed": 1.5 if args.uninstrumented_steps else None, "rank_elapsed": [2.0],
+                "collect_ms": 100.0, "step_ms": 300.0, "global_envs": 1 << 20, "envs_per_gpu": 1 << 20, "horizon": 32,
+                "env_name": "DiscreteDummyEnv", "num_sgd_iters": 4, "num_minibatches": 1, "collectives": 0,
+                "piecewise": None, "max_memory_allocated_GB": 7.0, "dumped": None}
+
+    monkeypatch.setattr(bench, "measure", measure)
+    monkeypatch.setattr(bench, "secondary_lines", lambda *a: calls.append("secondary") or {"cfg3": {}})
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a: calls.append("cpu_baseline") or {"value": 1.0})
+    bench.run(bench.parse_args(["--gpus", "1", "--steps", "10", "--warmup", "3"] + (["--full"] if full else [])))
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line["value"] == (1 << 20) * 32 * 10 / 2.0 and line["ms_per_step"] == 200.0
+    assert line["metric"].startswith("env transitions/sec") and line["unit"] == "env transitions/sec"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32"
+    if full:
+        assert calls == [(10, 3, 10), "secondary", "cpu_baseline"]
+        assert "secondary" in line and "cpu_baseline" in line and line["uninstrumented_steps"] == 10
+    else:
+        assert calls == [(10, 3, 0)]
+        assert "secondary" not in line and "cpu_baseline" not in line
+        assert line["value_uninstrumented"] is None and line["uninstrumented_steps"] == 0
+
+
 def test_dump_outputs_writes_the_last_steps_results(tmp_path):
     """--dump-outputs: stats (timings left out) as float64, parameters as float32, a seeded sample of the final
     observations; two dumps of the same state are identical file for file."""

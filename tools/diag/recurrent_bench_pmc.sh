@@ -1,11 +1,14 @@
 # Fabric request counters of every kernel of the recurrent bench (kernel trace only), summarised per kernel.
-R=$PWD; cd /tmp && export TMPDIR=/tmp
+# Run from the repository root; the profiler's output goes under the directory given as first argument
+# (default build/measurements).
+R=$PWD; mkdir -p "${1:-build/measurements}" && OUT=$(cd "${1:-build/measurements}" && pwd) || exit 1
+cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum --kernel-trace --output-format csv \
-    -d $R/gpurun_out/rb_pmc -o p -- python3 $R/bench.py --recurrent --num-envs 8192 --horizon 256 --steps 1 --warmup 1 --no-cpu-baseline > $R/gpurun_out/rb_pmc.log 2>&1
+    -d "$OUT/rb_pmc" -o p -- python3 $R/bench.py --full --recurrent --num-envs 8192 --horizon 256 --steps 1 --warmup 1 --no-cpu-baseline > "$OUT/rb_pmc.log" 2>&1
 echo rc=$?
-cd $R && python3 - <<'PY'
-import csv, collections, glob
-f = glob.glob("gpurun_out/rb_pmc/*counter_collection.csv")[0]
+cd $R && RB_PMC="$OUT/rb_pmc" python3 - <<'PY'
+import csv, collections, glob, os
+f = glob.glob(os.path.join(os.environ["RB_PMC"], "*counter_collection.csv"))[0]
 # One line per (kernel, grid size): a kernel launched at several sizes (the heads: 2^21 training rows, 8 192 bootstrap
 # rows) must not be averaged across them -- round 3's summary did, and bench.py then scaled a 1.56 GB "per launch"
 # that was 8/11 of the training launch's 2.17 GB (a traffic ratio of 0.73).
