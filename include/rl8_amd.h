@@ -675,6 +675,27 @@ int rl8_linear_heads_backward_f32(const float *h, const float *dout, int64_t m, 
                                   int n_out, float *dh_out, float *partials,
                                   int *partial_rows_out /*host*/, void *stream);
 
+/* ---- Narrow towers: Linear(d_in, H) ReLU Linear(H, H) ReLU Linear(H, n_out), H = 64 or 128 (mlp_narrow_kernels.hip).
+ * Weights in torch layout, unpacked: w1 [H][d_in], b1 [H], w2 [H][H], b2 [H], w3 [n_out][H], b3 [n_out]; d_in <= 16,
+ * n_out <= 8.  Layer 2 (and, backward, dh1 and dW2) on fp32 MFMA; no activation goes to HBM.
+ * rl8_mlp_narrow_supports: 1 when (hidden, d_in, n_out) is compiled in, else 0.
+ * rl8_mlp_narrow_forward_f32: x [m][d_in] -> out [m][n_out].
+ * rl8_mlp_narrow_backward_f32: recomputes the forward from x and writes one partial slab of gradients per workgroup
+ *   into `workspace` (rl8_mlp_narrow_workspace_bytes(m, ...) bytes, no initialisation); rl8_mlp_narrow_reduce_f32
+ *   then sums the slabs in a fixed order (fp64) into grads_out = [dW1 (H d_in) | db1 (H) | dW2 (H H) | db2 (H) |
+ *   dW3 (n_out H) | db3 (n_out)] floats: bitwise reproducible.  No gradient is produced for x.
+ * All pointers 4-byte aligned; m >= 1; RL8_ESIZE for widths outside the compiled set. */
+int rl8_mlp_narrow_supports(int hidden, int d_in, int n_out);
+int64_t rl8_mlp_narrow_workspace_bytes(int64_t m, int hidden, int d_in, int n_out);
+int rl8_mlp_narrow_forward_f32(const float *x, int64_t m, int d_in, const float *w1, const float *b1, const float *w2,
+                               const float *b2, const float *w3, const float *b3, int n_out, int hidden, float *out,
+                               void *stream);
+int rl8_mlp_narrow_backward_f32(const float *x, const float *dout, int64_t m, int d_in, const float *w1,
+                                const float *b1, const float *w2, const float *b2, const float *w3, int n_out,
+                                int hidden, float *workspace, void *stream);
+int rl8_mlp_narrow_reduce_f32(const float *workspace, int64_t m, int hidden, int d_in, int n_out, float *grads_out,
+                              void *stream);
+
 /* ---- OPT-IN: towers of a SCALAR observation as exact piecewise-linear tables (round 4 prototype; VERDICT r3 item 10,
  * DESIGN.md section 9).  Special to d_in = 1 -- the dummy envs of BASELINE configs 2 and 4 -- and never a replacement
  * for the general tower kernels above, which every other shape runs and against which this path is tested.  The

@@ -173,6 +173,11 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_mlp_wgrad_fused_split_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp],
     "rl8_mlp_wgrad_workspace_bytes": [],
     "rl8_mlp_wgrad_f32": [_vp, _vp, _i64, _vp, _vp, _i32, _vp],
+    "rl8_mlp_narrow_supports": [_i32, _i32, _i32],
+    "rl8_mlp_narrow_workspace_bytes": [_i64, _i32, _i32, _i32],
+    "rl8_mlp_narrow_forward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "rl8_mlp_narrow_backward_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "rl8_mlp_narrow_reduce_f32": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
 }
 
 
@@ -204,7 +209,8 @@ def load() -> C.CDLL:
                 if name in ("rl8_scratch_bytes", "rl8_mlp_backward_partial_floats", "rl8_mlp_wgrad_workspace_bytes",
                             "rl8_lstm_pack_floats", "rl8_lstm_backward_partial_floats",
                             "rl8_lstm_split_packed_bytes", "rl8_lstm_split_wb_floats", "rl8_lstm_split_state_bytes",
-                            "rl8_mlp_f16_packed_bytes", "rl8_lstm_rows_backward_pack_bytes", "rl8_pw_workspace_bytes")
+                            "rl8_mlp_f16_packed_bytes", "rl8_lstm_rows_backward_pack_bytes", "rl8_pw_workspace_bytes",
+                            "rl8_mlp_narrow_workspace_bytes")
                 else C.c_int
             )
         built = int(lib.rl8_abi_version(None, 0))
@@ -1189,6 +1195,76 @@ def mlp_wgrad(dz2: torch.Tensor, h1: torch.Tensor) -> torch.Tensor:
         _check(lib.rl8_mlp_wgrad_f32(_ptr(dz2), _ptr(h1), dz2.shape[0], _ptr(ws), _ptr(out), 0, _stream()),
                "rl8_mlp_wgrad_f32")
     return out
+
+
+# --------------------------------------------------------------------------- #
+# Narrow towers: hidden width 64 or 128 (mlp_narrow_kernels.hip).
+# --------------------------------------------------------------------------- #
+MLP_NARROW_HIDDEN = (64, 128)
+
+
+def mlp_narrow_supports(hidden: int, d_in: int, n_out: int) -> bool:
+    return bool(load().rl8_mlp_narrow_supports(hidden, d_in, n_out))
+
+
+def _narrow_params(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                   w3: torch.Tensor, b3: None | torch.Tensor) -> tuple[int, int, int, int]:
+    """(m, d_in, hidden, n_out) after the dtype / contiguity / shape checks of the narrow entries."""
+    _dense(x, torch.float32, "x")
+    if x.ndim != 2:
+        raise ValueError("x must be [M, d_in]")
+    m, d_in = x.shape
+    hidden, n_out = w1.shape[0], w3.shape[0]
+    shapes = (("w1", w1, (hidden, d_in)), ("b1", b1, (hidden,)), ("w2", w2, (hidden, hidden)), ("b2", b2, (hidden,)),
+              ("w3", w3, (n_out, hidden)), ("b3", b3, (n_out,)))
+    for name, t, shape in shapes:
+        if t is None:
+            continue
+        _dense(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    if m < 1 or not mlp_narrow_supports(hidden, d_in, n_out):
+        raise ValueError(f"no narrow tower kernel for m={m}, hidden={hidden}, d_in={d_in}, n_out={n_out}")
+    return m, d_in, hidden, n_out
+
+
+def mlp_narrow_forward(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                       w3: torch.Tensor, b3: torch.Tensor) -> torch.Tensor:
+    """out [M, n_out] = relu(relu(x w1^T + b1) w2^T + b2) w3^T + b3 for hidden width 64 or 128 (nothing saved)."""
+    x, w1, b1, w2, b2, w3, b3 = (t.detach() for t in (x, w1, b1, w2, b2, w3, b3))
+    m, d_in, hidden, n_out = _narrow_params(x, w1, b1, w2, b2, w3, b3)
+    out = torch.empty(m, n_out, dtype=torch.float32, device=x.device)
+    with _timed("mlp_narrow_forward", m):
+        _check(load().rl8_mlp_narrow_forward_f32(_ptr(x), m, d_in, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(w3),
+                                                 _ptr(b3), n_out, hidden, _ptr(out), _stream()),
+               "rl8_mlp_narrow_forward_f32")
+    return out
+
+
+def mlp_narrow_backward(x: torch.Tensor, dout: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
+                        b2: torch.Tensor, w3: torch.Tensor) -> dict[str, torch.Tensor]:
+    """Gradients of the six tower parameters ("w1", "b1", "w2", "b2", "w3", "b3") for the output gradient ``dout``
+    [M, n_out]: the forward recomputed from x, partial slabs per workgroup summed in a fixed order (deterministic)."""
+    x, dout, w1, b1, w2, b2, w3 = (t.detach() for t in (x, dout, w1, b1, w2, b2, w3))
+    m, d_in, hidden, n_out = _narrow_params(x, w1, b1, w2, b2, w3, None)
+    _dense(dout, torch.float32, "dout")
+    if tuple(dout.shape) != (m, n_out):
+        raise ValueError(f"dout must have shape {(m, n_out)}, got {tuple(dout.shape)}")
+    lib = load()
+    ws = torch.empty(int(lib.rl8_mlp_narrow_workspace_bytes(m, hidden, d_in, n_out)) // 4, dtype=torch.float32,
+                     device=x.device)
+    sizes = (hidden * d_in, hidden, hidden * hidden, hidden, n_out * hidden, n_out)
+    grads = torch.empty(sum(sizes), dtype=torch.float32, device=x.device)
+    with _timed("mlp_narrow_backward", m):
+        _check(lib.rl8_mlp_narrow_backward_f32(_ptr(x), _ptr(dout), m, d_in, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
+                                               _ptr(w3), n_out, hidden, _ptr(ws), _stream()),
+               "rl8_mlp_narrow_backward_f32")
+    with _timed("mlp_narrow_reduce", m):
+        _check(lib.rl8_mlp_narrow_reduce_f32(_ptr(ws), m, hidden, d_in, n_out, _ptr(grads), _stream()),
+               "rl8_mlp_narrow_reduce_f32")
+    parts = torch.split(grads, sizes)
+    shapes = ((hidden, d_in), (hidden,), (hidden, hidden), (hidden,), (n_out, hidden), (n_out,))
+    return {k: p.view(s) for k, p, s in zip(("w1", "b1", "w2", "b2", "w3", "b3"), parts, shapes)}
 
 
 # --------------------------------------------------------------------------- #

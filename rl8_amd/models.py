@@ -2,9 +2,9 @@
 ``src/rl8/models/_feedforward.py`` (``Model`` :20-203, ``DefaultContinuousModel``
 :234-310, ``DefaultDiscreteModel`` :313-383) and ``src/rl8/nn/modules/mlp.py``.
 
-The arithmetic stays on PyTorch-ROCm (rocBLAS / hipBLASLt GEMMs), as the
-north_star specifies: this build's hand-written kernels are the memory-bound
-ops around the networks, not the networks. Module structure (and therefore
+The default towers -- two ReLU layers of width 256, or 64 / 128 -- run as fused
+gfx950 kernels through ``nn.fused_mlp.tower_forward``; any other configuration
+runs the modules eagerly on PyTorch-ROCm. Module structure (and therefore
 ``state_dict`` keys) matches the reference so its checkpoints load unchanged.
 
 """

@@ -8,8 +8,13 @@ per call) -- instead of ~8 (forward) / ~20 (backward) eager launches whose 256-w
 activations each make an HBM round trip. Parameters stay ordinary ``torch.nn.Linear``
 weights; this module only changes how the tower is evaluated.
 
+Towers of hidden width 64 or 128 (same structure, ``d_in <= 16``, ``n_out <= 8``) run
+their own kernel family (``mlp_narrow_kernels.hip``, ``_NarrowTower``): fp32 MFMA for
+layer 2, nothing saved by the forward, activations recomputed by the one backward
+kernel.  They are never recorded for rollout replay.
+
 ``tower_forward`` falls back to the module's own eager path whenever the tower
-is not exactly that shape (other widths, activations, norm layers, non-HIP or
+is none of these shapes (other widths, activations, norm layers, non-HIP or
 non-fp32 inputs), so custom models are unaffected.
 
 Under ``enable_amp`` (torch autocast) the fused towers still run, at fp32 accuracy: that is
@@ -483,6 +488,45 @@ def _match(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[nn.Line
     return l1, l2
 
 
+def _match_narrow(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[nn.Linear, nn.Linear]:
+    """(layer1, layer2) if ``trunk`` is ``Sequential(MLP(Linear, ReLU, Linear), ReLU)`` with biased layers of one
+    width in ``hip.MLP_NARROW_HIDDEN`` and heads that read that width (``mlp_narrow_kernels.hip``)."""
+    if not isinstance(trunk, nn.Sequential) or len(trunk) < 2:
+        return None
+    mlp, act = trunk[0], trunk[1]
+    if not isinstance(mlp, nn.Sequential) or len(mlp) != 3 or not isinstance(act, nn.ReLU):
+        return None
+    l1, a1, l2 = mlp[0], mlp[1], mlp[2]
+    if not (isinstance(l1, nn.Linear) and isinstance(a1, nn.ReLU) and isinstance(l2, nn.Linear)):
+        return None
+    width = l1.out_features
+    if width not in hip.MLP_NARROW_HIDDEN or l2.in_features != width or l2.out_features != width:
+        return None
+    if l1.in_features > hip.MLP_MAX_IN or l1.bias is None or l2.bias is None:
+        return None
+    if not heads or sum(h.out_features for h in heads) > hip.MLP_MAX_OUT or any(h.bias is None for h in heads):
+        return None
+    if any(h.in_features != width for h in heads):
+        return None
+    return l1, l2
+
+
+class _NarrowTower(torch.autograd.Function):
+    """A narrow tower (hidden width 64 / 128): one forward kernel that saves nothing, one backward kernel that
+    recomputes the activations from x, and the fixed-order reduction of its partial gradients."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3):  # type: ignore[override]
+        ctx.save_for_backward(x, w1, b1, w2, b2, w3, b3)
+        return hip.mlp_narrow_forward(x, w1, b1, w2, b2, w3, b3)
+
+    @staticmethod
+    def backward(ctx, dout):  # type: ignore[override]
+        x, w1, b1, w2, b2, w3, _ = ctx.saved_tensors
+        g = hip.mlp_narrow_backward(x, dout.contiguous().float(), w1, b1, w2, b2, w3)
+        return None, g["w1"], g["b1"], g["w2"], g["b2"], g["w3"], g["b3"]
+
+
 def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Tensor, *,
                   pair_gradients: None | bool = None) -> None | torch.Tensor:
     """``cat([head(trunk(x)) for head in heads], -1)`` through the fused kernels,
@@ -495,6 +539,14 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
     ``Algorithm``). Checked on the device in the backward either way."""
     if not ENABLED or not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
         return None
+    narrow = _match_narrow(trunk, heads)
+    if narrow is not None:  # (never recorded or replayed: everything below assumes width 256)
+        l1, l2 = narrow
+        if x.shape[1] != l1.in_features:
+            return None
+        w3 = heads[0].weight if len(heads) == 1 else torch.cat([h.weight for h in heads], 0)
+        b3 = heads[0].bias if len(heads) == 1 else torch.cat([h.bias for h in heads], 0)
+        return _NarrowTower.apply(x.contiguous(), l1.weight, l1.bias, l2.weight, l2.bias, w3, b3)
     layers = _match(trunk, heads)
     if layers is None or x.shape[1] != layers[0].in_features:
         return None
