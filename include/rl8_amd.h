@@ -38,12 +38,20 @@
  *                rl8_lstm_rows_backward_pack, rl8_lstm_rows_backward[_heads]_f32, rl8_lstm_wgrad_f16_f32,
  *                rl8_linear_heads_{forward,forward_pair,backward}_f32
  *   PRODUCT, fallback (shapes outside the plane kernels' envelope -- d_in > 16, n_out > 8, hidden != 256 go to eager --
- *   or a switch: RL8_AMD_TOWER_GEMM=f32, RL8_AMD_LSTM_GEMM=f32, RL8_WGRAD_PLANES=bf16, RL8_AMD_LSTM_WGRAD_PLANES=bf16,
- *   RL8_AMD_LSTM_BACKWARD_ROWS=0), and THE YARDSTICK the parity tests hold the plane kernels against beside fp64:
+ *   or a switch: RL8_AMD_TOWER_GEMM=f32, RL8_WGRAD_PLANES=bf16, the LSTM switches below), and THE YARDSTICK the parity
+ *   tests hold the plane kernels against beside fp64:
  *     rl8_mlp_tower_forward_f32, rl8_mlp_tower_backward_f32, rl8_mlp_wgrad_f32, rl8_mlp_wgrad_split_f32,
  *     rl8_mlp_pack_w2_f32, rl8_lstm_pack_f32, rl8_lstm_forward_f32, rl8_lstm_backward_f32,
  *     rl8_mlp_wgrad_strided_f32, rl8_mlp_wgrad_split_strided_f32, rl8_mlp_wgrad_f16_strided_f32 (one gate per launch)
  *   OPT-IN prototype (RL8_AMD_TOWERS=piecewise; never the default, never the headline): rl8_pw_*
+ * The LSTM switches and where each is read.  rl8_amd/nn/fused_lstm.py reads RL8_AMD_LSTM_GEMM=f32 (the fp32-MFMA step
+ * kernel, backward and weight gradient), RL8_AMD_LSTM_BACKWARD_ROWS=0 (the fp32-MFMA backward through time, the bf16-plane
+ * weight gradient) and RL8_AMD_LSTM_FUSE_HEADS=0 (LSTM and heads as two autograd nodes) at import, into module attributes;
+ * fused_lstm._plan reads those and RL8_AMD_LSTM_WGRAD_PLANES=bf16 (the bf16-plane weight gradient) and
+ * RL8_AMD_LSTM_WGRAD_GATES=separate (one weight-gradient launch per gate) on every call, once for a forward and its
+ * backward.  RL8_AMD_ROLLOUT_FUSE_HEADS=0 (the lean recurrent rollout's heads in launches of their own) is read by
+ * fused_lstm when a rollout is set up; RL8_AMD_LSTM_BACKWARD_PLANES=bf16 (the heads form of the backward through time on
+ * three bf16 planes instead of two fp16 ones) by rl8_lstm_rows_backward_heads_f32 itself, on every call.
  */
 #ifndef RL8_AMD_H
 #define RL8_AMD_H

@@ -25,7 +25,6 @@ the backward-through-time kernel.
 
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass
 from typing import Any
 
@@ -79,11 +78,11 @@ class _LeanRollout:
         self.d_in = int(tm[DataKeys.OBS].shape[-1])
         self.k = int(model.feature_head.out_features)
         dev = tm[DataKeys.OBS].device
-        self.split = fused_lstm.use_split(model.lstm)
+        self.split = fused_lstm._plan(model.lstm.input_size, n).forward_planes
         if self.split:  # bf16-plane step kernel: W_hh planes, [w_ih | bias] rows, planes of h_{t-1}
             self.packed, self.wb = fused_lstm._packs(model.lstm, "split")
         else:
-            self.packed, self.wb = fused_lstm._packs(model.lstm, False), None
+            self.packed, self.wb = fused_lstm._packs(model.lstm, "step"), None
         # parameters are leaf tensors: .detach() shares storage (kept alive on self)
         self.params = [p.detach().contiguous() for p in (model.feature_head.weight, model.feature_head.bias,
                                                          model.vf_head.weight, model.vf_head.bias)]
@@ -111,8 +110,8 @@ class _LeanRollout:
         self.split_ptrs = (self.planes.data_ptr(), self.wb.data_ptr() if self.wb is not None else None)
         self.planes_half = self.planes.numel() // 2
         self.planes_of = -1   # timestep whose hidden state the planes buffer (t & 1) holds (-1: none)
-        # two-way categorical + value head: evaluated inside the timestep's last kernel (RL8_AMD_ROLLOUT_FUSE_HEADS=0: two launches)
-        self.fuse_heads = self.k == 2 and os.environ.get("RL8_AMD_ROLLOUT_FUSE_HEADS", "1") != "0"
+        # two-way categorical + value head: evaluated inside the timestep's last kernel (switched off: two launches)
+        self.fuse_heads = self.k == 2 and fused_lstm._rollout_fuse_heads()
 
     @staticmethod
     def available(algo: "RecurrentAlgorithm") -> bool:

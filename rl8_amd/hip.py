@@ -1528,26 +1528,29 @@ def lstm_rows_backward(c0: torch.Tensor, gates: torch.Tensor, cs: torch.Tensor, 
     return (dgates, bound) if with_bound else dgates
 
 
-#: column-sum partial rows of the fused LSTM weight gradient, per (device, stream, L, d_in)
+#: column-sum partial rows of the plane LSTM weight gradients, per (device, stream, L, d_in[, "gates"])
 _lstm_colsum_ws: dict[tuple, torch.Tensor] = {}
+#: fewest sequences the four-gate weight-gradient launch takes (rl8_lstm_wgrad_f16_f32)
+LSTM_WGRAD_GATES_MIN_ROWS = 128
 
 
 def lstm_backward(
     x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, hs: torch.Tensor, gates: torch.Tensor, cs: torch.Tensor,
-    dhs: None | torch.Tensor, whht_packed: None | torch.Tensor, *, split: None | bool = None,
+    dhs: None | torch.Tensor, whht_packed: None | torch.Tensor, *, wgrad: None | str = None, split: bool = True,
     rows_packed: None | torch.Tensor = None, h0_bound: None | torch.Tensor = None,
     heads: None | tuple[torch.Tensor, torch.Tensor] = None, hs_bound: None | float = None,
 ) -> dict[str, torch.Tensor]:
     """Parameter gradients of the LSTM given ``dhs`` [B, L, 256] (gradient of every
     ``h_t``) and what ``lstm_forward(..., save=True)`` returned. Returns ``w_ih``,
-    ``w_hh``, ``b`` (the gradient of each of the two bias vectors). ``split``: the
-    weight-gradient GEMMs on bf16 planes (True) or the fp32 MFMA (False); the caller
-    passes the mode its forward ran in (``fused_lstm.use_split``), None reads
-    ``RL8_AMD_LSTM_GEMM`` as the forward's module switch does at import.
+    ``w_hh``, ``b`` (the gradient of each of the two bias vectors). ``wgrad``: the weight
+    gradient's route (``fused_lstm._plan``) -- "f16-gates" (four gates per launch, from
+    ``LSTM_WGRAD_GATES_MIN_ROWS`` sequences) or "f16" (one) on fp16 planes scaled by the bound on
+    |dG| the ``rows_packed`` kernel leaves, "bf16" on exact planes (these three sum dW_ih and the
+    bias too, at the widths of :func:`lstm_split_supports`), "f32" on the fp32 MFMA. None: "f32"
+    with ``split=False``, else the fp16 routes behind ``rows_packed``, "bf16" behind ``whht_packed``.
     ``rows_packed`` (:func:`lstm_rows_backward_pack`): the backward through time runs
     on bf16 planes too (``rl8_lstm_rows_backward_f32``) instead of the fp32-MFMA kernel
-    that reads ``whht_packed``; only with ``split`` (its dW_ih / bias sums come from the
-    weight-gradient kernel). ``h0_bound``: one float32 element >= max |h0| when the caller
+    that reads ``whht_packed``. ``h0_bound``: one float32 element >= max |h0| when the caller
     has it (:func:`lstm_forward_split`'s ``h0_bound_out``); computed here otherwise.
     ``heads`` (with ``rows_packed``, ``dhs`` None): see :func:`lstm_rows_backward`.
     ``hs_bound``: a number >= max |hs| the caller vouches for -- 1.0 when ``hs`` is this LSTM's own output
@@ -1563,101 +1566,74 @@ def lstm_backward(
         _dense(t, torch.float32, name)
         if tuple(t.shape) != shape:
             raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
-    lib = load()
-    dev = x.device
-    H = LSTM_HIDDEN
-    if split is None:
-        split = os.environ.get("RL8_AMD_LSTM_GEMM", "split") == "split"
-    # With the bf16-plane weight-gradient kernel and a compiled input width, dW_ih and the
-    # bias gradient come out of that kernel as column sums of the dG it reads anyway; else
-    # the backward call makes one more pass over dG for them.
-    fused_colsums = split and lstm_split_supports(d_in)
-    rows = C.c_int(0)
-    partials = None
-    dg_bound = None
+    if wgrad is None:
+        wgrad = ("f32" if not split else "bf16" if rows_packed is None else
+                 "f16-gates" if b >= LSTM_WGRAD_GATES_MIN_ROWS else "f16")
+    name = {"f16-gates": "rl8_lstm_wgrad_f16_f32", "f16": "rl8_mlp_wgrad_f16_strided_f32",  # the route's entry point
+            "bf16": "rl8_mlp_wgrad_split_strided_f32", "f32": "rl8_mlp_wgrad_strided_f32"}.get(wgrad)
+    if name is None:
+        raise ValueError(f"lstm_backward: wgrad must be 'f16-gates', 'f16', 'bf16' or 'f32', got {wgrad!r}")
+    planes, f16, four_gates = wgrad != "f32", wgrad in ("f16", "f16-gates"), wgrad == "f16-gates"
+    if rows_packed is not None and not planes:
+        raise ValueError("rows_packed needs a plane weight gradient (wgrad 'bf16', 'f16' or 'f16-gates')")
+    if f16 and rows_packed is None:
+        raise ValueError(f"wgrad {wgrad!r} needs rows_packed: its planes are scaled by the rows kernel's bound on |dG|")
+    lib, dev, H = load(), x.device, LSTM_HIDDEN
+    rows, partials = C.c_int(0), None
     if rows_packed is not None:
-        if not fused_colsums:
-            raise ValueError("rows_packed needs the bf16-plane weight gradient (split) and a compiled input width")
         dgates, dg_bound = lstm_rows_backward(c0, gates, cs, dhs, rows_packed, with_bound=True, heads=heads)
     else:
         dgates = torch.empty(b, l, 4, H, dtype=torch.float32, device=dev)
-        if not fused_colsums:
-            width = int(lib.rl8_lstm_backward_partial_floats(d_in))
-            partials = torch.empty(int(lib.rl8_lstm_backward_max_rows()), width, dtype=torch.float32, device=dev)
+        if not planes:  # dW_ih and the bias come out of this kernel's partials
+            partials = torch.empty(int(lib.rl8_lstm_backward_max_rows()), int(lib.rl8_lstm_backward_partial_floats(d_in)),
+                                   dtype=torch.float32, device=dev)
         with _timed("lstm_backward", b * l):
             _check(lib.rl8_lstm_backward_f32(_ptr(x), b, l, d_in, _ptr(c0), _ptr(gates), _ptr(cs), _ptr(dhs),
                                              _ptr(whht_packed), _ptr(dgates), _ptr(partials), C.byref(rows), _stream()),
                    "rl8_lstm_backward_f32")
-    m = b * l
-    ws = _wgrad_workspace(dev)
-    dw_hh = torch.empty(4 * H, H, dtype=torch.float32, device=dev)
-    # per gate and timestep dW_hh[q] += dG_q^T h_{t-1} over the B rows of that step: h_{t-1} is
-    # h0 for t = 0 and hs[:, t-1] (row pitch L*256) after, so no shifted copy of hs is made
+    ws, dw_hh = _wgrad_workspace(dev), torch.empty(4 * H, H, dtype=torch.float32, device=dev)
     dgp, hsp, h0p, wsp, dwp, stream = _ptr(dgates), _ptr(hs), _ptr(h0), _ptr(ws), _ptr(dw_hh), _stream()
-    if fused_colsums:
+    if planes:
         xt = [x[:, t].contiguous() for t in range(l)]            # dense [B][d] per step (the kernel's scalar loads)
-        ckey = (dev.index or 0, _stream() or 0, l, d_in)
-        cols = _lstm_colsum_ws.get(ckey)                          # [gate][step][workgroup][...], kept between calls
+        width = H * (d_in + 1)                                    # a column-sum row: dW_ih^T, then the bias
+        # kept between calls: [gate][step][workgroup][...]; four gates per launch: [step][gate][workgroup of gate][...]
+        key = (dev.index or 0, _stream() or 0, l, d_in, *(("gates",) if four_gates else ()))
+        cols = _lstm_colsum_ws.get(key)
         if cols is None:
-            cols = _lstm_colsum_ws[ckey] = torch.empty(4, l, 256, H * (d_in + 1), dtype=torch.float32, device=dev)
+            cols = _lstm_colsum_ws[key] = torch.empty(*((l, 4, 64) if four_gates else (4, l, 256)), width,
+                                                      dtype=torch.float32, device=dev)
         crow = C.c_int(0)
-        # with the backward kernel's bound on |dG| the products run on fp16 planes (three instead of six): dG scaled by
-        # one power of two for the tensor, h_{t-1} by one from max |h0| (t = 0) or 1 (an LSTM's own outputs)
-        f16 = dg_bound is not None and os.environ.get("RL8_AMD_LSTM_WGRAD_PLANES", "f16") != "bf16"
-        if f16:
-            if h0_bound is None:
-                h0_bound = torch.linalg.vector_norm(h0, ord=float("inf")).reshape(1)
-            elif h0_bound.dtype != torch.float32 or h0_bound.numel() != 1 or h0_bound.device != dev:
-                raise ValueError("h0_bound must be one float32 element on x's device")
-            if hs_bound is None:  # (one pass over hs: callers that know their hs say so)
-                one = torch.linalg.vector_norm(hs, ord=float("inf")).reshape(1) if l > 1 else torch.ones(1, dtype=torch.float32, device=dev)
-            else:
-                one = torch.full((1,), float(hs_bound), dtype=torch.float32, device=dev)
-        if f16 and b >= 128 and os.environ.get("RL8_AMD_LSTM_WGRAD_GATES", "fused") != "separate":
-            # the four gates of a timestep in one launch: h_{t-1} comes out of HBM once instead of four times
-            gkey = (dev.index or 0, _stream() or 0, l, d_in, "gates")
-            gcols = _lstm_colsum_ws.get(gkey)                     # [step][gate][workgroup of the gate][...]
-            if gcols is None:
-                gcols = _lstm_colsum_ws[gkey] = torch.empty(l, 4, 64, H * (d_in + 1), dtype=torch.float32, device=dev)
-            with _timed("lstm_wgrad", m):
-                for t in range(l):
-                    h_prev, h_pitch = (h0p, H) if t == 0 else (hsp + (t - 1) * H * 4, l * H)
-                    _check(lib.rl8_lstm_wgrad_f16_f32(
-                        dgp + t * 4 * H * 4, l * 4 * H, _ptr(dg_bound), h_prev, h_pitch, _ptr(h0_bound if t == 0 else one), b,
-                        wsp, dwp, int(t > 0), _ptr(xt[t]), d_in, _ptr(gcols[t]), C.byref(crow), stream), "rl8_lstm_wgrad_f16_f32")
-            # (a step's rows sit gate-major, crow.value per gate -- 64 at the sizes that fill the chip)
-            width = H * (d_in + 1)
-            sums = gcols.view(l, -1)[:, : 4 * crow.value * width].reshape(l, 4, crow.value, width).sum(dim=(0, 2))
-            return {"w_ih": sums[:, : H * d_in].reshape(4 * H, d_in), "w_hh": dw_hh, "b": sums[:, H * d_in :].reshape(4 * H)}
-        with _timed("lstm_wgrad", m):
-            for q in range(4):
-                for t in range(l):
-                    h_prev, h_pitch = (h0p, H) if t == 0 else (hsp + (t - 1) * H * 4, l * H)
-                    if f16:
-                        _check(lib.rl8_mlp_wgrad_f16_strided_f32(
-                            dgp + (t * 4 * H + q * H) * 4, l * 4 * H, _ptr(dg_bound), h_prev, h_pitch,
-                            _ptr(h0_bound if t == 0 else one), b, wsp, dwp + 4 * H * H * q, int(t > 0),
-                            _ptr(xt[t]), d_in, _ptr(cols[q, t]), C.byref(crow), stream), "rl8_mlp_wgrad_f16_strided_f32")
-                        continue
-                    _check(lib.rl8_mlp_wgrad_split_strided_f32(
-                        dgp + (t * 4 * H + q * H) * 4, l * 4 * H, h_prev, h_pitch, b, wsp, dwp + 4 * H * H * q, int(t > 0),
-                        _ptr(xt[t]), d_in, _ptr(cols[q, t]), C.byref(crow), stream), "rl8_mlp_wgrad_split_strided_f32")
-        sums = cols[:, :, : crow.value].sum(dim=(1, 2))          # [4][256*(d+1)], steps then workgroups in order
-        dw_ih = sums[:, : H * d_in].reshape(4 * H, d_in)
-        db = sums[:, H * d_in :].reshape(4 * H)
-        return {"w_ih": dw_ih, "w_hh": dw_hh, "b": db}
-    small = partials[: rows.value].sum(0)
-    fn, name = ((lib.rl8_mlp_wgrad_split_strided_f32, "rl8_mlp_wgrad_split_strided_f32") if split
-                else (lib.rl8_mlp_wgrad_strided_f32, "rl8_mlp_wgrad_strided_f32"))
-    extra = (None, 0, None, None) if split else ()
-    with _timed("lstm_wgrad", m):
-        for q in range(4):
+    else:
+        small = partials[: rows.value].sum(0)
+    if f16:
+        # three products instead of six: dG scaled by one power of two for the tensor, h_{t-1} by one from max |h0|
+        # (t = 0) or 1 (an LSTM's own outputs)
+        if h0_bound is None:
+            h0_bound = torch.linalg.vector_norm(h0, ord=float("inf")).reshape(1)
+        elif h0_bound.dtype != torch.float32 or h0_bound.numel() != 1 or h0_bound.device != dev:
+            raise ValueError("h0_bound must be one float32 element on x's device")
+        if hs_bound is None:  # (one pass over hs: callers that know their hs say so)
+            one = torch.linalg.vector_norm(hs, ord=float("inf")).reshape(1) if l > 1 else torch.ones(1, dtype=torch.float32, device=dev)
+        else:
+            one = torch.full((1,), float(hs_bound), dtype=torch.float32, device=dev)
+    # per gate (or the four at once) and timestep dW_hh[q] += dG_q^T h_{t-1} over the B rows of that step: h_{t-1} is
+    # h0 for t = 0 and hs[:, t-1] (row pitch L*256) after, so no shifted copy of hs is made
+    dg_scale = (_ptr(dg_bound),) if f16 else ()
+    with _timed("lstm_wgrad", b * l):
+        for q in range(1 if four_gates else 4):
             for t in range(l):
                 h_prev, h_pitch = (h0p, H) if t == 0 else (hsp + (t - 1) * H * 4, l * H)
-                _check(fn(dgp + (t * 4 * H + q * H) * 4, l * 4 * H, h_prev, h_pitch, b, wsp, dwp + 4 * H * H * q,
-                          int(t > 0), *extra, stream), name)
-    return {"w_ih": small[: 4 * LSTM_HIDDEN * d_in].view(4 * LSTM_HIDDEN, d_in), "w_hh": dw_hh,
-            "b": small[4 * LSTM_HIDDEN * d_in :]}
+                h_scale = (_ptr(h0_bound if t == 0 else one),) if f16 else ()
+                col_sums = (_ptr(xt[t]), d_in, _ptr(cols[t] if four_gates else cols[q, t]), C.byref(crow)) if planes else ()
+                _check(getattr(lib, name)(dgp + (t * 4 * H + q * H) * 4, l * 4 * H, *dg_scale, h_prev, h_pitch, *h_scale, b,
+                                          wsp, dwp + 4 * H * H * q, int(t > 0), *col_sums, stream), name)
+    if not planes:
+        return {"w_ih": small[: 4 * H * d_in].view(4 * H, d_in), "w_hh": dw_hh, "b": small[4 * H * d_in :]}
+    if four_gates:  # (a step's rows sit gate-major, crow.value per gate -- 64 at the sizes that fill the chip)
+        sums = cols.view(l, -1)[:, : 4 * crow.value * width].reshape(l, 4, crow.value, width).sum(dim=(0, 2))
+    else:
+        sums = cols[:, :, : crow.value].sum(dim=(1, 2))          # [4][256*(d+1)], steps then workgroups in order
+    return {"w_ih": sums[:, : H * d_in].reshape(4 * H, d_in), "w_hh": dw_hh, "b": sums[:, H * d_in :].reshape(4 * H)}
 
 
 HEADS_MAX_OUT = 8  # outputs of one linear-heads launch

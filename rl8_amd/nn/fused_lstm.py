@@ -14,6 +14,8 @@ module itself.
 
 from __future__ import annotations
 
+import dataclasses
+import functools
 import os
 
 import torch
@@ -23,6 +25,7 @@ from .. import hip
 
 #: Set to False to evaluate LSTMs with PyTorch (A/B comparisons).
 ENABLED = True
+# ``_plan`` reads these three and RL8_AMD_LSTM_WGRAD_PLANES / _GATES on every call (tests change them at run time).
 #: "split": the forward step on the bf16 matrix pipe (fp32-accurate bf16-plane products,
 #: lstm_split_kernels.hip) where the input width has a compiled variant; "f32": the
 #: fp32-MFMA kernel with the time loop inside (lstm_kernels.hip).
@@ -32,6 +35,11 @@ BACKWARD_ROWS = os.environ.get("RL8_AMD_LSTM_BACKWARD_ROWS", "1") != "0"
 #: Training passes through LSTM + heads as one autograd node whose backward forms the heads' data gradient inside the
 #: backward-through-time kernel (lstm_heads_forward); 0: two nodes, dL/dh through HBM.
 FUSE_HEADS = os.environ.get("RL8_AMD_LSTM_FUSE_HEADS", "1") != "0"
+
+
+def _rollout_fuse_heads() -> bool:
+    """The lean rollout's two-way categorical + value head inside its last kernel (0: two launches); read per rollout."""
+    return os.environ.get("RL8_AMD_ROLLOUT_FUSE_HEADS", "1") != "0"
 
 
 def _eligible(lstm: nn.LSTM, x: torch.Tensor) -> bool:
@@ -51,28 +59,50 @@ def _eligible(lstm: nn.LSTM, x: torch.Tensor) -> bool:
     )
 
 
-def _packs(lstm: nn.LSTM, transposed: bool) -> torch.Tensor:
-    """Fragment-ordered copies of the weights, cached ON the module and re-made
-    when the optimizer has changed a parameter (version counters) or a parameter
-    tensor has been replaced / moved."""
+def _packs(lstm: nn.LSTM, kind: str):
+    """Fragment-ordered copies of the weights for one kernel ("step" / "split": the fp32 / plane forward step,
+    "transposed" / "rows": the fp32 / rows backward), cached ON the module and re-made when the optimizer has changed
+    a parameter (version counters) or a parameter tensor has been replaced / moved."""
     params = (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0)
     stamp = tuple((p._version, p.data_ptr()) for p in params)
     cache = lstm.__dict__.setdefault("_rl8_lstm_packs", {})
-    hit = cache.get(transposed)
+    hit = cache.get(kind)
     if hit is not None and hit[0] == stamp:
         return hit[1]
-    if transposed == "split":
-        packed = hip.lstm_pack_split(*params)
-    elif transposed == "rows":
-        packed = hip.lstm_rows_backward_pack(params[1])
-    else:
-        packed = hip.lstm_pack_transposed(params[1]) if transposed else hip.lstm_pack(*params)
-    cache[transposed] = (stamp, packed)
+    pack = {"step": hip.lstm_pack, "split": hip.lstm_pack_split, "transposed": hip.lstm_pack_transposed,
+            "rows": hip.lstm_rows_backward_pack}[kind]
+    packed = pack(*params) if kind in ("step", "split") else pack(params[1])
+    cache[kind] = (stamp, packed)
     return packed
 
 
-def use_split(lstm: nn.LSTM) -> bool:
-    return FORWARD_GEMM == "split" and hip.lstm_split_supports(lstm.input_size)
+@functools.lru_cache(maxsize=None)
+def _planes_supported(d_in: int) -> bool:
+    """The plane kernels are compiled for this input width: fixed by the build, asked once per width."""
+    return hip.lstm_split_supports(d_in)
+
+
+@dataclasses.dataclass(frozen=True)
+class _LstmPlan:
+    """The kernels one LSTM call runs, forward and backward: made once by ``_plan`` and saved on ``ctx`` so that the
+    backward runs what its forward prepared for (its packs: "split" or "step", "rows" or "transposed")."""
+
+    forward_planes: bool  # the step kernel on fp16 planes (training: max |h0| from its state split); else fp32 MFMA
+    backward_rows: bool  # the backward through time on planes (rows kernel), which leaves a bound on |dG|; else fp32 MFMA
+    wgrad: str  # the weight gradient's route (hip.lstm_backward): "f16-gates", "f16", "bf16" or "f32"
+    fuse_heads: bool  # a training pass through LSTM + heads as one node (lstm_heads_forward)
+
+
+def _plan(d_in: int, b: int) -> _LstmPlan:
+    """The one place the LSTM routes are decided, for ``b`` sequences of ``d_in`` floats; reads the switches as they
+    are now."""
+    forward_planes = FORWARD_GEMM == "split" and _planes_supported(d_in)
+    backward_rows = forward_planes and BACKWARD_ROWS
+    four_gates = b >= hip.LSTM_WGRAD_GATES_MIN_ROWS and os.environ.get("RL8_AMD_LSTM_WGRAD_GATES", "fused") != "separate"
+    wgrad = ("f32" if not forward_planes else
+             "bf16" if not backward_rows or os.environ.get("RL8_AMD_LSTM_WGRAD_PLANES", "f16") == "bf16" else
+             "f16-gates" if four_gates else "f16")
+    return _LstmPlan(forward_planes, backward_rows, wgrad, FUSE_HEADS and backward_rows)
 
 
 #: The fp16 planes of the last training pass's initial hidden states and max |h0|: the SGD iterations of one step() read
@@ -107,20 +137,19 @@ def clear_state_cache() -> None:
 
 class _FusedLSTM(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, lstm, grad_mode):  # type: ignore[override]
+    def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, lstm, grad_mode, plan):  # type: ignore[override]
         need_grad = grad_mode and any(ctx.needs_input_grad[3:7])
-        if use_split(lstm):
+        if plan.forward_planes:
             packed, wb = _packs(lstm, "split")
             # max |h0| for the backward's fp16-plane weight gradient comes out of the state split
             planes0, bound = _h0_planes(h0) if need_grad else (None, None)
             hs, _, cn, gates, cs = hip.lstm_forward_split(x, h0, c0, packed, wb, save=need_grad, h0_planes=planes0)
         else:
             bound = None
-            hs, _, cn, gates, cs = hip.lstm_forward(x, h0, c0, _packs(lstm, False), save=need_grad)
+            hs, _, cn, gates, cs = hip.lstm_forward(x, h0, c0, _packs(lstm, "step"), save=need_grad)
         ctx.set_materialize_grads(False)
         if need_grad:
-            ctx.lstm = lstm
-            ctx.h0_bound = bound
+            ctx.lstm, ctx.plan, ctx.h0_bound = lstm, plan, bound
             ctx.save_for_backward(x, h0, c0, hs, gates, cs)
         ctx.mark_non_differentiable(cn)
         # (c_n may be the last column of the saved cell states, strided: a training pass, which drops the final
@@ -130,15 +159,12 @@ class _FusedLSTM(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dhs, dcn):  # type: ignore[override]
         x, h0, c0, hs, gates, cs = ctx.saved_tensors
-        if dhs is None:
-            dhs = torch.zeros_like(hs)
-        dhs = dhs.contiguous().float()
-        if use_split(ctx.lstm) and BACKWARD_ROWS:
-            g = hip.lstm_backward(x, h0, c0, hs, gates, cs, dhs, None, split=True, rows_packed=_packs(ctx.lstm, "rows"),
-                                  h0_bound=ctx.h0_bound, hs_bound=1.0)  # (hs: this LSTM's own outputs, |o tanh c| < 1)
-        else:
-            g = hip.lstm_backward(x, h0, c0, hs, gates, cs, dhs, _packs(ctx.lstm, True), split=use_split(ctx.lstm))
-        return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None, None
+        dhs = torch.zeros_like(hs) if dhs is None else dhs.contiguous().float()
+        packed = _packs(ctx.lstm, "rows" if ctx.plan.backward_rows else "transposed")
+        whht, rows = (None, packed) if ctx.plan.backward_rows else (packed, None)
+        g = hip.lstm_backward(x, h0, c0, hs, gates, cs, dhs, whht, wgrad=ctx.plan.wgrad, rows_packed=rows,
+                              h0_bound=ctx.h0_bound, hs_bound=1.0)  # (hs: this LSTM's own outputs, |o tanh c| < 1)
+        return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None, None, None
 
 
 def lstm_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
@@ -150,7 +176,7 @@ def lstm_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Ten
         return None
     hs, cn = _FusedLSTM.apply(
         x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
-        lstm.bias_ih_l0, lstm.bias_hh_l0, lstm, torch.is_grad_enabled(),
+        lstm.bias_ih_l0, lstm.bias_hh_l0, lstm, torch.is_grad_enabled(), _plan(lstm.input_size, x.shape[0]),
     )
     return hs, hs[:, -1], cn  # h_n is h_{L-1}: a view, so a gradient into it reaches dhs by itself
 
@@ -176,13 +202,13 @@ class _FusedLSTMHeads(torch.autograd.Function):
     row-step of the recurrent bench less)."""
 
     @staticmethod
-    def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, w_heads, b_heads, lstm):  # type: ignore[override]
+    def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, w_heads, b_heads, lstm, plan):  # type: ignore[override]
         packed, wb = _packs(lstm, "split")
         planes0, bound = _h0_planes(h0)
         hs, _, cn, gates, cs = hip.lstm_forward_split(x, h0, c0, packed, wb, save=True, h0_planes=planes0)
         out = hip.linear_heads_forward(hs.view(-1, hip.LSTM_HIDDEN), w_heads, b_heads)
         ctx.set_materialize_grads(False)
-        ctx.lstm, ctx.h0_bound = lstm, bound
+        ctx.lstm, ctx.plan, ctx.h0_bound = lstm, plan, bound
         ctx.save_for_backward(x, h0, c0, hs, gates, cs, w_heads)
         ctx.mark_non_differentiable(cn)
         return out, hs, cn
@@ -191,17 +217,16 @@ class _FusedLSTMHeads(torch.autograd.Function):
     def backward(ctx, dout, dhs, dcn):  # type: ignore[override]
         x, h0, c0, hs, gates, cs, w_heads = ctx.saved_tensors
         flat = hs.view(-1, hip.LSTM_HIDDEN)
-        if dout is None:
-            dout = torch.zeros(flat.shape[0], w_heads.shape[0], dtype=torch.float32, device=flat.device)
-        dout = dout.contiguous().float()
-        common = dict(split=True, rows_packed=_packs(ctx.lstm, "rows"), h0_bound=ctx.h0_bound, hs_bound=1.0)
+        dout = (torch.zeros(flat.shape[0], w_heads.shape[0], dtype=torch.float32, device=flat.device) if dout is None
+                else dout.contiguous().float())
+        common = dict(wgrad=ctx.plan.wgrad, rows_packed=_packs(ctx.lstm, "rows"), h0_bound=ctx.h0_bound, hs_bound=1.0)
         if dhs is None:  # nothing but the heads reads the latents: the usual case
             _, dw, db = hip.linear_heads_backward(flat, dout, w_heads, need_dh=False)
             g = hip.lstm_backward(x, h0, c0, hs, gates, cs, None, None, heads=(dout, w_heads), **common)
         else:
             dh, dw, db = hip.linear_heads_backward(flat, dout, w_heads)
             g = hip.lstm_backward(x, h0, c0, hs, gates, cs, dh.view_as(hs) + dhs.float(), None, **common)
-        return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], dw, db, None
+        return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], dw, db, None, None
 
 
 def _heads_eligible(heads: list[nn.Linear], max_out: int) -> bool:
@@ -213,20 +238,20 @@ def _heads_eligible(heads: list[nn.Linear], max_out: int) -> bool:
 def lstm_heads_forward(lstm: nn.LSTM, heads: list[nn.Linear], x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
     """A training pass through ``lstm`` and ``Linear(256, n_i)`` heads on its outputs as one autograd node
     (:class:`_FusedLSTMHeads`): ``([head_i(hs) as [B * L, n_i]], hs [B, L, 256], h_n, c_n)``, or ``None`` when this
-    combination is not eligible (no gradient wanted, more than four head outputs, an LSTM the fp16-plane forward or
-    the plane-product backward does not take): the caller then runs :func:`lstm_forward` and :func:`heads_forward`."""
-    if not (FUSE_HEADS and torch.is_grad_enabled() and _eligible(lstm, x) and use_split(lstm) and BACKWARD_ROWS):
+    combination is not eligible (no gradient wanted, more than four head outputs, a plan that does not fuse the
+    heads): the caller then runs :func:`lstm_forward` and :func:`heads_forward`."""
+    if not (torch.is_grad_enabled() and _eligible(lstm, x)):
         return None
-    if not _heads_eligible(heads, hip.ROWS_BACKWARD_HEADS):
-        return None
-    if not any(p.requires_grad for p in lstm.parameters()):
+    plan = _plan(lstm.input_size, x.shape[0])
+    if not (plan.fuse_heads and _heads_eligible(heads, hip.ROWS_BACKWARD_HEADS)
+            and any(p.requires_grad for p in lstm.parameters())):
         return None
     widths = [h.out_features for h in heads]
     w = torch.cat([h.weight for h in heads], 0) if len(heads) > 1 else heads[0].weight
     b = torch.cat([h.bias for h in heads], 0) if len(heads) > 1 else heads[0].bias
     out, hs, cn = _FusedLSTMHeads.apply(
         x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
-        lstm.bias_ih_l0, lstm.bias_hh_l0, w, b, lstm,
+        lstm.bias_ih_l0, lstm.bias_hh_l0, w, b, lstm, plan,
     )
     return list(out.split(widths, dim=1)), hs, hs[:, -1], cn
 

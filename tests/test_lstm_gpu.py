@@ -422,7 +422,7 @@ def test_lstm_backward_on_planes_matches_autograd(b, l, d_in):
 
 
 @pytest.mark.parametrize("case", ["plain", "one_outlier_sequence", "six_decades"])
-def test_lstm_weight_gradient_planes_hold_over_the_dynamic_range(case, monkeypatch):
+def test_lstm_weight_gradient_planes_hold_over_the_dynamic_range(case):
     """The LSTM's weight gradient runs on two fp16 planes per operand WITHOUT a guard on the data:
     dG is scaled by its true maximum and its low plane is wide.  Entry by entry against fp64 on the kernel's own dG,
     relative to the entry's sum of |terms|: with one sequence 10^6 above all others, or sequences spread over six
@@ -440,10 +440,9 @@ def test_lstm_weight_gradient_planes_hold_over_the_dynamic_range(case, monkeypat
         dhs *= 10.0 ** torch.randint(-4, 3, (b, 1, 1), device=DEV, generator=g).float()
     hs, hn, cn, gates, cs = hip.lstm_forward(x, h0, c0, pack(lstm), save=True)
     packed = hip.lstm_rows_backward_pack(lstm.weight_hh_l0)
-    run = lambda: hip.lstm_backward(x, h0, c0, hs, gates, cs, dhs, None, split=True, rows_packed=packed)  # noqa: E731
-    f16 = run()
-    monkeypatch.setenv("RL8_AMD_LSTM_WGRAD_PLANES", "bf16")
-    exact = run()
+    run = lambda wgrad: hip.lstm_backward(x, h0, c0, hs, gates, cs, dhs, None, wgrad=wgrad, rows_packed=packed)  # noqa: E731
+    f16 = run("f16-gates")
+    exact = run("bf16")
     dg = hip.lstm_rows_backward(c0, gates, cs, dhs, packed).double().reshape(b, l, 1024)
     h_prev = torch.cat([h0[:, None], hs[:, :-1]], 1).double()
     want = torch.einsum("blj,bli->ji", dg, h_prev)
