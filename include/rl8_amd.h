@@ -704,6 +704,31 @@ int rl8_mlp_narrow_backward_f32(const float *x, const float *dout, int64_t m, in
 int rl8_mlp_narrow_reduce_f32(const float *workspace, int64_t m, int hidden, int d_in, int n_out, float *grads_out,
                               void *stream);
 
+/* ---- Narrow LSTMs: one layer, biased, batch_first, hidden width H = 64 or 128, d_in <= 16 (lstm_narrow_kernels.hip).
+ * Weights in torch layout, unpacked: w_ih [4H][d_in], w_hh [4H][H], b_ih / b_hh [4H], gate order i, f, g, o.  The
+ * products run on fp32 MFMA with the time loop inside the kernel.
+ * rl8_lstm_narrow_supports: 1 when (hidden, d_in) is compiled in, else 0.
+ * rl8_lstm_narrow_forward_f32: x [b][l][d_in], h0 / c0 [b][H] -> hs [b][l][H], hn / cn [b][H].  save_gates
+ *   ([b][l][4][H], post-activation) and save_c ([b][l][H], cell states) both NULL: inference; both set: training, for
+ *   the backward.  hs, hn and cn are bitwise the same in both modes.
+ * rl8_lstm_narrow_backward_f32: backward through time from dL/dhs (dhs [b][l][H]) and what the training forward
+ *   saved; writes the gate gradients and one partial slab of weight gradients per sequence chunk into `workspace`
+ *   (rl8_lstm_narrow_workspace_bytes(b, l, ...) bytes, no initialisation); rl8_lstm_narrow_reduce_f32 then sums the
+ *   slabs in a fixed order (fp64) into grads_out = [dW_ih (4H d_in) | dW_hh (4H H) | db (4H)] floats, db being the
+ *   gradient of b_ih and of b_hh alike: bitwise reproducible.  No gradient for x, h0 or c0; c_n is not differentiable.
+ * Pointers 4-byte aligned, workspace 16-byte aligned; b >= 1, 1 <= l < 2^31 / (256 H); RL8_ESIZE for widths outside
+ * the compiled set. */
+int rl8_lstm_narrow_supports(int hidden, int d_in);
+int64_t rl8_lstm_narrow_workspace_bytes(int64_t b, int l, int hidden, int d_in);
+int rl8_lstm_narrow_forward_f32(const float *x, int64_t b, int l, int d_in, const float *h0, const float *c0,
+                                const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, int hidden,
+                                float *hs, float *hn, float *cn, float *save_gates, float *save_c, void *stream);
+int rl8_lstm_narrow_backward_f32(const float *x, int64_t b, int l, int d_in, const float *h0, const float *c0,
+                                 const float *w_hh, int hidden, const float *hs, const float *gates, const float *cs,
+                                 const float *dhs, float *workspace, void *stream);
+int rl8_lstm_narrow_reduce_f32(const float *workspace, int64_t b, int l, int hidden, int d_in, float *grads_out,
+                               void *stream);
+
 /* ---- OPT-IN: towers of a SCALAR observation as exact piecewise-linear tables (round 4 prototype; VERDICT r3 item 10,
  * DESIGN.md section 9).  Special to d_in = 1 -- the dummy envs of BASELINE configs 2 and 4 -- and never a replacement
  * for the general tower kernels above, which every other shape runs and against which this path is tested.  The

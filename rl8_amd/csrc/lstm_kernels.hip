@@ -15,6 +15,7 @@
 // unit 64w + 32nt + (l&31).  Gate order in the weights is torch's: i, f, g, o.
 // Gates are evaluated i, g, f, o so that at most one gate's activations, the
 // product i*g and the cell state are live next to the accumulators.
+#include "lstm_gates.hip.h"
 #include "mfma_tile.hip.h"
 
 namespace rl8 {
@@ -25,15 +26,7 @@ constexpr int kLstmStride = kHidden + 9;              // LDS row pitch of the [h
 constexpr int kLstmMaxIn = 7;                         // inputs + the bias column fit the extra k-group
 constexpr int kLstmPackFloats = 4 * 8 * kLstmGroups * 4 * kWave;  // per direction
 constexpr int kGateOrder[4] = {0, 2, 1, 3};
-
-// Gate non-linearities on the hardware exp2 / rcp (1 ulp each; the reference's
-// tolerance is 1e-5): sigmoid(x) = 1 / (1 + e^-x), tanh(x) = 1 - 2 / (e^2x + 1).
-__device__ __forceinline__ float sigmoid_f(float x) {
-  return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
-__device__ __forceinline__ float tanh_f(float x) {
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f);
-}
+// (gate non-linearities sigmoid_f / tanh_f: lstm_gates.hip.h)
 
 // Forward weights in fragment order, the input projection and the biases folded
 // into the recurrent product as eight extra k: with the operand row

@@ -178,6 +178,12 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_mlp_narrow_forward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "rl8_mlp_narrow_backward_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "rl8_mlp_narrow_reduce_f32": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "rl8_lstm_narrow_supports": [_i32, _i32],
+    "rl8_lstm_narrow_workspace_bytes": [_i64, _i32, _i32, _i32],
+    "rl8_lstm_narrow_forward_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                    _vp],
+    "rl8_lstm_narrow_backward_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rl8_lstm_narrow_reduce_f32": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
 }
 
 
@@ -210,7 +216,7 @@ def load() -> C.CDLL:
                             "rl8_lstm_pack_floats", "rl8_lstm_backward_partial_floats",
                             "rl8_lstm_split_packed_bytes", "rl8_lstm_split_wb_floats", "rl8_lstm_split_state_bytes",
                             "rl8_mlp_f16_packed_bytes", "rl8_lstm_rows_backward_pack_bytes", "rl8_pw_workspace_bytes",
-                            "rl8_mlp_narrow_workspace_bytes")
+                            "rl8_mlp_narrow_workspace_bytes", "rl8_lstm_narrow_workspace_bytes")
                 else C.c_int
             )
         built = int(lib.rl8_abi_version(None, 0))
@@ -1362,6 +1368,84 @@ def lstm_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_packed: 
         _check(load().rl8_lstm_forward_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_packed), _ptr(hs), _ptr(hn),
                                            _ptr(cn), _ptr(gates), _ptr(cs), _stream()), "rl8_lstm_forward_f32")
     return hs, hn, cn, gates, cs
+
+
+# --------------------------------------------------------------------------- #
+# Narrow LSTMs: one layer, hidden width 64 or 128, d_in <= 16 (lstm_narrow_kernels.hip).
+# --------------------------------------------------------------------------- #
+LSTM_NARROW_HIDDEN = (64, 128)
+
+
+def lstm_narrow_supports(hidden: int, d_in: int) -> bool:
+    return bool(load().rl8_lstm_narrow_supports(int(hidden), int(d_in)))
+
+
+def _lstm_narrow_params(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: None | torch.Tensor, w_hh: torch.Tensor,
+                        b_ih: None | torch.Tensor, b_hh: None | torch.Tensor) -> tuple[int, int, int, int]:
+    """(b, l, d_in, hidden) after the dtype / contiguity / shape checks of the narrow LSTM entries."""
+    _dense(x, torch.float32, "x")
+    if x.ndim != 3:
+        raise ValueError("x must be [B, L, d_in]")
+    b, l, d_in = x.shape
+    hidden = w_hh.shape[1] if w_hh.ndim == 2 else -1
+    shapes = (("h0", h0, (b, hidden)), ("c0", c0, (b, hidden)), ("w_ih", w_ih, (4 * hidden, d_in)),
+              ("w_hh", w_hh, (4 * hidden, hidden)), ("b_ih", b_ih, (4 * hidden,)), ("b_hh", b_hh, (4 * hidden,)))
+    for name, t, shape in shapes:
+        if t is None:
+            continue
+        _dense(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    if b < 1 or l < 1 or not lstm_narrow_supports(hidden, d_in):
+        raise ValueError(f"no narrow LSTM kernel for b={b}, l={l}, hidden={hidden}, d_in={d_in}")
+    return b, l, d_in, hidden
+
+
+def lstm_narrow_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
+                        b_ih: torch.Tensor, b_hh: torch.Tensor, *, save: bool = False):
+    """x [B, L, d], h0 / c0 [B, H] (H = 64 or 128) -> (hs [B, L, H], hn, cn [B, H], gates, cs); ``gates``
+    [B, L, 4, H] (post-activation, order i, f, g, o) and ``cs`` [B, L, H] only with ``save``."""
+    x, h0, c0, w_ih, w_hh, b_ih, b_hh = (t.detach() for t in (x, h0, c0, w_ih, w_hh, b_ih, b_hh))
+    b, l, d_in, hidden = _lstm_narrow_params(x, h0, c0, w_ih, w_hh, b_ih, b_hh)
+    dev = x.device
+    hs = torch.empty(b, l, hidden, dtype=torch.float32, device=dev)
+    hn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
+    cn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
+    gates = torch.empty(b, l, 4, hidden, dtype=torch.float32, device=dev) if save else None
+    cs = torch.empty(b, l, hidden, dtype=torch.float32, device=dev) if save else None
+    with _timed("lstm_narrow_forward", b * l):
+        _check(load().rl8_lstm_narrow_forward_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_ih), _ptr(w_hh),
+                                                  _ptr(b_ih), _ptr(b_hh), hidden, _ptr(hs), _ptr(hn), _ptr(cn),
+                                                  _ptr(gates), _ptr(cs), _stream()), "rl8_lstm_narrow_forward_f32")
+    return hs, hn, cn, gates, cs
+
+
+def lstm_narrow_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_hh: torch.Tensor, hs: torch.Tensor,
+                         gates: torch.Tensor, cs: torch.Tensor, dhs: torch.Tensor) -> dict[str, torch.Tensor]:
+    """Gradients ("w_ih", "w_hh", "b": of b_ih and b_hh alike) for dL/dhs ``dhs`` [B, L, H], from what
+    :func:`lstm_narrow_forward` saved: backward through time, partial slabs per sequence chunk summed in a fixed
+    order (deterministic). No gradient for x, h0, c0."""
+    x, h0, c0, w_hh, hs, gates, cs, dhs = (t.detach() for t in (x, h0, c0, w_hh, hs, gates, cs, dhs))
+    b, l, d_in, hidden = _lstm_narrow_params(x, h0, c0, None, w_hh, None, None)
+    for name, t, shape in (("hs", hs, (b, l, hidden)), ("gates", gates, (b, l, 4, hidden)), ("cs", cs, (b, l, hidden)),
+                           ("dhs", dhs, (b, l, hidden))):
+        _dense(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    lib = load()
+    ws = torch.empty(int(lib.rl8_lstm_narrow_workspace_bytes(b, l, hidden, d_in)) // 4, dtype=torch.float32,
+                     device=x.device)
+    sizes = (4 * hidden * d_in, 4 * hidden * hidden, 4 * hidden)
+    grads = torch.empty(sum(sizes), dtype=torch.float32, device=x.device)
+    with _timed("lstm_narrow_backward", b * l):
+        _check(lib.rl8_lstm_narrow_backward_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_hh), hidden, _ptr(hs),
+                                                _ptr(gates), _ptr(cs), _ptr(dhs), _ptr(ws), _stream()),
+               "rl8_lstm_narrow_backward_f32")
+    with _timed("lstm_narrow_reduce", b * l):
+        _check(lib.rl8_lstm_narrow_reduce_f32(_ptr(ws), b, l, hidden, d_in, _ptr(grads), _stream()),
+               "rl8_lstm_narrow_reduce_f32")
+    w_ih, w_hh_grad, db = torch.split(grads, sizes)
+    return {"w_ih": w_ih.view(4 * hidden, d_in), "w_hh": w_hh_grad.view(4 * hidden, hidden), "b": db}
 
 
 def lstm_split_supports(d_in: int) -> bool:

@@ -1,10 +1,12 @@
-"""Recurrent policy / value networks (LSTM on PyTorch-ROCm / MIOpen).
+"""Recurrent policy / value networks (LSTM: fused HIP kernels, else PyTorch-ROCm).
 
 Interfaces follow the reference's ``src/rl8/models/_recurrent.py``:
 ``RecurrentModel`` :19-138 (``forward(batch, states) -> (features, states)``,
 ``state_spec``, ``init_states``), ``DefaultContinuousRecurrentModel`` :169-256,
 ``DefaultDiscreteRecurrentModel`` :259-341. Module names match, so reference
-``state_dict``s load unchanged.
+``state_dict``s load unchanged. A one-layer LSTM of hidden width 256 (d_in <= 7) or
+64 / 128 (d_in <= 16) runs the fused HIP kernels (``nn/fused_lstm.py``); any other
+runs the module.
 
 """
 

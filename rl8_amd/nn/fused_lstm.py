@@ -5,10 +5,13 @@
 around (``src/rl8/models/_recurrent.py:201-321`` of the reference) -- runs as one
 forward kernel (time loop inside, gates never leave the chip) and, for training,
 one backward-through-time kernel plus the weight-gradient kernels, instead of two
-GEMMs and a pointwise kernel per timestep. Parameters stay the module's own;
-``lstm_forward`` returns ``None`` for any other LSTM (more layers, other widths,
-projections, bidirectional, non-HIP / non-fp32 inputs) and the caller runs the
-module itself.
+GEMMs and a pointwise kernel per timestep. ``nn.LSTM(d_in, 64 | 128)`` with
+d_in <= 16 -- the reference's example model is ``nn.LSTM(4, 64)`` -- runs the
+narrow kernels (lstm_narrow_kernels.hip: fp32 MFMA forward with the time loop
+inside, backward through time, deterministic weight gradient) under the same
+rules. Parameters stay the module's own; ``lstm_forward`` returns ``None`` for
+any other LSTM (more layers, other widths, projections, bidirectional, non-HIP /
+non-fp32 inputs) and the caller runs the module itself.
 
 """
 
@@ -56,6 +59,30 @@ def _eligible(lstm: nn.LSTM, x: torch.Tensor) -> bool:
         and lstm.proj_size == 0
         and x.shape[2] == lstm.input_size
         and hip.lstm_supports(lstm.input_size)
+    )
+
+
+@functools.lru_cache(maxsize=None)
+def _narrow_supported(hidden: int, d_in: int) -> bool:
+    """The narrow kernels are compiled for this (hidden, d_in): fixed by the build, asked once per pair."""
+    return hip.lstm_narrow_supports(hidden, d_in)
+
+
+def _narrow_eligible(lstm: nn.LSTM, x: torch.Tensor) -> bool:
+    """``_eligible`` at hidden width 64 or 128 and d_in <= 16 (lstm_narrow_kernels.hip)."""
+    return (
+        ENABLED
+        and x.is_cuda
+        and x.dtype == torch.float32
+        and x.ndim == 3
+        and lstm.num_layers == 1
+        and lstm.hidden_size in hip.LSTM_NARROW_HIDDEN
+        and lstm.batch_first
+        and lstm.bias
+        and not lstm.bidirectional
+        and lstm.proj_size == 0
+        and x.shape[2] == lstm.input_size
+        and _narrow_supported(lstm.hidden_size, lstm.input_size)
     )
 
 
@@ -167,11 +194,40 @@ class _FusedLSTM(torch.autograd.Function):
         return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None, None, None
 
 
+class _NarrowLSTM(torch.autograd.Function):
+    """A hidden-64 / 128 LSTM: the weights are read in torch layout (nothing packed, nothing cached); a training
+    pass saves the gates and cell states for the backward through time."""
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, grad_mode):  # type: ignore[override]
+        need_grad = grad_mode and any(ctx.needs_input_grad[3:7])
+        hs, _, cn, gates, cs = hip.lstm_narrow_forward(x, h0, c0, w_ih, w_hh, b_ih, b_hh, save=need_grad)
+        ctx.set_materialize_grads(False)
+        if need_grad:
+            ctx.save_for_backward(x, h0, c0, w_hh, hs, gates, cs)
+        ctx.mark_non_differentiable(cn)
+        return hs, cn
+
+    @staticmethod
+    def backward(ctx, dhs, dcn):  # type: ignore[override]
+        x, h0, c0, w_hh, hs, gates, cs = ctx.saved_tensors
+        dhs = torch.zeros_like(hs) if dhs is None else dhs.contiguous().float()
+        g = hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, dhs)
+        return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None
+
+
 def lstm_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
-    """``lstm(x, (h0[None], c0[None]))`` for ``x`` [B, L, d], ``h0`` / ``c0`` [B, 256]
-    through the fused kernels: ``(hs [B, L, 256], h_n [B, 256], c_n [B, 256])``, or
-    ``None`` when this LSTM / input is not eligible. No gradient flows to ``x``,
-    ``h0``, ``c0`` (rollout-buffer data) nor out of ``c_n``."""
+    """``lstm(x, (h0[None], c0[None]))`` for ``x`` [B, L, d], ``h0`` / ``c0`` [B, H]
+    through the fused kernels: ``(hs [B, L, H], h_n [B, H], c_n [B, H])``, or
+    ``None`` when this LSTM / input is not eligible (H = 256 with d <= 7, or H = 64 /
+    128 with d <= 16). No gradient flows to ``x``, ``h0``, ``c0`` (rollout-buffer
+    data) nor out of ``c_n``."""
+    if _narrow_eligible(lstm, x):
+        hs, cn = _NarrowLSTM.apply(
+            x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
+            lstm.bias_ih_l0, lstm.bias_hh_l0, torch.is_grad_enabled(),
+        )
+        return hs, hs[:, -1], cn
     if not _eligible(lstm, x):
         return None
     hs, cn = _FusedLSTM.apply(
