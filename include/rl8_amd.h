@@ -729,6 +729,30 @@ int rl8_lstm_narrow_backward_f32(const float *x, int64_t b, int l, int d_in, con
 int rl8_lstm_narrow_reduce_f32(const float *workspace, int64_t b, int l, int hidden, int d_in, float *grads_out,
                                void *stream);
 
+/* ---- Stacked LSTMs: layers 1.. of nn.LSTM(d_in, H, num_layers >= 2), H = 64 or 128, biased, batch_first, fp32, no
+ * dropout (lstm_narrow_kernels.hip, lstm_narrow_stack_*).  One upper layer per call: its input x [b][l][H] is the
+ * lower layer's hs; layer 0 runs rl8_lstm_narrow_*.  Weights in torch layout: w_ih [4H][H], w_hh [4H][H], b_ih / b_hh
+ * [4H].  rl8_lstm_stack_supports: 1 when `hidden` is compiled in, else 0.
+ * rl8_lstm_stack_forward_f32: the input projection of all b l row-steps into zin ([b][l][4][H] floats of scratch,
+ *   16-byte aligned, not needed after the call), then the recurrent forward: h0 / c0 [b][H] -> hs [b][l][H], hn / cn
+ *   [b][H].  save_gates / save_c as for rl8_lstm_narrow_forward_f32; hs, hn and cn are bitwise the same in both modes.
+ * rl8_lstm_stack_backward_f32: backward through time from dhs [b][l][H] and what the training forward saved, then
+ *   dx [b][l][H] = dL/dx (the lower layer's dhs) and one partial slab of weight gradients per sequence chunk in
+ *   `workspace` (rl8_lstm_stack_workspace_bytes(b, l, hidden) bytes = 4 (b l 4H + chunks 4H (2H + 1)), no
+ *   initialisation, reusable from layer to layer); rl8_lstm_stack_reduce_f32 then sums the slabs in a fixed order
+ *   (fp64) into grads_out = [dW_ih (4H H) | dW_hh (4H H) | db (4H)]: bitwise reproducible.  No gradient for h0 or c0.
+ * Pointers 4-byte aligned, zin and workspace 16-byte aligned; sizes as for the narrow entries; RL8_ESIZE for other
+ * widths. */
+int rl8_lstm_stack_supports(int hidden);
+int64_t rl8_lstm_stack_workspace_bytes(int64_t b, int l, int hidden);
+int rl8_lstm_stack_forward_f32(const float *x, int64_t b, int l, const float *h0, const float *c0, const float *w_ih,
+                               const float *w_hh, const float *b_ih, const float *b_hh, int hidden, float *zin,
+                               float *hs, float *hn, float *cn, float *save_gates, float *save_c, void *stream);
+int rl8_lstm_stack_backward_f32(const float *x, int64_t b, int l, const float *h0, const float *c0, const float *w_ih,
+                                const float *w_hh, int hidden, const float *hs, const float *gates, const float *cs,
+                                const float *dhs, float *workspace, float *dx, void *stream);
+int rl8_lstm_stack_reduce_f32(const float *workspace, int64_t b, int l, int hidden, float *grads_out, void *stream);
+
 /* ---- OPT-IN: towers of a SCALAR observation as exact piecewise-linear tables (round 4 prototype; VERDICT r3 item 10,
  * DESIGN.md section 9).  Special to d_in = 1 -- the dummy envs of BASELINE configs 2 and 4 -- and never a replacement
  * for the general tower kernels above, which every other shape runs and against which this path is tested.  The

@@ -184,6 +184,11 @@ SIGNATURES: dict[str, list[Any]] = {
                                     _vp],
     "rl8_lstm_narrow_backward_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_lstm_narrow_reduce_f32": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "rl8_lstm_stack_supports": [_i32],
+    "rl8_lstm_stack_workspace_bytes": [_i64, _i32, _i32],
+    "rl8_lstm_stack_forward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rl8_lstm_stack_backward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rl8_lstm_stack_reduce_f32": [_vp, _i64, _i32, _i32, _vp, _vp],
 }
 
 
@@ -216,7 +221,8 @@ def load() -> C.CDLL:
                             "rl8_lstm_pack_floats", "rl8_lstm_backward_partial_floats",
                             "rl8_lstm_split_packed_bytes", "rl8_lstm_split_wb_floats", "rl8_lstm_split_state_bytes",
                             "rl8_mlp_f16_packed_bytes", "rl8_lstm_rows_backward_pack_bytes", "rl8_pw_workspace_bytes",
-                            "rl8_mlp_narrow_workspace_bytes", "rl8_lstm_narrow_workspace_bytes")
+                            "rl8_mlp_narrow_workspace_bytes", "rl8_lstm_narrow_workspace_bytes",
+                            "rl8_lstm_stack_workspace_bytes")
                 else C.c_int
             )
         built = int(lib.rl8_abi_version(None, 0))
@@ -1371,7 +1377,7 @@ def lstm_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_packed: 
 
 
 # --------------------------------------------------------------------------- #
-# Narrow LSTMs: one layer, hidden width 64 or 128, d_in <= 16 (lstm_narrow_kernels.hip).
+# Narrow LSTMs: one layer (or layer 0 of a stack), hidden width 64 or 128, d_in <= 16 (lstm_narrow_kernels.hip).
 # --------------------------------------------------------------------------- #
 LSTM_NARROW_HIDDEN = (64, 128)
 
@@ -1401,16 +1407,30 @@ def _lstm_narrow_params(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_i
     return b, l, d_in, hidden
 
 
+def _lstm_state_out(state_out: tuple[torch.Tensor, torch.Tensor], b: int, hidden: int):
+    """The caller's (hn, cn) [B, H] for a forward to write, checked."""
+    for name, t in zip(("hn", "cn"), state_out):
+        _dense(t, torch.float32, name)
+        if tuple(t.shape) != (b, hidden):
+            raise ValueError(f"{name} must have shape {(b, hidden)}, got {tuple(t.shape)}")
+    return state_out
+
+
 def lstm_narrow_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
-                        b_ih: torch.Tensor, b_hh: torch.Tensor, *, save: bool = False):
+                        b_ih: torch.Tensor, b_hh: torch.Tensor, *, save: bool = False,
+                        state_out: None | tuple[torch.Tensor, torch.Tensor] = None):
     """x [B, L, d], h0 / c0 [B, H] (H = 64 or 128) -> (hs [B, L, H], hn, cn [B, H], gates, cs); ``gates``
-    [B, L, 4, H] (post-activation, order i, f, g, o) and ``cs`` [B, L, H] only with ``save``."""
+    [B, L, 4, H] (post-activation, order i, f, g, o) and ``cs`` [B, L, H] only with ``save``. ``state_out``: the
+    (hn, cn) tensors to write (layer 0 of a stack writes its rows of the stack's states)."""
     x, h0, c0, w_ih, w_hh, b_ih, b_hh = (t.detach() for t in (x, h0, c0, w_ih, w_hh, b_ih, b_hh))
     b, l, d_in, hidden = _lstm_narrow_params(x, h0, c0, w_ih, w_hh, b_ih, b_hh)
     dev = x.device
     hs = torch.empty(b, l, hidden, dtype=torch.float32, device=dev)
-    hn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
-    cn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
+    if state_out is None:
+        hn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
+        cn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
+    else:
+        hn, cn = _lstm_state_out(state_out, b, hidden)
     gates = torch.empty(b, l, 4, hidden, dtype=torch.float32, device=dev) if save else None
     cs = torch.empty(b, l, hidden, dtype=torch.float32, device=dev) if save else None
     with _timed("lstm_narrow_forward", b * l):
@@ -1446,6 +1466,94 @@ def lstm_narrow_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_
                "rl8_lstm_narrow_reduce_f32")
     w_ih, w_hh_grad, db = torch.split(grads, sizes)
     return {"w_ih": w_ih.view(4 * hidden, d_in), "w_hh": w_hh_grad.view(4 * hidden, hidden), "b": db}
+
+
+# --------------------------------------------------------------------------- #
+# Stacked LSTMs: layers 1.. of a hidden-64 / 128 LSTM, whose input is the lower layer's hs (lstm_narrow_stack_*
+# kernels of lstm_narrow_kernels.hip). One upper layer per call; layer 0 runs the narrow entries above.
+# --------------------------------------------------------------------------- #
+def lstm_stack_supports(hidden: int) -> bool:
+    return bool(load().rl8_lstm_stack_supports(int(hidden)))
+
+
+def _lstm_stack_params(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
+                       b_ih: None | torch.Tensor, b_hh: None | torch.Tensor) -> tuple[int, int, int]:
+    """(b, l, hidden) after the dtype / contiguity / shape checks of the stacked LSTM entries."""
+    _dense(x, torch.float32, "x")
+    if x.ndim != 3:
+        raise ValueError("x must be [B, L, H]")
+    b, l, hidden = x.shape
+    shapes = (("h0", h0, (b, hidden)), ("c0", c0, (b, hidden)), ("w_ih", w_ih, (4 * hidden, hidden)),
+              ("w_hh", w_hh, (4 * hidden, hidden)), ("b_ih", b_ih, (4 * hidden,)), ("b_hh", b_hh, (4 * hidden,)))
+    for name, t, shape in shapes:
+        if t is None:
+            continue
+        _dense(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    if b < 1 or l < 1 or not lstm_stack_supports(hidden):
+        raise ValueError(f"no stacked LSTM kernel for b={b}, l={l}, hidden={hidden}")
+    return b, l, hidden
+
+
+def lstm_stack_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
+                       b_ih: torch.Tensor, b_hh: torch.Tensor, *, save: bool = False,
+                       zin: None | torch.Tensor = None,
+                       state_out: None | tuple[torch.Tensor, torch.Tensor] = None):
+    """One upper layer: x [B, L, H] (the lower layer's hs), h0 / c0 [B, H] -> (hs [B, L, H], hn, cn [B, H], gates,
+    cs) as :func:`lstm_narrow_forward`. ``zin``: [B, L, 4, H] floats of scratch for the input projection (made here
+    when None; a stack hands the same one to every layer)."""
+    x, h0, c0, w_ih, w_hh, b_ih, b_hh = (t.detach() for t in (x, h0, c0, w_ih, w_hh, b_ih, b_hh))
+    b, l, hidden = _lstm_stack_params(x, h0, c0, w_ih, w_hh, b_ih, b_hh)
+    dev = x.device
+    if zin is None:
+        zin = torch.empty(b, l, 4, hidden, dtype=torch.float32, device=dev)
+    _dense(zin, torch.float32, "zin")
+    if tuple(zin.shape) != (b, l, 4, hidden):
+        raise ValueError(f"zin must have shape {(b, l, 4, hidden)}, got {tuple(zin.shape)}")
+    hs = torch.empty(b, l, hidden, dtype=torch.float32, device=dev)
+    if state_out is None:
+        hn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
+        cn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
+    else:
+        hn, cn = _lstm_state_out(state_out, b, hidden)
+    gates = torch.empty(b, l, 4, hidden, dtype=torch.float32, device=dev) if save else None
+    cs = torch.empty(b, l, hidden, dtype=torch.float32, device=dev) if save else None
+    with _timed("lstm_stack_forward", b * l):
+        _check(load().rl8_lstm_stack_forward_f32(_ptr(x), b, l, _ptr(h0), _ptr(c0), _ptr(w_ih), _ptr(w_hh), _ptr(b_ih),
+                                                 _ptr(b_hh), hidden, _ptr(zin), _ptr(hs), _ptr(hn), _ptr(cn),
+                                                 _ptr(gates), _ptr(cs), _stream()), "rl8_lstm_stack_forward_f32")
+    return hs, hn, cn, gates, cs
+
+
+def lstm_stack_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
+                        hs: torch.Tensor, gates: torch.Tensor, cs: torch.Tensor,
+                        dhs: torch.Tensor) -> dict[str, torch.Tensor]:
+    """Gradients ("w_ih", "w_hh", "b": of b_ih and b_hh alike) of one upper layer and "dx" [B, L, H] = dL/dx (the
+    lower layer's dL/dhs) for ``dhs`` [B, L, H], from what :func:`lstm_stack_forward` saved (deterministic). No
+    gradient for h0, c0."""
+    x, h0, c0, w_ih, w_hh, hs, gates, cs, dhs = (t.detach() for t in (x, h0, c0, w_ih, w_hh, hs, gates, cs, dhs))
+    b, l, hidden = _lstm_stack_params(x, h0, c0, w_ih, w_hh, None, None)
+    for name, t, shape in (("hs", hs, (b, l, hidden)), ("gates", gates, (b, l, 4, hidden)), ("cs", cs, (b, l, hidden)),
+                           ("dhs", dhs, (b, l, hidden))):
+        _dense(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    lib = load()
+    ws = torch.empty(int(lib.rl8_lstm_stack_workspace_bytes(b, l, hidden)) // 4, dtype=torch.float32, device=x.device)
+    sizes = (4 * hidden * hidden, 4 * hidden * hidden, 4 * hidden)
+    grads = torch.empty(sum(sizes), dtype=torch.float32, device=x.device)
+    dx = torch.empty(b, l, hidden, dtype=torch.float32, device=x.device)
+    with _timed("lstm_stack_backward", b * l):
+        _check(lib.rl8_lstm_stack_backward_f32(_ptr(x), b, l, _ptr(h0), _ptr(c0), _ptr(w_ih), _ptr(w_hh), hidden,
+                                               _ptr(hs), _ptr(gates), _ptr(cs), _ptr(dhs), _ptr(ws), _ptr(dx),
+                                               _stream()), "rl8_lstm_stack_backward_f32")
+    with _timed("lstm_stack_reduce", b * l):
+        _check(lib.rl8_lstm_stack_reduce_f32(_ptr(ws), b, l, hidden, _ptr(grads), _stream()),
+               "rl8_lstm_stack_reduce_f32")
+    w_ih_grad, w_hh_grad, db = torch.split(grads, sizes)
+    return {"w_ih": w_ih_grad.view(4 * hidden, hidden), "w_hh": w_hh_grad.view(4 * hidden, hidden), "b": db,
+            "dx": dx}
 
 
 def lstm_split_supports(d_in: int) -> bool:

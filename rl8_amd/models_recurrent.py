@@ -107,10 +107,14 @@ def _run_lstm(lstm: nn.LSTM, obs: torch.Tensor, states: TensorDict) -> tuple[tor
 
     h_first = states[DataKeys.HIDDEN_STATES][:, 0, ...]  # [B, layers, hidden]
     c_first = states[DataKeys.CELL_STATES][:, 0, ...]
-    fused = fused_lstm.lstm_forward(lstm, obs, h_first[:, 0], c_first[:, 0]) if lstm.num_layers == 1 else None
+    if lstm.num_layers == 1:
+        fused = fused_lstm.lstm_forward(lstm, obs, h_first[:, 0], c_first[:, 0])
+        if fused is not None:
+            fused = fused[0], fused[1].unsqueeze(1), fused[2].unsqueeze(1)
+    else:
+        fused = fused_lstm.lstm_stack_forward(lstm, obs, h_first, c_first)
     if fused is not None:
-        latents, h_last, c_last = fused
-        h_n, c_n = h_last.unsqueeze(0), c_last.unsqueeze(0)
+        latents, h_new, c_new = fused  # states [B, layers, hidden], the buffer's layout
     else:
         h_0 = h_first.permute(1, 0, 2).contiguous()
         c_0 = c_first.permute(1, 0, 2).contiguous()
@@ -119,10 +123,8 @@ def _run_lstm(lstm: nn.LSTM, obs: torch.Tensor, states: TensorDict) -> tuple[tor
         # 32-bit-indexed workspace faults beyond 2^18 rows per call.
         with torch.backends.cudnn.flags(enabled=False):
             latents, (h_n, c_n) = lstm(obs, (h_0, c_0))
-    new_states = TensorDict(
-        {DataKeys.HIDDEN_STATES: h_n.permute(1, 0, 2), DataKeys.CELL_STATES: c_n.permute(1, 0, 2)},
-        batch_size=obs.size(0),
-    )
+        h_new, c_new = h_n.permute(1, 0, 2), c_n.permute(1, 0, 2)
+    new_states = TensorDict({DataKeys.HIDDEN_STATES: h_new, DataKeys.CELL_STATES: c_new}, batch_size=obs.size(0))
     return latents, new_states, obs.size(0)
 
 

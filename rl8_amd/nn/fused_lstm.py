@@ -11,7 +11,11 @@ narrow kernels (lstm_narrow_kernels.hip: fp32 MFMA forward with the time loop
 inside, backward through time, deterministic weight gradient) under the same
 rules. Parameters stay the module's own; ``lstm_forward`` returns ``None`` for
 any other LSTM (more layers, other widths, projections, bidirectional, non-HIP /
-non-fp32 inputs) and the caller runs the module itself.
+non-fp32 inputs) and the caller runs the module itself. Two or more layers of
+width 64 / 128 without dropout have their own entry, ``lstm_stack_forward``:
+layer 0 on the narrow kernels, the layers above on the lstm_narrow_stack_*
+kernels (input projection over all row-steps, recurrent forward from it, input
+gradient for the layer below).
 
 """
 
@@ -214,6 +218,89 @@ class _NarrowLSTM(torch.autograd.Function):
         dhs = torch.zeros_like(hs) if dhs is None else dhs.contiguous().float()
         g = hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, dhs)
         return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None
+
+
+_STACK_PARAMS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+
+
+def _stack_eligible(lstm: nn.LSTM, x: torch.Tensor) -> bool:
+    """``_narrow_eligible`` with two or more layers and no dropout between them (lstm_narrow_stack_* kernels)."""
+    return (
+        ENABLED
+        and x.is_cuda
+        and x.dtype == torch.float32
+        and x.ndim == 3
+        and lstm.num_layers >= 2
+        and lstm.dropout == 0
+        and lstm.hidden_size in hip.LSTM_NARROW_HIDDEN
+        and lstm.batch_first
+        and lstm.bias
+        and not lstm.bidirectional
+        and lstm.proj_size == 0
+        and x.shape[2] == lstm.input_size
+        and _narrow_supported(lstm.hidden_size, lstm.input_size)
+        and hip.lstm_stack_supports(lstm.hidden_size)
+    )
+
+
+class _StackLSTM(torch.autograd.Function):
+    """A stack of hidden-64 / 128 layers as one node: layer 0 on the narrow kernels, every upper layer on the stack
+    kernels, each reading the lower layer's ``hs`` where the kernel left it (no torch op between the layers). The
+    weights are read in torch layout, nothing packed or cached. ``h0`` / ``c0`` and the returned states are
+    [layers, B, H]; a training pass saves every layer's ``hs``, gates and cell states."""
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, grad_mode, *weights):  # type: ignore[override]
+        layers = len(weights) // 4
+        need_grad = grad_mode and any(ctx.needs_input_grad[4:])
+        b, l, hidden = x.shape[0], x.shape[1], h0.shape[2]
+        hn, cn = torch.empty_like(h0), torch.empty_like(c0)
+        zin = torch.empty(b, l, 4, hidden, dtype=torch.float32, device=x.device)  # the projections' scratch
+        saved, below = [], x
+        for k in range(layers):
+            w = weights[4 * k:4 * k + 4]
+            run = hip.lstm_narrow_forward if k == 0 else functools.partial(hip.lstm_stack_forward, zin=zin)
+            hs, _, _, gates, cs = run(below, h0[k], c0[k], *w, save=need_grad, state_out=(hn[k], cn[k]))
+            saved += [w[0], w[1], hs, gates, cs]
+            below = hs
+        ctx.set_materialize_grads(False)
+        if need_grad:
+            ctx.save_for_backward(x, h0, c0, *saved)
+        ctx.mark_non_differentiable(hn, cn)
+        return below, hn, cn
+
+    @staticmethod
+    def backward(ctx, dhs, dhn, dcn):  # type: ignore[override]
+        x, h0, c0, *saved = ctx.saved_tensors
+        layers = len(saved) // 5
+        top = saved[5 * (layers - 1) + 2]
+        dhs = torch.zeros_like(top) if dhs is None else dhs.contiguous().float()
+        grads: list = [None] * (4 * layers)
+        for k in range(layers - 1, 0, -1):
+            w_ih, w_hh, hs, gates, cs = saved[5 * k:5 * k + 5]
+            g = hip.lstm_stack_backward(saved[5 * (k - 1) + 2], h0[k], c0[k], w_ih, w_hh, hs, gates, cs, dhs)
+            grads[4 * k:4 * k + 4] = g["w_ih"], g["w_hh"], g["b"], g["b"]
+            dhs = g["dx"]  # dL/dx of layer k is dL/dhs of layer k - 1: nothing else reads that layer's outputs
+        _, w_hh, hs, gates, cs = saved[:5]
+        g = hip.lstm_narrow_backward(x, h0[0], c0[0], w_hh, hs, gates, cs, dhs)
+        grads[:4] = g["w_ih"], g["w_hh"], g["b"], g["b"]
+        return (None, None, None, None, *grads)
+
+
+def lstm_stack_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
+    """``lstm(x, (h0, c0))`` for a stack of two or more layers of width 64 / 128: ``x`` [B, L, d], ``h0`` / ``c0``
+    [B, layers, H] (the rollout buffer's layout) -> ``(hs_top [B, L, H], h_n [B, layers, H], c_n [B, layers, H])``,
+    or ``None`` when this LSTM / input is not eligible (one layer, other widths, d > 16, no bias, dropout,
+    projections, bidirectional, non-HIP / non-fp32 inputs). No gradient flows to ``x``, ``h0``, ``c0`` nor out of
+    ``h_n``, ``c_n``."""
+    if not _stack_eligible(lstm, x):
+        return None
+    weights = [getattr(lstm, f"{name}_l{k}") for k in range(lstm.num_layers) for name in _STACK_PARAMS]
+    hs, hn, cn = _StackLSTM.apply(
+        x.contiguous(), h0.float().transpose(0, 1).contiguous(), c0.float().transpose(0, 1).contiguous(),
+        torch.is_grad_enabled(), *weights,
+    )
+    return hs, hn.transpose(0, 1), cn.transpose(0, 1)
 
 
 def lstm_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
