@@ -37,6 +37,10 @@
  *     recurrent  rl8_lstm_pack_split, rl8_lstm_split_state[_bound], rl8_lstm_step_split_f32,
  *                rl8_lstm_rows_backward_pack, rl8_lstm_rows_backward[_heads]_f32, rl8_lstm_wgrad_f16_f32,
  *                rl8_linear_heads_{forward,forward_pair,backward}_f32
+ *     recurrent, hidden width 64 / 128 (model_config={"hidden_size": 64}): rl8_lstm_narrow_{forward,backward,reduce}_f32,
+ *                rl8_lstm_narrow_backward_heads_f32 (one layer, heads of <= 4 outputs: the one-node training pass),
+ *                rl8_lstm_stack_* (layers 1..), rl8_linear_heads_narrow_{forward,forward_pair,backward}_f32,
+ *                rl8_rollout_step_dummy_heads_narrow_f32 (the lean rollout's last launch of a timestep)
  *   PRODUCT, fallback (shapes outside the plane kernels' envelope -- d_in > 16, n_out > 8, hidden != 256 go to eager --
  *   or a switch: RL8_AMD_TOWER_GEMM=f32, RL8_WGRAD_PLANES=bf16, the LSTM switches below), and THE YARDSTICK the parity
  *   tests hold the plane kernels against beside fp64:
@@ -179,6 +183,16 @@ int rl8_rollout_step_dummy_heads_f32(const float *h, const float *w_pol, const f
                                      float *logp_col, float *value_col, float *reward_col, float *obs_col_next,
                                      const float *rdr_t, float *rdr_t1, float gamma, int64_t n, uint64_t seed,
                                      uint64_t step, int64_t env_offset, int deterministic, void *stream);
+
+/* The same for an LSTM of hidden width 64 or 128: h [N][hidden], w_pol [2][hidden], w_vf [1][hidden]; logits and value
+ * exactly as rl8_linear_heads_narrow_forward_f32 forms them.  RL8_ESIZE for other widths; h, w_pol, w_vf 16-byte
+ * aligned, noise 8-byte aligned. */
+int rl8_rollout_step_dummy_heads_narrow_f32(const float *h, int hidden, const float *w_pol, const float *b_pol,
+                                            const float *w_vf, const float *b_vf, const float *noise, float *state,
+                                            int64_t *action_col, float *logp_col, float *value_col, float *reward_col,
+                                            float *obs_col_next, const float *rdr_t, float *rdr_t1, float gamma,
+                                            int64_t n, uint64_t seed, uint64_t step, int64_t env_offset,
+                                            int deterministic, void *stream);
 
 /* Fused per-timestep kernel for CartPole (K = 3): sampler + physics +
  * bookkeeping.  obs_col_next is a [N][5] slab. */
@@ -728,6 +742,36 @@ int rl8_lstm_narrow_backward_f32(const float *x, int64_t b, int l, int d_in, con
                                  const float *dhs, float *workspace, void *stream);
 int rl8_lstm_narrow_reduce_f32(const float *workspace, int64_t b, int l, int hidden, int d_in, float *grads_out,
                                void *stream);
+
+/* rl8_lstm_narrow_backward_f32 with dL/dhs given by the output heads it came through instead of as an array:
+ * dL/dh[b][t][u] = sum_q heads_dout[b][t][q] heads_w[q][u], q < 4, formed inside the backward through time (heads_dout
+ * [b][l][4] and heads_w [4][H], both zero-padded beyond the heads' outputs; heads_dout 16-byte aligned).  Same
+ * workspace, same reduce call after it; the [b][l][H] array is neither written by rl8_linear_heads_narrow_backward_f32
+ * (dh_out NULL) nor read here.  With dhs formed by that entry, the two forms give the same bits. */
+int rl8_lstm_narrow_backward_heads_f32(const float *x, int64_t b, int l, int d_in, const float *h0, const float *c0,
+                                       const float *w_hh, int hidden, const float *hs, const float *gates,
+                                       const float *cs, const float *heads_dout, const float *heads_w, float *workspace,
+                                       void *stream);
+
+/* ---- Output heads of the narrow recurrent models: Linear(H, n) layers on h [m][H], H = 64 or 128, evaluated together
+ * (lstm_narrow_heads_kernels.hip): w [n_out][H] (the heads' weights stacked), b [n_out], n_out <= 8.
+ * rl8_linear_heads_narrow_forward_f32: out [m][n_out] = h x w^T + b, one pass over h.
+ * rl8_linear_heads_narrow_forward_pair_f32: two layers that stay separate arrays (out_a [m][n_a], out_b [m][n_b],
+ *   n_a + n_b <= 8) in the same pass.  The arithmetic for one output and its order depend on H alone: single form, pair
+ *   form and rl8_rollout_step_dummy_heads_narrow_f32 agree bit for bit.
+ * rl8_linear_heads_narrow_backward_f32: grads_out = [dW (n_out H) | db (n_out)] and, unless dh_out is NULL, dh_out
+ *   [m][H] = dout x w.  One partial slab per workgroup in `workspace` (rl8_linear_heads_narrow_workspace_bytes(m, ...)
+ *   bytes, no initialisation; the grid is a function of m alone), summed in a fixed order in fp64: bitwise reproducible.
+ * h and w 16-byte aligned for the forward entries, every other pointer 4-byte aligned; m >= 1; RL8_ESIZE for other
+ * widths and for n_out outside 1..8. */
+int64_t rl8_linear_heads_narrow_workspace_bytes(int64_t m, int hidden, int n_out);
+int rl8_linear_heads_narrow_forward_f32(const float *h, int64_t m, int hidden, const float *w, const float *b, int n_out,
+                                        float *out, void *stream);
+int rl8_linear_heads_narrow_forward_pair_f32(const float *h, int64_t m, int hidden, const float *w_a, const float *b_a,
+                                             int n_a, float *out_a, const float *w_b, const float *b_b, int n_b,
+                                             float *out_b, void *stream);
+int rl8_linear_heads_narrow_backward_f32(const float *h, const float *dout, int64_t m, int hidden, const float *w,
+                                         int n_out, float *dh_out, float *workspace, float *grads_out, void *stream);
 
 /* ---- Stacked LSTMs: layers 1.. of nn.LSTM(d_in, H, num_layers >= 2), H = 64 or 128, biased, batch_first, fp32, no
  * dropout (lstm_narrow_kernels.hip, lstm_narrow_stack_*).  One upper layer per call: its input x [b][l][H] is the

@@ -18,8 +18,8 @@ sequence-major once per ``step()`` in buffer order and every SGD iteration reads
 that copy (the reference draws ``randperm`` and gathers per iteration,
 ``src/rl8/_utils.py:211-225``; ``bench.py --recurrent --minibatches 4`` times the
 shuffled path). A training pass through the default models is ONE autograd node
-(``nn/fused_lstm.py:_FusedLSTMHeads``): the heads' data gradient is formed inside
-the backward-through-time kernel.
+(``nn/fused_lstm.py:_FusedLSTMHeads``, ``_NarrowLSTMHeads`` at hidden width 64 / 128):
+the heads' data gradient is formed inside the backward-through-time kernel.
 
 """
 
@@ -64,7 +64,9 @@ class _LeanRollout:
     ``policy.sample()`` + ``_fused_step`` (tests/test_algorithm_gpu.py:
     ``test_recurrent_lean_and_plumbed_rollouts_agree``); what goes is ~150 us of
     tensordict / autograd-function / ``torch.cat`` host work per timestep, which at
-    8192 environments per GPU (BASELINE configs[4]) was twice the kernels' time."""
+    8192 environments per GPU (BASELINE configs[4]) was twice the kernels' time. A one-layer LSTM of width 64 / 128
+    takes the narrow route (``_step_narrow``: ``rl8_lstm_narrow_forward_f32`` with l = 1, then
+    ``rl8_rollout_step_dummy_heads_narrow_f32``), decided before any width-256 rule: no packs, no planes, no plan."""
 
     TIMER_EVERY = 16  # with hip.timer enabled, only every 16th timestep is bracketed by events
 
@@ -78,20 +80,29 @@ class _LeanRollout:
         self.d_in = int(tm[DataKeys.OBS].shape[-1])
         self.k = int(model.feature_head.out_features)
         dev = tm[DataKeys.OBS].device
-        self.split = fused_lstm._plan(model.lstm.input_size, n).forward_planes
-        if self.split:  # bf16-plane step kernel: W_hh planes, [w_ih | bias] rows, planes of h_{t-1}
-            self.packed, self.wb = fused_lstm._packs(model.lstm, "split")
+        lstm = model.lstm
+        self.hidden = int(lstm.hidden_size)
+        # width 64 / 128: the narrow forward kernel with l = 1 on the weights as they are -- no packs, no planes, no plan
+        self.narrow = self.hidden in hip.LSTM_NARROW_HIDDEN
+        if self.narrow:
+            self.split, self.packed, self.wb = False, None, None
+            self.lstm_params = [p.detach().contiguous() for p in (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0,
+                                                                  lstm.bias_hh_l0)]
         else:
-            self.packed, self.wb = fused_lstm._packs(model.lstm, "step"), None
+            self.split = fused_lstm._plan(lstm.input_size, n).forward_planes
+            if self.split:  # bf16-plane step kernel: W_hh planes, [w_ih | bias] rows, planes of h_{t-1}
+                self.packed, self.wb = fused_lstm._packs(lstm, "split")
+            else:
+                self.packed, self.wb = fused_lstm._packs(lstm, "step"), None
         # parameters are leaf tensors: .detach() shares storage (kept alive on self)
         self.params = [p.detach().contiguous() for p in (model.feature_head.weight, model.feature_head.bias,
                                                          model.vf_head.weight, model.vf_head.bias)]
         cache = algo.__dict__.setdefault("_lean_scratch", {})
-        key = (n, self.k, str(dev))
+        key = (n, self.k, str(dev), self.hidden)
         if cache.get("key") != key:
-            cache.update(key=key, hs=torch.empty(n, hip.LSTM_HIDDEN, device=dev),
+            cache.update(key=key, hs=torch.empty(n, self.hidden, device=dev),
                          logits=torch.empty(n, self.k, device=dev), value=torch.empty(n, 1, device=dev),
-                         planes=hip.lstm_state_planes(n, dev, copies=2))
+                         planes=None if self.narrow else hip.lstm_state_planes(n, dev, copies=2))
         self.hs, self.logits, self.value, self.planes = cache["hs"], cache["logits"], cache["value"], cache["planes"]
         rdr = tm.get(DataKeys.REVERSED_DISCOUNTED_RETURNS)
 
@@ -106,9 +117,14 @@ class _LeanRollout:
         self.gamma = float(torch.tensor(algo.hparams.gamma, dtype=torch.float32))
         self.seed, self.env_offset = algo.noise.seed, algo.env.env_offset
         self.deterministic = int(deterministic)
-        self.ptrs = [t.data_ptr() for t in (self.packed, self.hs, self.logits, self.value, *self.params)]
-        self.split_ptrs = (self.planes.data_ptr(), self.wb.data_ptr() if self.wb is not None else None)
-        self.planes_half = self.planes.numel() // 2
+        self.ptrs = [t.data_ptr() if t is not None else None
+                     for t in (self.packed, self.hs, self.logits, self.value, *self.params)]
+        if self.narrow:
+            self.lstm_ptrs = [t.data_ptr() for t in self.lstm_params]
+            self.split_ptrs, self.planes_half = (None, None), 0
+        else:
+            self.split_ptrs = (self.planes.data_ptr(), self.wb.data_ptr() if self.wb is not None else None)
+            self.planes_half = self.planes.numel() // 2
         self.planes_of = -1   # timestep whose hidden state the planes buffer (t & 1) holds (-1: none)
         # two-way categorical + value head: evaluated inside the timestep's last kernel (switched off: two launches)
         self.fuse_heads = self.k == 2 and fused_lstm._rollout_fuse_heads()
@@ -126,16 +142,23 @@ class _LeanRollout:
             return False
         lstm = model.lstm
         obs = algo._tm[DataKeys.OBS]
-        return (fused_lstm.ENABLED and lstm.num_layers == 1 and lstm.hidden_size == hip.LSTM_HIDDEN and lstm.bias
-                and lstm.proj_size == 0 and not lstm.bidirectional and hip.lstm_supports(lstm.input_size)
-                and obs.dtype == torch.float32 and model.vf_head.bias is not None
-                and all(p.dtype == torch.float32 for p in model.parameters()))
+        if not (fused_lstm.ENABLED and lstm.num_layers == 1 and lstm.bias and lstm.proj_size == 0
+                and not lstm.bidirectional):
+            return False
+        if lstm.hidden_size in hip.LSTM_NARROW_HIDDEN:  # (decided before any width-256 rule, as in lstm_forward)
+            kernels = lstm.batch_first and hip.lstm_narrow_supports(lstm.hidden_size, lstm.input_size)
+        else:
+            kernels = lstm.hidden_size == hip.LSTM_HIDDEN and hip.lstm_supports(lstm.input_size)
+        return bool(kernels and obs.dtype == torch.float32 and model.vf_head.bias is not None
+                    and all(p.dtype == torch.float32 for p in model.parameters()))
 
     def step(self, t: int, noise: None | torch.Tensor, step_id: int) -> None:
         lib, n, stream = self.lib, self.n, hip._stream()
         packed, hs, logits, value, w_pol, b_pol, w_vf, b_vf = self.ptrs
         at = lambda col, i: col[0] + i * col[1]  # noqa: E731
         timed = hip.timer.enabled and t % self.TIMER_EVERY == 0
+        if self.narrow:
+            return self._step_narrow(t, noise, step_id, timed)
         if self.split:
             planes, wb = self.split_ptrs
             H = hip.LSTM_HIDDEN
@@ -179,6 +202,41 @@ class _LeanRollout:
                 at(self.act, t), at(self.logp, t), at(self.val, t), at(self.rew, t), at(self.obs, t + 1),
                 at(self.rdr, t) if self.rdr else None, at(self.rdr, t + 1) if self.rdr else None, self.gamma, n,
                 self.seed, step_id, self.env_offset, self.deterministic, stream), "rl8_rollout_step_dummy_f32")
+
+
+    def _step_narrow(self, t: int, noise: None | torch.Tensor, step_id: int, timed: bool) -> None:
+        """One timestep behind an LSTM of width 64 / 128: the narrow forward with l = 1 (h_t and c_t straight into the
+        state buffers' next column, which is a dense [N][H] slab for one layer), then the two heads inside the
+        sampler + env.step + bookkeeping kernel, or the pair form and that kernel."""
+        lib, n, stream, H = self.lib, self.n, hip._stream(), self.hidden
+        _, hs, logits, value, w_pol, b_pol, w_vf, b_vf = self.ptrs
+        w_ih, w_hh, b_ih, b_hh = self.lstm_ptrs
+        at = lambda col, i: col[0] + i * col[1]  # noqa: E731
+        with hip._timed("lstm_narrow_forward", n) if timed else _NO_TIMER:
+            hip._check(lib.rl8_lstm_narrow_forward_f32(at(self.obs, t), n, 1, self.d_in, at(self.h, t), at(self.c, t), w_ih,
+                                                       w_hh, b_ih, b_hh, H, hs, at(self.h, t + 1), at(self.c, t + 1), None,
+                                                       None, stream), "rl8_lstm_narrow_forward_f32")
+        tail = (noise.data_ptr() if noise is not None else None, self.state_ptr, at(self.act, t), at(self.logp, t),
+                at(self.val, t), at(self.rew, t), at(self.obs, t + 1), at(self.rdr, t) if self.rdr else None,
+                at(self.rdr, t + 1) if self.rdr else None, self.gamma, n, self.seed, step_id, self.env_offset,
+                self.deterministic, stream)
+        if self.fuse_heads:
+            with hip._timed("rollout_step_dummy_heads_narrow", n) if timed else _NO_TIMER:
+                hip._check(lib.rl8_rollout_step_dummy_heads_narrow_f32(hs, H, w_pol, b_pol, w_vf, b_vf, *tail),
+                           "rl8_rollout_step_dummy_heads_narrow_f32")
+            return
+        with hip._timed("linear_heads_narrow_forward", n) if timed else _NO_TIMER:
+            if self.k + 1 <= hip.HEADS_MAX_OUT:  # both heads in one pass over h_t
+                hip._check(lib.rl8_linear_heads_narrow_forward_pair_f32(hs, n, H, w_pol, b_pol, self.k, logits, w_vf, b_vf,
+                                                                        1, value, stream),
+                           "rl8_linear_heads_narrow_forward_pair_f32")
+            else:
+                hip._check(lib.rl8_linear_heads_narrow_forward_f32(hs, n, H, w_pol, b_pol, self.k, logits, stream),
+                           "rl8_linear_heads_narrow_forward_f32")
+                hip._check(lib.rl8_linear_heads_narrow_forward_f32(hs, n, H, w_vf, b_vf, 1, value, stream),
+                           "rl8_linear_heads_narrow_forward_f32")
+        with hip._timed("rollout_step_dummy", n) if timed else _NO_TIMER:
+            hip._check(lib.rl8_rollout_step_dummy_f32(1, 0, logits, None, value, *tail), "rl8_rollout_step_dummy_f32")
 
 
 class _NoTimer:

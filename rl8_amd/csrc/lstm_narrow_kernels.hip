@@ -258,99 +258,21 @@ template <int H>
 __global__ __launch_bounds__(Geo<H>::kThreads, Geo<H>::kWgPerCU) void lstm_narrow_backward_kernel(
     int64_t b, int l, const float *__restrict__ c0, const float *__restrict__ w_hh, const float *__restrict__ gates,
     const float *__restrict__ cs, const float *__restrict__ dhs, float *__restrict__ dz) {
-  using G = Geo<H>;
-  constexpr int MT = G::MTB, R = G::RB, LD = G::LD;
-  extern __shared__ float lds[];  // [R][LD]: dz of the step
-  const int tid = threadIdx.x, lane = tid & 63, qq = lane >> 4, l16 = lane & 15;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int u = 16 * wave + l16;
+  constexpr bool HEADS = false;
+  const float *heads_dout = nullptr, *heads_w = nullptr;
+#include "lstm_narrow_backward_body.hip.h"
+}
 
-  // B operand of dh_{t-1} = dz x W_hh: wt[4g + e] = W_hh[16g + 4qq + e][u], k over the 4H gate columns.
-  float wt[H];
-#pragma unroll
-  for (int g = 0; g < H / 4; ++g)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) wt[4 * g + e] = w_hh[(int64_t)(16 * g + 4 * qq + e) * H + u];
-  const int v_state = (4 * qq * H + u) * 4, v_seq = (4 * qq * l * H + u) * 4, v_gates = (4 * qq * l * 4 * H + u) * 4;
-
-  const int64_t tiles = (b + R - 1) / R;
-  for (int64_t ti = blockIdx.x; ti < tiles; ti += gridDim.x) {
-    const int64_t b0 = ti * R;
-    float dh_carry[MT][4], dc_carry[MT][4];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dh_carry[mt][r] = dc_carry[mt][r] = 0.0f;
-    // (buffer descriptors as in the forward: rows past b read 0 and drop their stores)
-    const int rows = (int)(b - b0 < R ? b - b0 : R);
-    const uint32_t span = (uint32_t)((rows - 1) * l + 1) * 4;
-    const __amdgpu_buffer_rsrc_t c0r = buffer_rsrc(c0 + b0 * H, (uint32_t)rows * H * 4);
-    for (int t = l - 1; t >= 0; --t) {
-      const int64_t rs0 = b0 * l + t;
-      const __amdgpu_buffer_rsrc_t gr = buffer_rsrc(gates + rs0 * 4 * H, span * 4 * H);
-      const __amdgpu_buffer_rsrc_t zr = buffer_rsrc(dz + rs0 * 4 * H, span * 4 * H);
-      const __amdgpu_buffer_rsrc_t cr = buffer_rsrc(cs + rs0 * H, span * H);
-      const __amdgpu_buffer_rsrc_t cpr = buffer_rsrc(cs + (t > 0 ? rs0 - 1 : 0) * H, span * H);
-      const __amdgpu_buffer_rsrc_t dr = buffer_rsrc(dhs + rs0 * H, span * H);
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int sr = 16 * mt + r, so_g = sr * l * 4 * H * 4, so_s = sr * l * H * 4;
-          const float ig = buffer_load_f32(gr, v_gates + so_g, 0), fg = buffer_load_f32(gr, v_gates + so_g + H * 4, 0);
-          const float gg = buffer_load_f32(gr, v_gates + so_g + 2 * H * 4, 0);
-          const float og = buffer_load_f32(gr, v_gates + so_g + 3 * H * 4, 0);
-          const float ct = buffer_load_f32(cr, v_seq + so_s, 0);
-          const float cp = t > 0 ? buffer_load_f32(cpr, v_seq + so_s, 0) : buffer_load_f32(c0r, v_state + sr * H * 4, 0);
-          const float dh = buffer_load_f32(dr, v_seq + so_s, 0) + dh_carry[mt][r];
-          const float tc = tanh_f(ct);
-          const float d_o = dh * tc * (og * (1.0f - og));
-          const float dc = __builtin_fmaf(dh * og, 1.0f - tc * tc, dc_carry[mt][r]);
-          const float d_i = dc * gg * (ig * (1.0f - ig));
-          const float d_g = dc * ig * (1.0f - gg * gg);
-          const float d_f = dc * cp * (fg * (1.0f - fg));
-          dc_carry[mt][r] = dc * fg;
-          buffer_store_f32(d_i, zr, v_gates + so_g, 0);
-          buffer_store_f32(d_f, zr, v_gates + so_g + H * 4, 0);
-          buffer_store_f32(d_g, zr, v_gates + so_g + 2 * H * 4, 0);
-          buffer_store_f32(d_o, zr, v_gates + so_g + 3 * H * 4, 0);
-          float *zs = lds + (16 * mt + 4 * qq + r) * LD + u;
-          zs[0] = d_i;
-          zs[H] = d_f;
-          zs[2 * H] = d_g;
-          zs[3 * H] = d_o;
-        }
-      if (t == 0) break;  // (dh_{-1}: a gradient to h0, not formed)
-      __syncthreads();  // the step's dz is complete
-      f32x4 acc[MT];
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      f32x4 a[MT], an[MT];  // (read a group ahead, fenced: as in the forward)
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) a[mt] = *reinterpret_cast<const f32x4 *>(lds + (16 * mt + l16) * LD + 4 * qq);
-#pragma unroll
-      for (int g = 0; g < H / 4; ++g) {
-        if (g + 1 < H / 4) {
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-            an[mt] = *reinterpret_cast<const f32x4 *>(lds + (16 * mt + l16) * LD + 16 * (g + 1) + 4 * qq);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-            acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt][e], wt[4 * g + e], acc[mt], 0, 0, 0);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) a[mt] = an[mt];
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dh_carry[mt][r] = acc[mt][r];
-      __syncthreads();  // every wave has read the step's dz
-    }
-  }
+// The same with dL/dh_t formed from heads_dout [b][l][4] and heads_w [4][H] (zero-padded beyond the heads' outputs)
+// instead of read from dhs [b][l][H].
+template <int H>
+__global__ __launch_bounds__(Geo<H>::kThreads, Geo<H>::kWgPerCU) void lstm_narrow_backward_heads_kernel(
+    int64_t b, int l, const float *__restrict__ c0, const float *__restrict__ w_hh, const float *__restrict__ gates,
+    const float *__restrict__ cs, const float *__restrict__ heads_dout, const float *__restrict__ heads_w,
+    float *__restrict__ dz) {
+  constexpr bool HEADS = true;
+  const float *dhs = nullptr;
+#include "lstm_narrow_backward_body.hip.h"
 }
 
 // dW[j][k] += sum over the chunk's rows (b, t) of dz[b][t][j] * a[b][t][k], a = [h_{t-1} (h0 at t = 0) | x_t | 1 | 0..]:
@@ -480,6 +402,18 @@ int launch_backward(hipStream_t s, int64_t b, int l, const float *c0, const floa
   auto *kernel = &lstm_narrow_backward_kernel<H>;
   if (const int e = allow_dynamic_lds(opt_in, reinterpret_cast<const void *>(kernel), (int)bytes)) return e;
   kernel<<<tile_grid<H>(b, Geo<H>::RB), Geo<H>::kThreads, bytes, s>>>(b, l, c0, w_hh, gates, cs, dhs, dz);
+  return launch_status();
+}
+
+template <int H>
+int launch_backward_heads(hipStream_t s, int64_t b, int l, const float *c0, const float *w_hh, const float *gates,
+                          const float *cs, const float *heads_dout, const float *heads_w, float *dz) {
+  constexpr size_t bytes = sizeof(float) * Geo<H>::RB * Geo<H>::LD;
+  static LdsOptIn opt_in;
+  auto *kernel = &lstm_narrow_backward_heads_kernel<H>;
+  if (const int e = allow_dynamic_lds(opt_in, reinterpret_cast<const void *>(kernel), (int)bytes)) return e;
+  kernel<<<tile_grid<H>(b, Geo<H>::RB), Geo<H>::kThreads, bytes, s>>>(b, l, c0, w_hh, gates, cs, heads_dout, heads_w,
+                                                                      dz);
   return launch_status();
 }
 
@@ -1003,6 +937,34 @@ RL8_API int rl8_lstm_narrow_backward_f32(const float *x, int64_t b, int l, int d
                      : lstm_narrow::launch_wgrad<64, 16>(s, x, b, l, d_in, h0, hs, dz, slabs);
   }
   st = lstm_narrow::launch_backward<128>(s, b, l, c0, w_hh, gates, cs, dhs, dz);
+  if (st != RL8_OK) return st;
+  return narrow_in ? lstm_narrow::launch_wgrad<128, 4>(s, x, b, l, d_in, h0, hs, dz, slabs)
+                   : lstm_narrow::launch_wgrad<128, 16>(s, x, b, l, d_in, h0, hs, dz, slabs);
+}
+
+// rl8_lstm_narrow_backward_f32 with dL/dhs given by the output heads it came through (heads_dout [b][l][4], heads_w
+// [4][H], both zero-padded beyond the heads' outputs): the same workspace, the same weight-gradient kernel after it.
+RL8_API int rl8_lstm_narrow_backward_heads_f32(const float *x, int64_t b, int l, int d_in, const float *h0,
+                                               const float *c0, const float *w_hh, int hidden, const float *hs,
+                                               const float *gates, const float *cs, const float *heads_dout,
+                                               const float *heads_w, float *workspace, void *stream) {
+  if (!x || !h0 || !c0 || !w_hh || !hs || !gates || !cs || !heads_dout || !heads_w || !workspace) return RL8_ENULL;
+  if (!lstm_narrow_sizes_ok(b, l, hidden) || !rl8_lstm_narrow_supports(hidden, d_in)) return RL8_ESIZE;
+  for (const void *p : {(const void *)x, (const void *)h0, (const void *)c0, (const void *)w_hh, (const void *)hs,
+                        (const void *)gates, (const void *)cs, (const void *)heads_w})
+    if (!lstm_narrow::aligned4(p)) return RL8_EALIGN;
+  if (!aligned16(heads_dout) || !aligned16(workspace)) return RL8_EALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  float *dz = workspace, *slabs = workspace + lstm_narrow::dz_floats(b, l, hidden);
+  const bool narrow_in = d_in <= 4;
+  int st;
+  if (hidden == 64) {
+    st = lstm_narrow::launch_backward_heads<64>(s, b, l, c0, w_hh, gates, cs, heads_dout, heads_w, dz);
+    if (st != RL8_OK) return st;
+    return narrow_in ? lstm_narrow::launch_wgrad<64, 4>(s, x, b, l, d_in, h0, hs, dz, slabs)
+                     : lstm_narrow::launch_wgrad<64, 16>(s, x, b, l, d_in, h0, hs, dz, slabs);
+  }
+  st = lstm_narrow::launch_backward_heads<128>(s, b, l, c0, w_hh, gates, cs, heads_dout, heads_w, dz);
   if (st != RL8_OK) return st;
   return narrow_in ? lstm_narrow::launch_wgrad<128, 4>(s, x, b, l, d_in, h0, hs, dz, slabs)
                    : lstm_narrow::launch_wgrad<128, 16>(s, x, b, l, d_in, h0, hs, dz, slabs);

@@ -15,6 +15,7 @@
 // Distribution.sample API and custom environments.
 #include "common.hip.h"
 #include "device_math.hip.h"
+#include "lstm_narrow_heads.hip.h"
 
 namespace rl8 {
 
@@ -283,6 +284,46 @@ __global__ __launch_bounds__(kBlock) void rollout_step_dummy_heads_kernel(
   }
 }
 
+// The same for an LSTM of hidden width H = 64 or 128 (h [N][H]): the two heads as linear_heads_narrow_forward_kernel
+// forms them (lstm_narrow_heads.hip.h: bit for bit the launches it replaces), the rest as above.
+template <int H>
+__global__ __launch_bounds__(kBlock) void rollout_step_dummy_heads_narrow_kernel(
+    const float4 *__restrict__ h, const float *__restrict__ w_pol, const float *__restrict__ b_pol,
+    const float *__restrict__ w_vf, const float *__restrict__ b_vf, const float *__restrict__ noise,
+    float *__restrict__ state, int64_t *__restrict__ action_col, float *__restrict__ logp_col,
+    float *__restrict__ value_col, float *__restrict__ reward_col, float *__restrict__ obs_col_next,
+    const float *__restrict__ rdr_t, float *__restrict__ rdr_t1, float gamma, int64_t n, uint64_t seed, uint64_t step,
+    int64_t env_offset, int deterministic) {
+  constexpr int kOut = 3;
+  __shared__ float4 ws[kOut * H / 4];
+  narrow_heads::stage_weights<H>(ws, kOut, w_pol, 2, w_vf);
+  __syncthreads();
+  const int q4 = threadIdx.x & 3;
+  const int64_t stride = (int64_t)gridDim.x * (kBlock / 4);
+  for (int64_t i = (int64_t)blockIdx.x * (kBlock / 4) + (threadIdx.x >> 2); i < n; i += stride) {
+    float o[kOut];
+    narrow_heads::row_dots<H, kOut>(h + i * (H / 4), ws, q4, o);
+    if (q4 != 0) continue;
+    const float x[2] = {o[0] + b_pol[0], o[1] + b_pol[1]};
+    float q[2], lp;
+    if (noise) {
+      const float2 qn = *reinterpret_cast<const float2 *>(noise + 2 * i);
+      q[0] = qn.x; q[1] = qn.y;
+    }
+    const int act = categorical_draw<2>(x, noise ? q : nullptr, seed, (uint64_t)(i + env_offset), step, 0u,
+                                        deterministic != 0, &lp);
+    action_col[i] = act;
+    const float s = dummy_step_discrete(state[i], act);
+    const float r = -fabsf(s);
+    state[i] = s;
+    obs_col_next[i] = s;
+    reward_col[i] = r;
+    logp_col[i] = lp;
+    value_col[i] = o[2] + b_vf[0];
+    if (rdr_t1) rdr_t1[i] = gamma * rdr_t[i] + r;
+  }
+}
+
 // CartPole (K = 3): one lane per env; obs[t+1] rows are 20 B so the five
 // components of 64 consecutive envs fill 1280 contiguous bytes per wave.
 __global__ __launch_bounds__(kBlock) void rollout_step_cartpole_kernel(
@@ -444,6 +485,34 @@ RL8_API int rl8_rollout_step_dummy_heads_f32(const float *h, const float *w_pol,
   rollout_step_dummy_heads_kernel<<<grid_for(n, kBlock / 4), kBlock, 0, (hipStream_t)stream>>>(
       reinterpret_cast<const float4 *>(h), w_pol, b_pol, w_vf, b_vf, noise, state, action_col, logp_col, value_col,
       reward_col, obs_col_next, rdr_t, rdr_t1, gamma, n, seed, step, env_offset, deterministic);
+  return launch_status();
+}
+
+RL8_API int rl8_rollout_step_dummy_heads_narrow_f32(const float *h, int hidden, const float *w_pol, const float *b_pol,
+                                                    const float *w_vf, const float *b_vf, const float *noise,
+                                                    float *state, int64_t *action_col, float *logp_col,
+                                                    float *value_col, float *reward_col, float *obs_col_next,
+                                                    const float *rdr_t, float *rdr_t1, float gamma, int64_t n,
+                                                    uint64_t seed, uint64_t step, int64_t env_offset, int deterministic,
+                                                    void *stream) {
+  if (!h || !w_pol || !b_pol || !w_vf || !b_vf || !state || !action_col || !logp_col || !value_col || !reward_col ||
+      !obs_col_next)
+    return RL8_ENULL;
+  if ((rdr_t == nullptr) != (rdr_t1 == nullptr)) return RL8_ENULL;
+  if (n <= 0 || (hidden != 64 && hidden != 128)) return RL8_ESIZE;
+  if (!aligned16(h) || !aligned16(w_pol) || !aligned16(w_vf) || (noise && (reinterpret_cast<uintptr_t>(noise) & 7u)))
+    return RL8_EALIGN;
+  const int grid = grid_for(n, kBlock / 4);
+  hipStream_t s = (hipStream_t)stream;
+  const float4 *h4 = reinterpret_cast<const float4 *>(h);
+  if (hidden == 64)
+    rollout_step_dummy_heads_narrow_kernel<64><<<grid, kBlock, 0, s>>>(
+        h4, w_pol, b_pol, w_vf, b_vf, noise, state, action_col, logp_col, value_col, reward_col, obs_col_next, rdr_t,
+        rdr_t1, gamma, n, seed, step, env_offset, deterministic);
+  else
+    rollout_step_dummy_heads_narrow_kernel<128><<<grid, kBlock, 0, s>>>(
+        h4, w_pol, b_pol, w_vf, b_vf, noise, state, action_col, logp_col, value_col, reward_col, obs_col_next, rdr_t,
+        rdr_t1, gamma, n, seed, step, env_offset, deterministic);
   return launch_status();
 }
 

@@ -111,6 +111,8 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_rollout_step_dummy_f32": [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _u64, _u64, _i64, _i32, _vp],
     "rl8_rollout_step_dummy_heads_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _u64,
                                          _u64, _i64, _i32, _vp],
+    "rl8_rollout_step_dummy_heads_narrow_f32": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32,
+                                                _i64, _u64, _u64, _i64, _i32, _vp],
     "rl8_mountain_car_step_f32": [_vp, _vp, C.POINTER(MountainCarCfg), _vp, _i64, _vp, _i64, _vp],
     "rl8_mountain_car_reset_f32": [_vp, _i64, _u64, _u64, _i64, _vp, _i64, _vp],
     "rl8_rollout_step_mountain_car_f32": [_vp, _vp, _vp, _vp, C.POINTER(MountainCarCfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _u64, _u64, _i64, _i32, _vp],
@@ -184,6 +186,11 @@ SIGNATURES: dict[str, list[Any]] = {
                                     _vp],
     "rl8_lstm_narrow_backward_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_lstm_narrow_reduce_f32": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "rl8_lstm_narrow_backward_heads_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rl8_linear_heads_narrow_workspace_bytes": [_i64, _i32, _i32],
+    "rl8_linear_heads_narrow_forward_f32": [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp],
+    "rl8_linear_heads_narrow_forward_pair_f32": [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp],
+    "rl8_linear_heads_narrow_backward_f32": [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp],
     "rl8_lstm_stack_supports": [_i32],
     "rl8_lstm_stack_workspace_bytes": [_i64, _i32, _i32],
     "rl8_lstm_stack_forward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -222,7 +229,7 @@ def load() -> C.CDLL:
                             "rl8_lstm_split_packed_bytes", "rl8_lstm_split_wb_floats", "rl8_lstm_split_state_bytes",
                             "rl8_mlp_f16_packed_bytes", "rl8_lstm_rows_backward_pack_bytes", "rl8_pw_workspace_bytes",
                             "rl8_mlp_narrow_workspace_bytes", "rl8_lstm_narrow_workspace_bytes",
-                            "rl8_lstm_stack_workspace_bytes")
+                            "rl8_lstm_stack_workspace_bytes", "rl8_linear_heads_narrow_workspace_bytes")
                 else C.c_int
             )
         built = int(lib.rl8_abi_version(None, 0))
@@ -1441,14 +1448,18 @@ def lstm_narrow_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_i
 
 
 def lstm_narrow_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_hh: torch.Tensor, hs: torch.Tensor,
-                         gates: torch.Tensor, cs: torch.Tensor, dhs: torch.Tensor) -> dict[str, torch.Tensor]:
+                         gates: torch.Tensor, cs: torch.Tensor, dhs: None | torch.Tensor, *,
+                         heads: None | tuple[torch.Tensor, torch.Tensor] = None) -> dict[str, torch.Tensor]:
     """Gradients ("w_ih", "w_hh", "b": of b_ih and b_hh alike) for dL/dhs ``dhs`` [B, L, H], from what
     :func:`lstm_narrow_forward` saved: backward through time, partial slabs per sequence chunk summed in a fixed
-    order (deterministic). No gradient for x, h0, c0."""
-    x, h0, c0, w_hh, hs, gates, cs, dhs = (t.detach() for t in (x, h0, c0, w_hh, hs, gates, cs, dhs))
+    order (deterministic). No gradient for x, h0, c0. ``heads`` = (dout [B * L, n], w [n, H]), n <= 4, instead of
+    ``dhs`` (None): dL/dh_t = dout x w is formed inside the backward through time (rl8_lstm_narrow_backward_heads_f32)."""
+    if (heads is None) == (dhs is None):
+        raise ValueError("lstm_narrow_backward: either dhs or heads")
+    x, h0, c0, w_hh, hs, gates, cs = (t.detach() for t in (x, h0, c0, w_hh, hs, gates, cs))
     b, l, d_in, hidden = _lstm_narrow_params(x, h0, c0, None, w_hh, None, None)
     for name, t, shape in (("hs", hs, (b, l, hidden)), ("gates", gates, (b, l, 4, hidden)), ("cs", cs, (b, l, hidden)),
-                           ("dhs", dhs, (b, l, hidden))):
+                           *([("dhs", dhs.detach(), (b, l, hidden))] if heads is None else [])):
         _dense(t, torch.float32, name)
         if tuple(t.shape) != shape:
             raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
@@ -1457,10 +1468,26 @@ def lstm_narrow_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_
                      device=x.device)
     sizes = (4 * hidden * d_in, 4 * hidden * hidden, 4 * hidden)
     grads = torch.empty(sum(sizes), dtype=torch.float32, device=x.device)
-    with _timed("lstm_narrow_backward", b * l):
-        _check(lib.rl8_lstm_narrow_backward_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_hh), hidden, _ptr(hs),
-                                                _ptr(gates), _ptr(cs), _ptr(dhs), _ptr(ws), _stream()),
-               "rl8_lstm_narrow_backward_f32")
+    if heads is not None:
+        dout, w = heads
+        n = w.shape[0] if w.ndim == 2 else -1
+        if not 1 <= n <= ROWS_BACKWARD_HEADS or tuple(w.shape) != (n, hidden) or dout.numel() != b * l * n \
+                or dout.dtype != torch.float32 or w.dtype != torch.float32:
+            raise ValueError(f"heads: float32 dout [B * L, n], w [n, {hidden}], n <= {ROWS_BACKWARD_HEADS}")
+        # four floats per row-step, four weight rows, zero-padded
+        dout4 = torch.zeros(b * l, ROWS_BACKWARD_HEADS, dtype=torch.float32, device=x.device)
+        dout4[:, :n] = dout.detach().reshape(b * l, n)
+        w4 = torch.zeros(ROWS_BACKWARD_HEADS, hidden, dtype=torch.float32, device=x.device)
+        w4[:n] = w.detach()
+        with _timed("lstm_narrow_backward", b * l):  # (one name for both forms, as "lstm_rows_backward" is at 256)
+            _check(lib.rl8_lstm_narrow_backward_heads_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_hh), hidden,
+                                                          _ptr(hs), _ptr(gates), _ptr(cs), _ptr(dout4), _ptr(w4),
+                                                          _ptr(ws), _stream()), "rl8_lstm_narrow_backward_heads_f32")
+    else:
+        with _timed("lstm_narrow_backward", b * l):
+            _check(lib.rl8_lstm_narrow_backward_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_hh), hidden,
+                                                    _ptr(hs), _ptr(gates), _ptr(cs), _ptr(dhs.detach()), _ptr(ws),
+                                                    _stream()), "rl8_lstm_narrow_backward_f32")
     with _timed("lstm_narrow_reduce", b * l):
         _check(lib.rl8_lstm_narrow_reduce_f32(_ptr(ws), b, l, hidden, d_in, _ptr(grads), _stream()),
                "rl8_lstm_narrow_reduce_f32")
@@ -1882,3 +1909,98 @@ def linear_heads_backward(h: torch.Tensor, dout: torch.Tensor, w: torch.Tensor, 
                                                  C.byref(rows), _stream()), "rl8_linear_heads_backward_f32")
     small = partials[: rows.value].sum(0)
     return dh, small[: n * LSTM_HIDDEN].view(n, LSTM_HIDDEN), small[n * LSTM_HIDDEN :]
+
+
+# --------------------------------------------------------------------------- #
+# Output heads of the narrow recurrent models: Linear(H, n) layers on h [M, H], H = 64 or 128
+# (lstm_narrow_heads_kernels.hip).
+# --------------------------------------------------------------------------- #
+def _heads_narrow_params(name: str, h: torch.Tensor, *layers: tuple[torch.Tensor, None | torch.Tensor]) -> tuple[int, int]:
+    """(m, hidden) after the dtype / contiguity / shape checks of the narrow heads entries; ``layers``: (w, b) pairs."""
+    _dense(h, torch.float32, "h")
+    hidden = h.shape[1] if h.ndim == 2 else -1
+    if hidden not in LSTM_NARROW_HIDDEN or h.shape[0] < 1:
+        raise ValueError(f"{name}: h [M, H], M >= 1, H in {LSTM_NARROW_HIDDEN}, got {tuple(h.shape)}")
+    for w, b in layers:
+        _dense(w, torch.float32, "w")
+        if w.ndim != 2 or w.shape[1] != hidden or (b is not None and (_dense(b, torch.float32, "b").numel() != w.shape[0])):
+            raise ValueError(f"{name}: w [n, {hidden}], b [n]")
+    if not 1 <= sum(w.shape[0] for w, _ in layers) <= HEADS_MAX_OUT:
+        raise ValueError(f"{name}: 1 to {HEADS_MAX_OUT} outputs")
+    return h.shape[0], hidden
+
+
+def linear_heads_narrow_forward(h: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """h [M, H] x w [n, H]^T + b [n] -> [M, n] (H = 64 or 128, n <= 8)."""
+    h, w, b = h.detach(), w.detach(), b.detach()
+    m, hidden = _heads_narrow_params("linear_heads_narrow_forward", h, (w, b))
+    n = w.shape[0]
+    out = torch.empty(m, n, dtype=torch.float32, device=h.device)
+    with _timed("linear_heads_narrow_forward", m):
+        _check(load().rl8_linear_heads_narrow_forward_f32(_ptr(h), m, hidden, _ptr(w), _ptr(b), n, _ptr(out), _stream()),
+               "rl8_linear_heads_narrow_forward_f32")
+    return out
+
+
+def linear_heads_narrow_forward_pair(h: torch.Tensor, w_a: torch.Tensor, b_a: torch.Tensor, w_b: torch.Tensor,
+                                     b_b: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Two layers on the same rows in one pass: (h x w_a^T + b_a [M, n_a], h x w_b^T + b_b [M, n_b])."""
+    h, w_a, b_a, w_b, b_b = (t.detach() for t in (h, w_a, b_a, w_b, b_b))
+    m, hidden = _heads_narrow_params("linear_heads_narrow_forward_pair", h, (w_a, b_a), (w_b, b_b))
+    n_a, n_b = w_a.shape[0], w_b.shape[0]
+    out_a = torch.empty(m, n_a, dtype=torch.float32, device=h.device)
+    out_b = torch.empty(m, n_b, dtype=torch.float32, device=h.device)
+    with _timed("linear_heads_narrow_forward", m):
+        _check(load().rl8_linear_heads_narrow_forward_pair_f32(_ptr(h), m, hidden, _ptr(w_a), _ptr(b_a), n_a, _ptr(out_a),
+                                                               _ptr(w_b), _ptr(b_b), n_b, _ptr(out_b), _stream()),
+               "rl8_linear_heads_narrow_forward_pair_f32")
+    return out_a, out_b
+
+
+def linear_heads_narrow_backward(h: torch.Tensor, dout: torch.Tensor, w: torch.Tensor, *,
+                                 need_dh: bool = True) -> tuple[None | torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (dh [M, H], dw [n, H], db [n]); ``need_dh=False``: dh is None and never written. Deterministic."""
+    h, dout, w = h.detach(), _dense(dout.detach(), torch.float32, "dout"), w.detach()
+    m, hidden = _heads_narrow_params("linear_heads_narrow_backward", h, (w, None))
+    n = w.shape[0]
+    if tuple(dout.shape) != (m, n):
+        raise ValueError("linear_heads_narrow_backward: dout must be [M, n]")
+    lib = load()
+    dh = torch.empty(m, hidden, dtype=torch.float32, device=h.device) if need_dh else None
+    ws = torch.empty(int(lib.rl8_linear_heads_narrow_workspace_bytes(m, hidden, n)) // 4, dtype=torch.float32,
+                     device=h.device)
+    grads = torch.empty(n * hidden + n, dtype=torch.float32, device=h.device)
+    with _timed("linear_heads_narrow_backward", m):
+        _check(lib.rl8_linear_heads_narrow_backward_f32(_ptr(h), _ptr(dout), m, hidden, _ptr(w), n, _ptr(dh), _ptr(ws),
+                                                        _ptr(grads), _stream()), "rl8_linear_heads_narrow_backward_f32")
+    return dh, grads[: n * hidden].view(n, hidden), grads[n * hidden:]
+
+
+def rollout_step_dummy_heads_narrow(
+    h: torch.Tensor, w_pol: torch.Tensor, b_pol: torch.Tensor, w_vf: torch.Tensor, b_vf: torch.Tensor,
+    noise: None | torch.Tensor, state: torch.Tensor, action_col: torch.Tensor, logp_col: torch.Tensor,
+    value_col: torch.Tensor, reward_col: torch.Tensor, obs_col_next: torch.Tensor, rdr_t: None | torch.Tensor,
+    rdr_t1: None | torch.Tensor, gamma: float, seed: int, step: int, env_offset: int = 0, deterministic: bool = False,
+) -> None:
+    """One rollout timestep of the discrete dummy env behind a narrow LSTM: two-way logits head and value head on
+    ``h`` [N, H] (as :func:`linear_heads_narrow_forward` forms them), then sampler + ``env.step`` + bookkeeping as
+    :func:`rollout_step_dummy` does them, in one launch."""
+    h, w_pol, b_pol, w_vf, b_vf = (t.detach() for t in (h, w_pol, b_pol, w_vf, b_vf))
+    n, hidden = _heads_narrow_params("rollout_step_dummy_heads_narrow", h, (w_pol, b_pol), (w_vf, b_vf))
+    if w_pol.shape[0] != 2 or w_vf.shape[0] != 1:
+        raise ValueError("rollout_step_dummy_heads_narrow: w_pol [2, H], w_vf [1, H]")
+    _dense(action_col, torch.int64, "action_col")
+    for name, t in (("state", state), ("logp_col", logp_col), ("value_col", value_col), ("reward_col", reward_col),
+                    ("obs_col_next", obs_col_next), ("noise", noise), ("rdr_t", rdr_t), ("rdr_t1", rdr_t1)):
+        if t is not None:
+            _dense(t, torch.float32, name)
+            if t.numel() != (2 * n if name == "noise" else n):
+                raise ValueError(f"rollout_step_dummy_heads_narrow: {name} has {t.numel()} elements for {n} envs")
+    if action_col.numel() != n:
+        raise ValueError("rollout_step_dummy_heads_narrow: action_col must hold one int64 per env")
+    with _timed("rollout_step_dummy_heads_narrow", n):
+        _check(load().rl8_rollout_step_dummy_heads_narrow_f32(
+            _ptr(h), hidden, _ptr(w_pol), _ptr(b_pol), _ptr(w_vf), _ptr(b_vf), _ptr(noise), _ptr(state), _ptr(action_col),
+            _ptr(logp_col), _ptr(value_col), _ptr(reward_col), _ptr(obs_col_next), _ptr(rdr_t), _ptr(rdr_t1),
+            float(gamma), n, int(seed), int(step), int(env_offset), int(deterministic), _stream()),
+            "rl8_rollout_step_dummy_heads_narrow_f32")

@@ -5,8 +5,8 @@ Interfaces follow the reference's ``src/rl8/models/_recurrent.py``:
 ``state_spec``, ``init_states``), ``DefaultContinuousRecurrentModel`` :169-256,
 ``DefaultDiscreteRecurrentModel`` :259-341. Module names match, so reference
 ``state_dict``s load unchanged. A one-layer LSTM of hidden width 256 (d_in <= 7) or
-64 / 128 (d_in <= 16) runs the fused HIP kernels (``nn/fused_lstm.py``); any other
-runs the module.
+64 / 128 (d_in <= 16) runs the fused HIP kernels (``nn/fused_lstm.py``), and so do
+the ``Linear`` heads on latents of those widths; any other runs the modules.
 
 """
 

@@ -15,7 +15,9 @@ non-fp32 inputs) and the caller runs the module itself. Two or more layers of
 width 64 / 128 without dropout have their own entry, ``lstm_stack_forward``:
 layer 0 on the narrow kernels, the layers above on the lstm_narrow_stack_*
 kernels (input projection over all row-steps, recurrent forward from it, input
-gradient for the layer below).
+gradient for the layer below). The ``Linear(64 | 128, n)`` heads on any of these
+run lstm_narrow_heads_kernels.hip, and a training pass through one narrow layer
+and heads of at most four outputs is one node (``_NarrowLSTMHeads``), as at 256.
 
 """
 
@@ -220,6 +222,35 @@ class _NarrowLSTM(torch.autograd.Function):
         return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None
 
 
+class _NarrowLSTMHeads(torch.autograd.Function):
+    """:class:`_NarrowLSTM` + output heads of a training pass as one node, as :class:`_FusedLSTMHeads` is at 256: the
+    heads' data gradient dL/dh_t = dOut x W (n <= 4) is formed inside the backward through time from the 16 bytes
+    per row-step it is made of, instead of being written as [B, L, H] by the heads' backward and read back."""
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, w_heads, b_heads):  # type: ignore[override]
+        hs, _, cn, gates, cs = hip.lstm_narrow_forward(x, h0, c0, w_ih, w_hh, b_ih, b_hh, save=True)
+        out = hip.linear_heads_narrow_forward(hs.view(-1, hs.shape[2]), w_heads, b_heads)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, h0, c0, w_hh, hs, gates, cs, w_heads)
+        ctx.mark_non_differentiable(cn)
+        return out, hs, cn
+
+    @staticmethod
+    def backward(ctx, dout, dhs, dcn):  # type: ignore[override]
+        x, h0, c0, w_hh, hs, gates, cs, w_heads = ctx.saved_tensors
+        flat = hs.view(-1, hs.shape[2])
+        dout = (torch.zeros(flat.shape[0], w_heads.shape[0], dtype=torch.float32, device=flat.device) if dout is None
+                else dout.contiguous().float())
+        if dhs is None:  # nothing but the heads reads the latents: the usual case
+            _, dw, db = hip.linear_heads_narrow_backward(flat, dout, w_heads, need_dh=False)
+            g = hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, None, heads=(dout, w_heads))
+        else:
+            dh, dw, db = hip.linear_heads_narrow_backward(flat, dout, w_heads)
+            g = hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, dh.view_as(hs) + dhs.float())
+        return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], dw, db
+
+
 _STACK_PARAMS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
 
 
@@ -338,6 +369,22 @@ class _FusedHeads(torch.autograd.Function):
         return dh, dw, db
 
 
+class _NarrowHeads(torch.autograd.Function):
+    """:class:`_FusedHeads` for latents of width 64 / 128 (lstm_narrow_heads_kernels.hip)."""
+
+    @staticmethod
+    def forward(ctx, h, w, b):  # type: ignore[override]
+        out = hip.linear_heads_narrow_forward(h, w, b)
+        ctx.save_for_backward(h, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):  # type: ignore[override]
+        h, w = ctx.saved_tensors
+        dh, dw, db = hip.linear_heads_narrow_backward(h, dout.contiguous().float(), w, need_dh=ctx.needs_input_grad[0])
+        return dh, dw, db
+
+
 class _FusedLSTMHeads(torch.autograd.Function):
     """LSTM + output heads of a training pass as one node: the heads' data gradient dL/dh_t = dOut x W (a rank-n
     product, n <= 4) is formed inside the backward-through-time kernel from the 16 bytes per row-step it is made
@@ -372,18 +419,43 @@ class _FusedLSTMHeads(torch.autograd.Function):
         return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], dw, db, None, None
 
 
-def _heads_eligible(heads: list[nn.Linear], max_out: int) -> bool:
-    if any(h.in_features != hip.LSTM_HIDDEN or h.bias is None or h.weight.dtype != torch.float32 for h in heads):
+def _heads_eligible(heads: list[nn.Linear], max_out: int, hidden: int = hip.LSTM_HIDDEN) -> bool:
+    if any(h.in_features != hidden or h.bias is None or h.weight.dtype != torch.float32 for h in heads):
         return False
     return sum(h.out_features for h in heads) <= max_out
+
+
+def _stacked(heads: list[nn.Linear]) -> tuple[torch.Tensor, torch.Tensor, list[int]]:
+    """The heads' weights [sum n_i, H] and biases [sum n_i] stacked, and the n_i."""
+    w = torch.cat([h.weight for h in heads], 0) if len(heads) > 1 else heads[0].weight
+    b = torch.cat([h.bias for h in heads], 0) if len(heads) > 1 else heads[0].bias
+    return w, b, [h.out_features for h in heads]
+
+
+def _narrow_lstm_heads_forward(lstm: nn.LSTM, heads: list[nn.Linear], x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
+    """:func:`lstm_heads_forward` for a one-layer LSTM of width 64 / 128 (``x`` already found ``_narrow_eligible``)."""
+    if not (FUSE_HEADS and _heads_eligible(heads, hip.ROWS_BACKWARD_HEADS, lstm.hidden_size)
+            and any(p.requires_grad for p in lstm.parameters())):
+        return None
+    w, b, widths = _stacked(heads)
+    out, hs, cn = _NarrowLSTMHeads.apply(
+        x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
+        lstm.bias_ih_l0, lstm.bias_hh_l0, w, b,
+    )
+    return list(out.split(widths, dim=1)), hs, hs[:, -1], cn
 
 
 def lstm_heads_forward(lstm: nn.LSTM, heads: list[nn.Linear], x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
     """A training pass through ``lstm`` and ``Linear(256, n_i)`` heads on its outputs as one autograd node
     (:class:`_FusedLSTMHeads`): ``([head_i(hs) as [B * L, n_i]], hs [B, L, 256], h_n, c_n)``, or ``None`` when this
     combination is not eligible (no gradient wanted, more than four head outputs, a plan that does not fuse the
-    heads): the caller then runs :func:`lstm_forward` and :func:`heads_forward`."""
-    if not (torch.is_grad_enabled() and _eligible(lstm, x)):
+    heads): the caller then runs :func:`lstm_forward` and :func:`heads_forward`. A one-layer LSTM of width 64 / 128
+    with ``Linear(H, n_i)`` heads has its own node (:class:`_NarrowLSTMHeads`), decided before any width-256 rule."""
+    if not torch.is_grad_enabled():
+        return None
+    if _narrow_eligible(lstm, x):
+        return _narrow_lstm_heads_forward(lstm, heads, x, h0, c0)
+    if not _eligible(lstm, x):
         return None
     plan = _plan(lstm.input_size, x.shape[0])
     if not (plan.fuse_heads and _heads_eligible(heads, hip.ROWS_BACKWARD_HEADS)
@@ -400,18 +472,18 @@ def lstm_heads_forward(lstm: nn.LSTM, heads: list[nn.Linear], x: torch.Tensor, h
 
 
 def heads_forward(heads: list[nn.Linear], latents: torch.Tensor) -> None | list[torch.Tensor]:
-    """``[head(latents) for head in heads]`` for ``Linear(256, n_i)`` heads on
-    ``latents`` [..., 256] in one pass over ``latents`` (and one for the backward),
-    or ``None`` when not eligible."""
-    if not ENABLED or not latents.is_cuda or latents.dtype != torch.float32 or latents.shape[-1] != hip.LSTM_HIDDEN:
+    """``[head(latents) for head in heads]`` for ``Linear(H, n_i)`` heads on
+    ``latents`` [..., H], H = 256, 64 or 128, in one pass over ``latents`` (and one
+    for the backward), or ``None`` when not eligible."""
+    hidden = latents.shape[-1]
+    narrow = hidden in hip.LSTM_NARROW_HIDDEN
+    if not ENABLED or not latents.is_cuda or latents.dtype != torch.float32 or not (narrow or hidden == hip.LSTM_HIDDEN):
         return None
-    if any(h.in_features != hip.LSTM_HIDDEN or h.bias is None for h in heads):
+    if any(h.in_features != hidden or h.bias is None for h in heads):
         return None
-    widths = [h.out_features for h in heads]
-    if sum(widths) > 8:
+    w, b, widths = _stacked(heads)
+    if sum(widths) > hip.HEADS_MAX_OUT:
         return None
-    w = torch.cat([h.weight for h in heads], 0) if len(heads) > 1 else heads[0].weight
-    b = torch.cat([h.bias for h in heads], 0) if len(heads) > 1 else heads[0].bias
-    flat = latents.reshape(-1, hip.LSTM_HIDDEN)
-    out = _FusedHeads.apply(flat.contiguous(), w, b)
+    flat = latents.reshape(-1, hidden)
+    out = (_NarrowHeads if narrow else _FusedHeads).apply(flat.contiguous(), w, b)
     return list(out.split(widths, dim=1))

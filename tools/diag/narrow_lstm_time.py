@@ -1,6 +1,7 @@
 """Time the narrow LSTMs (hidden width 64 / 128, lstm_narrow_kernels.hip) against the same LSTMs on the eager module.
 
     python tools/diag/narrow_lstm_time.py [--reps 5] [--no-algo] [--layers N] [--fused-only] [--only train|rollout]
+                                          [--heads]
 
 For each (H, d_in) at a rollout step (65536 sequences x L = 1) and a training pass (2^19 sequences x L = 4): the fused
 forward, the fused forward + backward (through autograd, as a model runs it), and both again with
@@ -19,6 +20,11 @@ layer's algorithmic bytes per row-step: forward 2H (the lower layer's h_t read, 
 backward as above with an H-wide x (7H + 4H + 6H) plus dx (dz read, dx written: 5H).  ``--fused-only`` leaves the
 eager runs and the algorithm out and ``--only`` keeps one of the two shapes: for a kernel trace
 (``rocprofv3 --kernel-trace --stats -- python tools/diag/narrow_lstm_time.py --layers 2 --fused-only --only train``).
+
+``--heads`` times the default discrete and continuous recurrent MODELS instead of the bare LSTM -- LSTM (``--layers``)
+plus output heads, through ``model(batch, states)`` alone, so the same file runs on any commit that has the models:
+forward (no grad) and forward + backward at the two shapes, median [min-max]; then collect() + step() for hidden 64 and
+128 at 65536 and 8192 environments x 256 steps on DiscreteDummyEnv, median [min-max] of wall time.
 """
 import argparse
 import os
@@ -38,6 +44,7 @@ p.add_argument("--no-algo", action="store_true")
 p.add_argument("--layers", type=int, default=1)
 p.add_argument("--fused-only", action="store_true")
 p.add_argument("--only", choices=("train", "rollout"))
+p.add_argument("--heads", action="store_true")
 args = p.parse_args()
 dev = torch.device("cuda:0")
 SHAPES = [s for name, s in (("rollout", (65536, 1)), ("train", (1 << 19, 4))) if args.only in (None, name)]
@@ -92,6 +99,90 @@ def measure(lstm, x, h0, c0, enabled):
 def cell(t):
     return f"{t[0]:.0f} [{t[1]:.0f}-{t[2]:.0f}]" if t else "-"
 
+
+def spread(ts):
+    ts = sorted(ts)
+    return f"{ts[len(ts) // 2]:.0f} [{ts[0]:.0f}-{ts[-1]:.0f}]"
+
+
+def times(fn):
+    """Every repetition's time in us (after one warm-up call)."""
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(args.reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b) * 1e3)
+    return ts
+
+
+def heads_mode():
+    from rl8_amd import RecurrentAlgorithmConfig
+    from rl8_amd.data import DataKeys
+    from rl8_amd.env import ContinuousDummyEnv, DiscreteDummyEnv
+    from rl8_amd.models_recurrent import DefaultContinuousRecurrentModel, DefaultDiscreteRecurrentModel
+    from rl8_amd.tensordict import TensorDict
+
+    n = args.layers
+    print(f"default recurrent models, layers = {n}; times in us: median [min-max] of {args.reps} repetitions")
+    print("| model | H | B x L | forward | forward + backward |")
+    print("|---|---|---|---|---|")
+    for name, model_cls, env_cls in (("discrete", DefaultDiscreteRecurrentModel, DiscreteDummyEnv),
+                                     ("continuous", DefaultContinuousRecurrentModel, ContinuousDummyEnv)):
+        env = env_cls(4, 8, device=str(dev))
+        for hidden in (64, 128):
+            torch.manual_seed(0)
+            model = model_cls(env.observation_spec, env.action_spec, hidden_size=hidden, num_layers=n).to(dev)
+            for b, l in SHAPES:
+                batch = TensorDict({DataKeys.OBS: torch.randn(b, l, 1, device=dev)}, batch_size=[b, l])
+                # (only [:, 0] of the states is read: one step's worth, expanded over l)
+                states = TensorDict(
+                    {DataKeys.HIDDEN_STATES: (torch.randn(b, 1, n, hidden, device=dev) * 0.5).expand(b, l, n, hidden),
+                     DataKeys.CELL_STATES: torch.randn(b, 1, n, hidden, device=dev).expand(b, l, n, hidden)},
+                    batch_size=[b, l])
+
+                def forward():
+                    with torch.no_grad():
+                        model(batch, states)
+
+                def train():
+                    model.zero_grad(set_to_none=True)
+                    feats, _ = model(batch, states)
+                    (sum(v.sum() for v in feats.values()) + model.value_function().sum()).backward()
+
+                print(f"| {name} | {hidden} | {b} x {l} | {spread(times(forward))} | {spread(times(train))} |", flush=True)
+                del batch, states
+            del model
+    if args.no_algo:
+        return
+    for hidden in (64, 128):
+        for envs in (65536, 8192):
+            torch.manual_seed(0)
+            algo = RecurrentAlgorithmConfig(num_envs=envs, horizon=256,
+                                            model_config={"hidden_size": hidden, "num_layers": n}).build(DiscreteDummyEnv)
+            algo.collect()
+            algo.step()  # (warm-up)
+            ts = []
+            for _ in range(args.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                algo.collect()
+                algo.step()
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts.sort()
+            print(f"collect()+step() hidden {hidden}, {n} layer(s), {envs} envs x 256: "
+                  f"{ts[len(ts) // 2]:.1f} ms [{ts[0]:.1f}-{ts[-1]:.1f}]", flush=True)
+            del algo
+
+
+if args.heads:
+    heads_mode()
+    sys.exit(0)
 
 if args.layers == 1:
     print("| H | d_in | B x L | fused fwd us | eager fwd us | fused fwd+bwd us | eager fwd+bwd us | fwd GB/s | fwd+bwd GB/s |")
