@@ -18,13 +18,15 @@ sequence-major once per ``step()`` in buffer order and every SGD iteration reads
 that copy (the reference draws ``randperm`` and gathers per iteration,
 ``src/rl8/_utils.py:211-225``; ``bench.py --recurrent --minibatches 4`` times the
 shuffled path). A training pass through the default models is ONE autograd node
-(``nn/fused_lstm.py:_FusedLSTMHeads``, ``_NarrowLSTMHeads`` at hidden width 64 / 128):
-the heads' data gradient is formed inside the backward-through-time kernel.
+(``nn/fused_lstm.py:lstm_heads_forward``: ``_FusedLSTMHeads`` at hidden width 256,
+``_NarrowLSTMHeads`` at 64 / 128): the heads' data gradient is formed inside the
+backward-through-time kernel.
 
 """
 
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass
 from typing import Any
 
@@ -48,11 +50,13 @@ from ..specs import Composite
 from ..tensordict import TensorDict
 from ._feedforward import Algorithm, AlgorithmConfig, _collect_stats_from_raw
 
-#: Rows (sequences x seq_len) pushed through the LSTM per forward/backward pass.
 #: Rows (sequences x steps) of one forward / backward pass through the LSTM;
 #: larger minibatches accumulate over several passes. 2^21 rows of the default
 #: 256-wide LSTM keep the pass's activations around 20 GB.
 RECURRENT_MAX_ROWS_PER_PASS = 1 << 21
+
+
+_NO_TIMER = contextlib.nullcontext()
 
 
 class _LeanRollout:
@@ -64,9 +68,11 @@ class _LeanRollout:
     ``policy.sample()`` + ``_fused_step`` (tests/test_algorithm_gpu.py:
     ``test_recurrent_lean_and_plumbed_rollouts_agree``); what goes is ~150 us of
     tensordict / autograd-function / ``torch.cat`` host work per timestep, which at
-    8192 environments per GPU (BASELINE configs[4]) was twice the kernels' time. A one-layer LSTM of width 64 / 128
-    takes the narrow route (``_step_narrow``: ``rl8_lstm_narrow_forward_f32`` with l = 1, then
-    ``rl8_rollout_step_dummy_heads_narrow_f32``), decided before any width-256 rule: no packs, no planes, no plan."""
+    8192 environments per GPU (BASELINE configs[4]) was twice the kernels' time.
+    ``step`` is one of three LSTM-step launches -- the plane step kernel or the fp32
+    forward with l = 1 at width 256 (``fused_lstm._plan``), the narrow forward with
+    l = 1 on the weights as they are at 64 / 128 (no packs, no planes, no plan) --
+    and then ``_heads_and_env``, the same at every width."""
 
     TIMER_EVERY = 16  # with hip.timer enabled, only every 16th timestep is bracketed by events
 
@@ -82,21 +88,28 @@ class _LeanRollout:
         dev = tm[DataKeys.OBS].device
         lstm = model.lstm
         self.hidden = int(lstm.hidden_size)
-        # width 64 / 128: the narrow forward kernel with l = 1 on the weights as they are -- no packs, no planes, no plan
-        self.narrow = self.hidden in hip.LSTM_NARROW_HIDDEN
+        self.narrow = self.hidden in hip.LSTM_NARROW_HIDDEN  # (``available`` has said "narrow" or "256")
+        self.split = not self.narrow and fused_lstm._plan(lstm.input_size, n).forward_planes
+        # what the LSTM step reads, kept alive on self (parameters are leaf tensors: .detach() shares storage)
         if self.narrow:
-            self.split, self.packed, self.wb = False, None, None
-            self.lstm_params = [p.detach().contiguous() for p in (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0,
-                                                                  lstm.bias_hh_l0)]
+            self.lstm_weights = [p.detach().contiguous() for p in (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0,
+                                                                   lstm.bias_hh_l0)]
+        elif self.split:  # bf16-plane step kernel: W_hh planes, [w_ih | bias] rows, planes of h_{t-1}
+            self.lstm_weights = list(fused_lstm._packs(lstm, "split"))
         else:
-            self.split = fused_lstm._plan(lstm.input_size, n).forward_planes
-            if self.split:  # bf16-plane step kernel: W_hh planes, [w_ih | bias] rows, planes of h_{t-1}
-                self.packed, self.wb = fused_lstm._packs(lstm, "split")
-            else:
-                self.packed, self.wb = fused_lstm._packs(lstm, "step"), None
-        # parameters are leaf tensors: .detach() shares storage (kept alive on self)
+            self.lstm_weights = [fused_lstm._packs(lstm, "step")]
         self.params = [p.detach().contiguous() for p in (model.feature_head.weight, model.feature_head.bias,
                                                          model.vf_head.weight, model.vf_head.bias)]
+        # the heads' entries and the names they are timed under; below 256 they take the width after hs (and n)
+        if self.narrow:
+            self.width: tuple = (self.hidden,)
+            self.sampler_heads = ("rl8_rollout_step_dummy_heads_narrow_f32", "rollout_step_dummy_heads_narrow")
+            self.heads = ("rl8_linear_heads_narrow_forward_pair_f32", "rl8_linear_heads_narrow_forward_f32",
+                          "linear_heads_narrow_forward")
+        else:
+            self.width = ()
+            self.sampler_heads = ("rl8_rollout_step_dummy_heads_f32", "rollout_step_dummy")
+            self.heads = ("rl8_linear_heads_forward_pair_f32", "rl8_linear_heads_forward_f32", "linear_heads_forward")
         cache = algo.__dict__.setdefault("_lean_scratch", {})
         key = (n, self.k, str(dev), self.hidden)
         if cache.get("key") != key:
@@ -117,14 +130,9 @@ class _LeanRollout:
         self.gamma = float(torch.tensor(algo.hparams.gamma, dtype=torch.float32))
         self.seed, self.env_offset = algo.noise.seed, algo.env.env_offset
         self.deterministic = int(deterministic)
-        self.ptrs = [t.data_ptr() if t is not None else None
-                     for t in (self.packed, self.hs, self.logits, self.value, *self.params)]
-        if self.narrow:
-            self.lstm_ptrs = [t.data_ptr() for t in self.lstm_params]
-            self.split_ptrs, self.planes_half = (None, None), 0
-        else:
-            self.split_ptrs = (self.planes.data_ptr(), self.wb.data_ptr() if self.wb is not None else None)
-            self.planes_half = self.planes.numel() // 2
+        self.lstm_ptrs = [t.data_ptr() for t in self.lstm_weights]
+        self.ptrs = [t.data_ptr() for t in (self.hs, self.logits, self.value, *self.params)]
+        self.planes_ptr, self.planes_half = (self.planes.data_ptr(), self.planes.numel() // 2) if self.split else (None, 0)
         self.planes_of = -1   # timestep whose hidden state the planes buffer (t & 1) holds (-1: none)
         # two-way categorical + value head: evaluated inside the timestep's last kernel (switched off: two launches)
         self.fuse_heads = self.k == 2 and fused_lstm._rollout_fuse_heads()
@@ -140,28 +148,26 @@ class _LeanRollout:
             return False
         if algo.policy.distribution_cls is not Categorical or model.action_spec.shape[0] != 1:
             return False
-        lstm = model.lstm
-        obs = algo._tm[DataKeys.OBS]
-        if not (fused_lstm.ENABLED and lstm.num_layers == 1 and lstm.bias and lstm.proj_size == 0
-                and not lstm.bidirectional):
-            return False
-        if lstm.hidden_size in hip.LSTM_NARROW_HIDDEN:  # (decided before any width-256 rule, as in lstm_forward)
-            kernels = lstm.batch_first and hip.lstm_narrow_supports(lstm.hidden_size, lstm.input_size)
-        else:
-            kernels = lstm.hidden_size == hip.LSTM_HIDDEN and hip.lstm_supports(lstm.input_size)
-        return bool(kernels and obs.dtype == torch.float32 and model.vf_head.bias is not None
+        # (the buffer may live on the CPU in tests of this rule: the module's family and the dtypes, not the device)
+        return bool(fused_lstm._family(model.lstm) in ("256", "narrow")
+                    and algo._tm[DataKeys.OBS].dtype == torch.float32 and model.vf_head.bias is not None
                     and all(p.dtype == torch.float32 for p in model.parameters()))
 
     def step(self, t: int, noise: None | torch.Tensor, step_id: int) -> None:
-        lib, n, stream = self.lib, self.n, hip._stream()
-        packed, hs, logits, value, w_pol, b_pol, w_vf, b_vf = self.ptrs
+        lib, n, stream, H = self.lib, self.n, hip._stream(), self.hidden
         at = lambda col, i: col[0] + i * col[1]  # noqa: E731
         timed = hip.timer.enabled and t % self.TIMER_EVERY == 0
+        hs = self.ptrs[0]
         if self.narrow:
-            return self._step_narrow(t, noise, step_id, timed)
-        if self.split:
-            planes, wb = self.split_ptrs
-            H = hip.LSTM_HIDDEN
+            # h_t and c_t straight into the state buffers' next column, a dense [N][H] slab for one layer
+            w_ih, w_hh, b_ih, b_hh = self.lstm_ptrs
+            with hip._timed("lstm_narrow_forward", n) if timed else _NO_TIMER:
+                hip._check(lib.rl8_lstm_narrow_forward_f32(at(self.obs, t), n, 1, self.d_in, at(self.h, t), at(self.c, t), w_ih,
+                                                           w_hh, b_ih, b_hh, H, hs, at(self.h, t + 1), at(self.c, t + 1), None,
+                                                           None, stream), "rl8_lstm_narrow_forward_f32")
+        elif self.split:
+            packed, wb = self.lstm_ptrs
+            planes = self.planes_ptr
             p_in, p_out = planes + (t & 1) * self.planes_half, planes + ((t + 1) & 1) * self.planes_half
             if self.planes_of != t:
                 # the first timestep, or one whose states were just re-initialised: planes of h_t
@@ -174,80 +180,38 @@ class _LeanRollout:
             self.planes_of = t + 1
             hs = at(self.h, t + 1)  # the heads read h_t where the buffer keeps it
         else:
+            (packed,) = self.lstm_ptrs
             with hip._timed("lstm_forward", n) if timed else _NO_TIMER:
                 hip._check(lib.rl8_lstm_forward_f32(at(self.obs, t), n, 1, self.d_in, at(self.h, t), at(self.c, t), packed,
                                                     hs, at(self.h, t + 1), at(self.c, t + 1), None, None, stream),
                            "rl8_lstm_forward_f32")
-        if self.fuse_heads:
-            # the two heads inside the sampler + env.step + bookkeeping kernel: one launch instead of two
-            with hip._timed("rollout_step_dummy", n) if timed else _NO_TIMER:
-                hip._check(lib.rl8_rollout_step_dummy_heads_f32(
-                    hs, w_pol, b_pol, w_vf, b_vf, noise.data_ptr() if noise is not None else None, self.state_ptr,
-                    at(self.act, t), at(self.logp, t), at(self.val, t), at(self.rew, t), at(self.obs, t + 1),
-                    at(self.rdr, t) if self.rdr else None, at(self.rdr, t + 1) if self.rdr else None, self.gamma, n,
-                    self.seed, step_id, self.env_offset, self.deterministic, stream), "rl8_rollout_step_dummy_heads_f32")
-            return
-        with hip._timed("linear_heads_forward", n) if timed else _NO_TIMER:
-            if self.k + 1 <= hip.HEADS_MAX_OUT:  # both heads in one pass over h_t
-                hip._check(lib.rl8_linear_heads_forward_pair_f32(hs, n, w_pol, b_pol, self.k, logits, w_vf, b_vf, 1, value,
-                                                                 stream), "rl8_linear_heads_forward_pair_f32")
-            else:
-                hip._check(lib.rl8_linear_heads_forward_f32(hs, n, w_pol, b_pol, self.k, logits, stream),
-                           "rl8_linear_heads_forward_f32")
-                hip._check(lib.rl8_linear_heads_forward_f32(hs, n, w_vf, b_vf, 1, value, stream),
-                           "rl8_linear_heads_forward_f32")
-        with hip._timed("rollout_step_dummy", n) if timed else _NO_TIMER:
-            hip._check(lib.rl8_rollout_step_dummy_f32(
-                1, 0, logits, None, value, noise.data_ptr() if noise is not None else None, self.state_ptr,
-                at(self.act, t), at(self.logp, t), at(self.val, t), at(self.rew, t), at(self.obs, t + 1),
-                at(self.rdr, t) if self.rdr else None, at(self.rdr, t + 1) if self.rdr else None, self.gamma, n,
-                self.seed, step_id, self.env_offset, self.deterministic, stream), "rl8_rollout_step_dummy_f32")
+        self._heads_and_env(t, hs, noise, step_id, timed, stream)
 
-
-    def _step_narrow(self, t: int, noise: None | torch.Tensor, step_id: int, timed: bool) -> None:
-        """One timestep behind an LSTM of width 64 / 128: the narrow forward with l = 1 (h_t and c_t straight into the
-        state buffers' next column, which is a dense [N][H] slab for one layer), then the two heads inside the
-        sampler + env.step + bookkeeping kernel, or the pair form and that kernel."""
-        lib, n, stream, H = self.lib, self.n, hip._stream(), self.hidden
-        _, hs, logits, value, w_pol, b_pol, w_vf, b_vf = self.ptrs
-        w_ih, w_hh, b_ih, b_hh = self.lstm_ptrs
+    def _heads_and_env(self, t: int, hs: int, noise: None | torch.Tensor, step_id: int, timed: bool, stream) -> None:
+        """The rest of a timestep, from ``h_t`` at ``hs``: the two heads inside the sampler + env.step + bookkeeping
+        kernel (one launch instead of two), or both heads in one pass over ``h_t`` (else one launch each) and then
+        that kernel on their outputs."""
+        lib, n, width = self.lib, self.n, self.width
+        _, logits, value, w_pol, b_pol, w_vf, b_vf = self.ptrs
         at = lambda col, i: col[0] + i * col[1]  # noqa: E731
-        with hip._timed("lstm_narrow_forward", n) if timed else _NO_TIMER:
-            hip._check(lib.rl8_lstm_narrow_forward_f32(at(self.obs, t), n, 1, self.d_in, at(self.h, t), at(self.c, t), w_ih,
-                                                       w_hh, b_ih, b_hh, H, hs, at(self.h, t + 1), at(self.c, t + 1), None,
-                                                       None, stream), "rl8_lstm_narrow_forward_f32")
-        tail = (noise.data_ptr() if noise is not None else None, self.state_ptr, at(self.act, t), at(self.logp, t),
-                at(self.val, t), at(self.rew, t), at(self.obs, t + 1), at(self.rdr, t) if self.rdr else None,
-                at(self.rdr, t + 1) if self.rdr else None, self.gamma, n, self.seed, step_id, self.env_offset,
-                self.deterministic, stream)
+        env = (noise.data_ptr() if noise is not None else None, self.state_ptr, at(self.act, t), at(self.logp, t),
+               at(self.val, t), at(self.rew, t), at(self.obs, t + 1), at(self.rdr, t) if self.rdr else None,
+               at(self.rdr, t + 1) if self.rdr else None, self.gamma, n, self.seed, step_id, self.env_offset,
+               self.deterministic, stream)
         if self.fuse_heads:
-            with hip._timed("rollout_step_dummy_heads_narrow", n) if timed else _NO_TIMER:
-                hip._check(lib.rl8_rollout_step_dummy_heads_narrow_f32(hs, H, w_pol, b_pol, w_vf, b_vf, *tail),
-                           "rl8_rollout_step_dummy_heads_narrow_f32")
+            entry, name = self.sampler_heads
+            with hip._timed(name, n) if timed else _NO_TIMER:
+                hip._check(getattr(lib, entry)(hs, *width, w_pol, b_pol, w_vf, b_vf, *env), entry)
             return
-        with hip._timed("linear_heads_narrow_forward", n) if timed else _NO_TIMER:
-            if self.k + 1 <= hip.HEADS_MAX_OUT:  # both heads in one pass over h_t
-                hip._check(lib.rl8_linear_heads_narrow_forward_pair_f32(hs, n, H, w_pol, b_pol, self.k, logits, w_vf, b_vf,
-                                                                        1, value, stream),
-                           "rl8_linear_heads_narrow_forward_pair_f32")
+        pair, single, name = self.heads
+        with hip._timed(name, n) if timed else _NO_TIMER:
+            if self.k + 1 <= hip.HEADS_MAX_OUT:
+                hip._check(getattr(lib, pair)(hs, n, *width, w_pol, b_pol, self.k, logits, w_vf, b_vf, 1, value, stream), pair)
             else:
-                hip._check(lib.rl8_linear_heads_narrow_forward_f32(hs, n, H, w_pol, b_pol, self.k, logits, stream),
-                           "rl8_linear_heads_narrow_forward_f32")
-                hip._check(lib.rl8_linear_heads_narrow_forward_f32(hs, n, H, w_vf, b_vf, 1, value, stream),
-                           "rl8_linear_heads_narrow_forward_f32")
+                hip._check(getattr(lib, single)(hs, n, *width, w_pol, b_pol, self.k, logits, stream), single)
+                hip._check(getattr(lib, single)(hs, n, *width, w_vf, b_vf, 1, value, stream), single)
         with hip._timed("rollout_step_dummy", n) if timed else _NO_TIMER:
-            hip._check(lib.rl8_rollout_step_dummy_f32(1, 0, logits, None, value, *tail), "rl8_rollout_step_dummy_f32")
-
-
-class _NoTimer:
-    def __enter__(self) -> None:
-        return None
-
-    def __exit__(self, *exc: Any) -> None:
-        return None
-
-
-_NO_TIMER = _NoTimer()
+            hip._check(lib.rl8_rollout_step_dummy_f32(1, 0, logits, None, value, *env), "rl8_rollout_step_dummy_f32")
 
 
 @dataclass

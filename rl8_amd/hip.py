@@ -322,6 +322,14 @@ def _dense(t: torch.Tensor, dtype: torch.dtype, what: str) -> torch.Tensor:
     return t
 
 
+def _shaped(t: torch.Tensor, shape: tuple, what: str, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``t`` when it is a dense ``dtype`` tensor of exactly ``shape``, else an error naming it."""
+    _dense(t, dtype, what)
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{what} must have shape {shape}, got {tuple(t.shape)}")
+    return t
+
+
 _scratch: dict[tuple[int, int], torch.Tensor] = {}
 
 
@@ -895,9 +903,7 @@ def mlp_tower_forward(
     n_out = w3.shape[0]
     for name, t, shape in (("w1", w1, (MLP_HIDDEN, d_in)), ("b1", b1, (MLP_HIDDEN,)), ("b2", b2, (MLP_HIDDEN,)),
                            ("w3", w3, (n_out, MLP_HIDDEN)), ("b3", b3, (n_out,))):
-        _dense(t.detach(), torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        _shaped(t, shape, name)
     if w2_packed.numel() != MLP_HIDDEN * MLP_HIDDEN:
         raise ValueError("w2_packed must come from mlp_pack_w2")
     out = torch.empty(m, n_out, dtype=torch.float32, device=x.device)
@@ -976,9 +982,7 @@ def mlp_tower_forward_split(
     n_out = w3.shape[0]
     for name, t, shape in (("w1", w1, (MLP_HIDDEN, d_in)), ("b1", b1, (MLP_HIDDEN,)), ("b2", b2, (MLP_HIDDEN,)),
                            ("w3", w3, (n_out, MLP_HIDDEN)), ("b3", b3, (n_out,))):
-        _dense(t.detach(), torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        _shaped(t, shape, name)
     lib = load()
     if w2_split.dtype == torch.uint8 and w2_split.numel() == int(lib.rl8_mlp_f16_packed_bytes()):
         fn, fn_name = lib.rl8_mlp_tower_forward_f16_f32, "rl8_mlp_tower_forward_f16_f32"  # fp16 two-plane pack
@@ -987,9 +991,7 @@ def mlp_tower_forward_split(
     for name, t, dtype, shape in (("out", out, torch.float32, (m, n_out)), ("h2_out", h2_out, torch.float32, (m, MLP_HIDDEN)),
                                   ("gate_out", gate_out, torch.int32, (m, 8))):
         if t is not None:
-            _dense(t, dtype, name)
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+            _shaped(t, shape, name, dtype)
     if out is None:
         out = torch.empty(m, n_out, dtype=torch.float32, device=x.device)
     if save and not save_h2:
@@ -1237,11 +1239,8 @@ def _narrow_params(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torc
     shapes = (("w1", w1, (hidden, d_in)), ("b1", b1, (hidden,)), ("w2", w2, (hidden, hidden)), ("b2", b2, (hidden,)),
               ("w3", w3, (n_out, hidden)), ("b3", b3, (n_out,)))
     for name, t, shape in shapes:
-        if t is None:
-            continue
-        _dense(t, torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        if t is not None:
+            _shaped(t, shape, name)
     if m < 1 or not mlp_narrow_supports(hidden, d_in, n_out):
         raise ValueError(f"no narrow tower kernel for m={m}, hidden={hidden}, d_in={d_in}, n_out={n_out}")
     return m, d_in, hidden, n_out
@@ -1266,9 +1265,7 @@ def mlp_narrow_backward(x: torch.Tensor, dout: torch.Tensor, w1: torch.Tensor, b
     [M, n_out]: the forward recomputed from x, partial slabs per workgroup summed in a fixed order (deterministic)."""
     x, dout, w1, b1, w2, b2, w3 = (t.detach() for t in (x, dout, w1, b1, w2, b2, w3))
     m, d_in, hidden, n_out = _narrow_params(x, w1, b1, w2, b2, w3, None)
-    _dense(dout, torch.float32, "dout")
-    if tuple(dout.shape) != (m, n_out):
-        raise ValueError(f"dout must have shape {(m, n_out)}, got {tuple(dout.shape)}")
+    _shaped(dout, (m, n_out), "dout")
     lib = load()
     ws = torch.empty(int(lib.rl8_mlp_narrow_workspace_bytes(m, hidden, d_in, n_out)) // 4, dtype=torch.float32,
                      device=x.device)
@@ -1345,16 +1342,53 @@ def lstm_supports(d_in: int) -> bool:
     return bool(load().rl8_lstm_supports(int(d_in)))
 
 
+def _lstm_pack_params(w_ih: torch.Tensor, w_hh: torch.Tensor, b_ih: torch.Tensor, b_hh: torch.Tensor) -> int:
+    """d_in after the dtype / contiguity / shape checks of a width-256 ``torch.nn.LSTM`` layer's parameters."""
+    d_in = w_ih.shape[1]
+    for name, t, shape in (("w_ih", w_ih, (4 * LSTM_HIDDEN, d_in)), ("w_hh", w_hh, (4 * LSTM_HIDDEN, LSTM_HIDDEN)),
+                           ("b_ih", b_ih, (4 * LSTM_HIDDEN,)), ("b_hh", b_hh, (4 * LSTM_HIDDEN,))):
+        _shaped(t, shape, name)
+    return d_in
+
+
+def _lstm_states_256(h0: torch.Tensor, c0: torch.Tensor, b: int) -> None:
+    """The dtype / contiguity / shape checks of the width-256 forwards' initial states."""
+    for name, t in (("h0", h0), ("c0", c0)):
+        _dense(t, torch.float32, name)
+        if tuple(t.shape) != (b, LSTM_HIDDEN):
+            raise ValueError(f"{name} must be [{b}, {LSTM_HIDDEN}], got {tuple(t.shape)}")
+
+
+def _lstm_outputs(b: int, l: int, hidden: int, device: torch.device, save: bool,
+                  state_out: None | tuple[torch.Tensor, torch.Tensor] = None):
+    """(hs [B, L, H], hn, cn [B, H], gates [B, L, 4, H], cs [B, L, H]) for a forward to write: ``gates`` and ``cs``
+    only with ``save``; ``hn`` / ``cn`` are the caller's ``state_out`` (checked) where given."""
+    def new(*shape: int) -> torch.Tensor:
+        return torch.empty(*shape, dtype=torch.float32, device=device)
+
+    hs = new(b, l, hidden)
+    if state_out is None:
+        hn, cn = new(b, hidden), new(b, hidden)
+    else:
+        hn, cn = (_shaped(t, (b, hidden), name) for name, t in zip(("hn", "cn"), state_out))
+    return hs, hn, cn, new(b, l, 4, hidden) if save else None, new(b, l, hidden) if save else None
+
+
+def _heads_padded(dout: torch.Tensor, w: torch.Tensor, n: int, rows: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(dout4 [rows, 4], w4 [4, H]) for a backward through time with the heads inside: four floats per row-step and
+    four weight rows (one 16-byte piece per sequence and head-row segment), zero-padded from ``n``."""
+    dout4 = torch.zeros(rows, ROWS_BACKWARD_HEADS, dtype=torch.float32, device=w.device)
+    dout4[:, :n] = dout.detach().reshape(rows, n)
+    w4 = torch.zeros(ROWS_BACKWARD_HEADS, w.shape[1], dtype=torch.float32, device=w.device)
+    w4[:n] = w.detach()
+    return dout4, w4
+
+
 def lstm_pack(w_ih: torch.Tensor, w_hh: torch.Tensor, b_ih: torch.Tensor, b_hh: torch.Tensor) -> torch.Tensor:
     """torch.nn.LSTM parameters (``weight_ih_l0`` [1024, d], ``weight_hh_l0``
     [1024, 256], ``bias_ih_l0``, ``bias_hh_l0`` [1024]) -> forward weights in MFMA
     fragment order with the input projection and biases folded in."""
-    d_in = w_ih.shape[1]
-    for name, t, shape in (("w_ih", w_ih, (4 * LSTM_HIDDEN, d_in)), ("w_hh", w_hh, (4 * LSTM_HIDDEN, LSTM_HIDDEN)),
-                           ("b_ih", b_ih, (4 * LSTM_HIDDEN,)), ("b_hh", b_hh, (4 * LSTM_HIDDEN,))):
-        _dense(t.detach(), torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    d_in = _lstm_pack_params(w_ih, w_hh, b_ih, b_hh)
     lib = load()
     packed = torch.empty(int(lib.rl8_lstm_pack_floats()), dtype=torch.float32, device=w_hh.device)
     _check(lib.rl8_lstm_pack_f32(_ptr(w_ih.detach()), _ptr(w_hh.detach()), _ptr(b_ih.detach()), _ptr(b_hh.detach()),
@@ -1367,16 +1401,8 @@ def lstm_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_packed: 
     ``gates`` [B, L, 4, 256] and ``cs`` [B, L, 256] only with ``save``."""
     x = _dense(x.detach(), torch.float32, "x")
     b, l, d_in = x.shape
-    for name, t in (("h0", h0), ("c0", c0)):
-        _dense(t, torch.float32, name)
-        if tuple(t.shape) != (b, LSTM_HIDDEN):
-            raise ValueError(f"{name} must be [{b}, {LSTM_HIDDEN}], got {tuple(t.shape)}")
-    dev = x.device
-    hs = torch.empty(b, l, LSTM_HIDDEN, dtype=torch.float32, device=dev)
-    hn = torch.empty(b, LSTM_HIDDEN, dtype=torch.float32, device=dev)
-    cn = torch.empty(b, LSTM_HIDDEN, dtype=torch.float32, device=dev)
-    gates = torch.empty(b, l, 4, LSTM_HIDDEN, dtype=torch.float32, device=dev) if save else None
-    cs = torch.empty(b, l, LSTM_HIDDEN, dtype=torch.float32, device=dev) if save else None
+    _lstm_states_256(h0, c0, b)
+    hs, hn, cn, gates, cs = _lstm_outputs(b, l, LSTM_HIDDEN, x.device, save)
     with _timed("lstm_forward_save" if save else "lstm_forward", b * l):
         _check(load().rl8_lstm_forward_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_packed), _ptr(hs), _ptr(hn),
                                            _ptr(cn), _ptr(gates), _ptr(cs), _stream()), "rl8_lstm_forward_f32")
@@ -1393,34 +1419,26 @@ def lstm_narrow_supports(hidden: int, d_in: int) -> bool:
     return bool(load().rl8_lstm_narrow_supports(int(hidden), int(d_in)))
 
 
-def _lstm_narrow_params(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: None | torch.Tensor, w_hh: torch.Tensor,
-                        b_ih: None | torch.Tensor, b_hh: None | torch.Tensor) -> tuple[int, int, int, int]:
-    """(b, l, d_in, hidden) after the dtype / contiguity / shape checks of the narrow LSTM entries."""
+def _lstm_layer_params(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: None | torch.Tensor, w_hh: torch.Tensor,
+                       b_ih: None | torch.Tensor, b_hh: None | torch.Tensor, *,
+                       upper: bool = False) -> tuple[int, int, int, int]:
+    """(b, l, d_in, hidden) after the dtype / contiguity / shape checks of the narrow LSTM entries (``x`` [B, L, d_in],
+    H from ``w_hh``) or, with ``upper``, of the stacked ones (``x`` [B, L, H], the lower layer's hs: d_in = H). A
+    parameter the entry does not read is None."""
     _dense(x, torch.float32, "x")
     if x.ndim != 3:
-        raise ValueError("x must be [B, L, d_in]")
+        raise ValueError("x must be [B, L, H]" if upper else "x must be [B, L, d_in]")
     b, l, d_in = x.shape
-    hidden = w_hh.shape[1] if w_hh.ndim == 2 else -1
+    hidden = d_in if upper else w_hh.shape[1] if w_hh.ndim == 2 else -1
     shapes = (("h0", h0, (b, hidden)), ("c0", c0, (b, hidden)), ("w_ih", w_ih, (4 * hidden, d_in)),
               ("w_hh", w_hh, (4 * hidden, hidden)), ("b_ih", b_ih, (4 * hidden,)), ("b_hh", b_hh, (4 * hidden,)))
     for name, t, shape in shapes:
-        if t is None:
-            continue
-        _dense(t, torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
-    if b < 1 or l < 1 or not lstm_narrow_supports(hidden, d_in):
-        raise ValueError(f"no narrow LSTM kernel for b={b}, l={l}, hidden={hidden}, d_in={d_in}")
+        if t is not None:
+            _shaped(t, shape, name)
+    if b < 1 or l < 1 or not (lstm_stack_supports(hidden) if upper else lstm_narrow_supports(hidden, d_in)):
+        raise ValueError(f"no stacked LSTM kernel for b={b}, l={l}, hidden={hidden}" if upper else
+                         f"no narrow LSTM kernel for b={b}, l={l}, hidden={hidden}, d_in={d_in}")
     return b, l, d_in, hidden
-
-
-def _lstm_state_out(state_out: tuple[torch.Tensor, torch.Tensor], b: int, hidden: int):
-    """The caller's (hn, cn) [B, H] for a forward to write, checked."""
-    for name, t in zip(("hn", "cn"), state_out):
-        _dense(t, torch.float32, name)
-        if tuple(t.shape) != (b, hidden):
-            raise ValueError(f"{name} must have shape {(b, hidden)}, got {tuple(t.shape)}")
-    return state_out
 
 
 def lstm_narrow_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
@@ -1430,16 +1448,8 @@ def lstm_narrow_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_i
     [B, L, 4, H] (post-activation, order i, f, g, o) and ``cs`` [B, L, H] only with ``save``. ``state_out``: the
     (hn, cn) tensors to write (layer 0 of a stack writes its rows of the stack's states)."""
     x, h0, c0, w_ih, w_hh, b_ih, b_hh = (t.detach() for t in (x, h0, c0, w_ih, w_hh, b_ih, b_hh))
-    b, l, d_in, hidden = _lstm_narrow_params(x, h0, c0, w_ih, w_hh, b_ih, b_hh)
-    dev = x.device
-    hs = torch.empty(b, l, hidden, dtype=torch.float32, device=dev)
-    if state_out is None:
-        hn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
-        cn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
-    else:
-        hn, cn = _lstm_state_out(state_out, b, hidden)
-    gates = torch.empty(b, l, 4, hidden, dtype=torch.float32, device=dev) if save else None
-    cs = torch.empty(b, l, hidden, dtype=torch.float32, device=dev) if save else None
+    b, l, d_in, hidden = _lstm_layer_params(x, h0, c0, w_ih, w_hh, b_ih, b_hh)
+    hs, hn, cn, gates, cs = _lstm_outputs(b, l, hidden, x.device, save, state_out)
     with _timed("lstm_narrow_forward", b * l):
         _check(load().rl8_lstm_narrow_forward_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_ih), _ptr(w_hh),
                                                   _ptr(b_ih), _ptr(b_hh), hidden, _ptr(hs), _ptr(hn), _ptr(cn),
@@ -1457,12 +1467,10 @@ def lstm_narrow_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_
     if (heads is None) == (dhs is None):
         raise ValueError("lstm_narrow_backward: either dhs or heads")
     x, h0, c0, w_hh, hs, gates, cs = (t.detach() for t in (x, h0, c0, w_hh, hs, gates, cs))
-    b, l, d_in, hidden = _lstm_narrow_params(x, h0, c0, None, w_hh, None, None)
+    b, l, d_in, hidden = _lstm_layer_params(x, h0, c0, None, w_hh, None, None)
     for name, t, shape in (("hs", hs, (b, l, hidden)), ("gates", gates, (b, l, 4, hidden)), ("cs", cs, (b, l, hidden)),
                            *([("dhs", dhs.detach(), (b, l, hidden))] if heads is None else [])):
-        _dense(t, torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        _shaped(t, shape, name)
     lib = load()
     ws = torch.empty(int(lib.rl8_lstm_narrow_workspace_bytes(b, l, hidden, d_in)) // 4, dtype=torch.float32,
                      device=x.device)
@@ -1474,11 +1482,7 @@ def lstm_narrow_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_
         if not 1 <= n <= ROWS_BACKWARD_HEADS or tuple(w.shape) != (n, hidden) or dout.numel() != b * l * n \
                 or dout.dtype != torch.float32 or w.dtype != torch.float32:
             raise ValueError(f"heads: float32 dout [B * L, n], w [n, {hidden}], n <= {ROWS_BACKWARD_HEADS}")
-        # four floats per row-step, four weight rows, zero-padded
-        dout4 = torch.zeros(b * l, ROWS_BACKWARD_HEADS, dtype=torch.float32, device=x.device)
-        dout4[:, :n] = dout.detach().reshape(b * l, n)
-        w4 = torch.zeros(ROWS_BACKWARD_HEADS, hidden, dtype=torch.float32, device=x.device)
-        w4[:n] = w.detach()
+        dout4, w4 = _heads_padded(dout, w, n, b * l)
         with _timed("lstm_narrow_backward", b * l):  # (one name for both forms, as "lstm_rows_backward" is at 256)
             _check(lib.rl8_lstm_narrow_backward_heads_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_hh), hidden,
                                                           _ptr(hs), _ptr(gates), _ptr(cs), _ptr(dout4), _ptr(w4),
@@ -1503,26 +1507,6 @@ def lstm_stack_supports(hidden: int) -> bool:
     return bool(load().rl8_lstm_stack_supports(int(hidden)))
 
 
-def _lstm_stack_params(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
-                       b_ih: None | torch.Tensor, b_hh: None | torch.Tensor) -> tuple[int, int, int]:
-    """(b, l, hidden) after the dtype / contiguity / shape checks of the stacked LSTM entries."""
-    _dense(x, torch.float32, "x")
-    if x.ndim != 3:
-        raise ValueError("x must be [B, L, H]")
-    b, l, hidden = x.shape
-    shapes = (("h0", h0, (b, hidden)), ("c0", c0, (b, hidden)), ("w_ih", w_ih, (4 * hidden, hidden)),
-              ("w_hh", w_hh, (4 * hidden, hidden)), ("b_ih", b_ih, (4 * hidden,)), ("b_hh", b_hh, (4 * hidden,)))
-    for name, t, shape in shapes:
-        if t is None:
-            continue
-        _dense(t, torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
-    if b < 1 or l < 1 or not lstm_stack_supports(hidden):
-        raise ValueError(f"no stacked LSTM kernel for b={b}, l={l}, hidden={hidden}")
-    return b, l, hidden
-
-
 def lstm_stack_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
                        b_ih: torch.Tensor, b_hh: torch.Tensor, *, save: bool = False,
                        zin: None | torch.Tensor = None,
@@ -1531,21 +1515,11 @@ def lstm_stack_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih
     cs) as :func:`lstm_narrow_forward`. ``zin``: [B, L, 4, H] floats of scratch for the input projection (made here
     when None; a stack hands the same one to every layer)."""
     x, h0, c0, w_ih, w_hh, b_ih, b_hh = (t.detach() for t in (x, h0, c0, w_ih, w_hh, b_ih, b_hh))
-    b, l, hidden = _lstm_stack_params(x, h0, c0, w_ih, w_hh, b_ih, b_hh)
-    dev = x.device
+    b, l, _, hidden = _lstm_layer_params(x, h0, c0, w_ih, w_hh, b_ih, b_hh, upper=True)
     if zin is None:
-        zin = torch.empty(b, l, 4, hidden, dtype=torch.float32, device=dev)
-    _dense(zin, torch.float32, "zin")
-    if tuple(zin.shape) != (b, l, 4, hidden):
-        raise ValueError(f"zin must have shape {(b, l, 4, hidden)}, got {tuple(zin.shape)}")
-    hs = torch.empty(b, l, hidden, dtype=torch.float32, device=dev)
-    if state_out is None:
-        hn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
-        cn = torch.empty(b, hidden, dtype=torch.float32, device=dev)
-    else:
-        hn, cn = _lstm_state_out(state_out, b, hidden)
-    gates = torch.empty(b, l, 4, hidden, dtype=torch.float32, device=dev) if save else None
-    cs = torch.empty(b, l, hidden, dtype=torch.float32, device=dev) if save else None
+        zin = torch.empty(b, l, 4, hidden, dtype=torch.float32, device=x.device)
+    _shaped(zin, (b, l, 4, hidden), "zin")
+    hs, hn, cn, gates, cs = _lstm_outputs(b, l, hidden, x.device, save, state_out)
     with _timed("lstm_stack_forward", b * l):
         _check(load().rl8_lstm_stack_forward_f32(_ptr(x), b, l, _ptr(h0), _ptr(c0), _ptr(w_ih), _ptr(w_hh), _ptr(b_ih),
                                                  _ptr(b_hh), hidden, _ptr(zin), _ptr(hs), _ptr(hn), _ptr(cn),
@@ -1560,12 +1534,10 @@ def lstm_stack_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_i
     lower layer's dL/dhs) for ``dhs`` [B, L, H], from what :func:`lstm_stack_forward` saved (deterministic). No
     gradient for h0, c0."""
     x, h0, c0, w_ih, w_hh, hs, gates, cs, dhs = (t.detach() for t in (x, h0, c0, w_ih, w_hh, hs, gates, cs, dhs))
-    b, l, hidden = _lstm_stack_params(x, h0, c0, w_ih, w_hh, None, None)
+    b, l, _, hidden = _lstm_layer_params(x, h0, c0, w_ih, w_hh, None, None, upper=True)
     for name, t, shape in (("hs", hs, (b, l, hidden)), ("gates", gates, (b, l, 4, hidden)), ("cs", cs, (b, l, hidden)),
                            ("dhs", dhs, (b, l, hidden))):
-        _dense(t, torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        _shaped(t, shape, name)
     lib = load()
     ws = torch.empty(int(lib.rl8_lstm_stack_workspace_bytes(b, l, hidden)) // 4, dtype=torch.float32, device=x.device)
     sizes = (4 * hidden * hidden, 4 * hidden * hidden, 4 * hidden)
@@ -1590,12 +1562,7 @@ def lstm_split_supports(d_in: int) -> bool:
 def lstm_pack_split(w_ih: torch.Tensor, w_hh: torch.Tensor, b_ih: torch.Tensor, b_hh: torch.Tensor):
     """torch.nn.LSTM parameters -> (W_hh as bf16 planes in the step kernel's fragment order,
     ``wb`` [1024, 8] = [w_ih | 0.. | b_ih + b_hh])."""
-    d_in = w_ih.shape[1]
-    for name, t, shape in (("w_ih", w_ih, (4 * LSTM_HIDDEN, d_in)), ("w_hh", w_hh, (4 * LSTM_HIDDEN, LSTM_HIDDEN)),
-                           ("b_ih", b_ih, (4 * LSTM_HIDDEN,)), ("b_hh", b_hh, (4 * LSTM_HIDDEN,))):
-        _dense(t.detach(), torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    d_in = _lstm_pack_params(w_ih, w_hh, b_ih, b_hh)
     lib = load()
     packed = torch.empty(int(lib.rl8_lstm_split_packed_bytes()), dtype=torch.uint8, device=w_hh.device)
     wb = torch.empty(int(lib.rl8_lstm_split_wb_floats()), dtype=torch.float32, device=w_hh.device)
@@ -1642,12 +1609,8 @@ def lstm_forward_split(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, pack
     earlier :func:`lstm_split_state` (read only; no split is made here)."""
     x = _dense(x.detach(), torch.float32, "x")
     b, l, d_in = x.shape
-    for name, t in (("h0", h0), ("c0", c0)):
-        _dense(t, torch.float32, name)
-        if tuple(t.shape) != (b, LSTM_HIDDEN):
-            raise ValueError(f"{name} must be [{b}, {LSTM_HIDDEN}], got {tuple(t.shape)}")
-    dev = x.device
-    lib = load()
+    _lstm_states_256(h0, c0, b)
+    dev, lib = x.device, load()
     hs = torch.empty(b, l, LSTM_HIDDEN, dtype=torch.float32, device=dev)
     cs = torch.empty(b, l, LSTM_HIDDEN, dtype=torch.float32, device=dev)
     gates = torch.empty(b, l, 4, LSTM_HIDDEN, dtype=torch.float32, device=dev) if save else None
@@ -1719,9 +1682,7 @@ def lstm_rows_backward(c0: torch.Tensor, gates: torch.Tensor, cs: torch.Tensor, 
     elif dhs is not None:
         raise ValueError("lstm_rows_backward: either dhs or heads")
     for name, t, shape in checks:
-        _dense(t, torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        _shaped(t, shape, name)
     dev = gates.device
     dgates = torch.empty(b, l, 4, LSTM_HIDDEN, dtype=torch.float32, device=dev)
     dc = torch.empty(b, LSTM_HIDDEN, dtype=torch.float32, device=dev)
@@ -1731,11 +1692,7 @@ def lstm_rows_backward(c0: torch.Tensor, gates: torch.Tensor, cs: torch.Tensor, 
         n = w.shape[0]
         if n > ROWS_BACKWARD_HEADS or tuple(w.shape) != (n, LSTM_HIDDEN) or dout.numel() != b * l * n:
             raise ValueError(f"heads: dout [B * L, n], w [n, 256], n <= {ROWS_BACKWARD_HEADS}")
-        # four floats per row-step, four weight rows: one 16-byte piece per sequence and head-row segment
-        dout4 = torch.zeros(b * l, ROWS_BACKWARD_HEADS, dtype=torch.float32, device=dev)
-        dout4[:, :n] = dout.reshape(b * l, n)
-        w4 = torch.zeros(ROWS_BACKWARD_HEADS, LSTM_HIDDEN, dtype=torch.float32, device=dev)
-        w4[:n] = w.detach()
+        dout4, w4 = _heads_padded(dout, w, n, b * l)
         with _timed("lstm_rows_backward", b * l):
             _check(load().rl8_lstm_rows_backward_heads_f32(b, l, _ptr(c0), _ptr(gates), _ptr(cs), _ptr(dout4), _ptr(w4),
                                                            _ptr(packed), _ptr(dgates), _ptr(dc), _ptr(bound), _stream()),
@@ -1782,9 +1739,7 @@ def lstm_backward(
     for name, t, shape in (("h0", h0, (b, LSTM_HIDDEN)), ("c0", c0, (b, LSTM_HIDDEN)), ("hs", hs, (b, l, LSTM_HIDDEN)),
                            ("gates", gates, (b, l, 4, LSTM_HIDDEN)), ("cs", cs, (b, l, LSTM_HIDDEN)),
                            *([("dhs", dhs, (b, l, LSTM_HIDDEN))] if heads is None else [])):
-        _dense(t, torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        _shaped(t, shape, name)
     if wgrad is None:
         wgrad = ("f32" if not split else "bf16" if rows_packed is None else
                  "f16-gates" if b >= LSTM_WGRAD_GATES_MIN_ROWS else "f16")

@@ -134,7 +134,7 @@ def _run_lstm_heads(lstm: nn.LSTM, heads: list[nn.Linear], obs: torch.Tensor,
     that applies (``fused_lstm.lstm_heads_forward``), else the LSTM (fused or the module) and then the heads."""
     from .nn import fused_lstm
 
-    if lstm.num_layers == 1 and torch.is_grad_enabled():
+    if torch.is_grad_enabled():  # (a rollout step does not pay for the slices; layer 0's states: a stack gets None)
         h_first = states[DataKeys.HIDDEN_STATES][:, 0, 0]
         c_first = states[DataKeys.CELL_STATES][:, 0, 0]
         fused = fused_lstm.lstm_heads_forward(lstm, heads, obs, h_first, c_first)

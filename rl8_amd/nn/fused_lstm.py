@@ -1,23 +1,30 @@
-"""The default recurrent models' LSTM as fused gfx950 kernels.
+"""``torch.nn.LSTM`` and the ``Linear`` heads on its outputs as fused gfx950 kernels.
 
-``torch.nn.LSTM(d_in, 256, num_layers=1, batch_first=True)`` -- what
-``DefaultContinuousRecurrentModel`` / ``DefaultDiscreteRecurrentModel`` are built
-around (``src/rl8/models/_recurrent.py:201-321`` of the reference) -- runs as one
-forward kernel (time loop inside, gates never leave the chip) and, for training,
-one backward-through-time kernel plus the weight-gradient kernels, instead of two
-GEMMs and a pointwise kernel per timestep. ``nn.LSTM(d_in, 64 | 128)`` with
-d_in <= 16 -- the reference's example model is ``nn.LSTM(4, 64)`` -- runs the
-narrow kernels (lstm_narrow_kernels.hip: fp32 MFMA forward with the time loop
-inside, backward through time, deterministic weight gradient) under the same
-rules. Parameters stay the module's own; ``lstm_forward`` returns ``None`` for
-any other LSTM (more layers, other widths, projections, bidirectional, non-HIP /
-non-fp32 inputs) and the caller runs the module itself. Two or more layers of
-width 64 / 128 without dropout have their own entry, ``lstm_stack_forward``:
-layer 0 on the narrow kernels, the layers above on the lstm_narrow_stack_*
-kernels (input projection over all row-steps, recurrent forward from it, input
-gradient for the layer below). The ``Linear(64 | 128, n)`` heads on any of these
-run lstm_narrow_heads_kernels.hip, and a training pass through one narrow layer
-and heads of at most four outputs is one node (``_NarrowLSTMHeads``), as at 256.
+The time loop runs inside the kernels and the gates never leave the chip; parameters stay the module's own. Which
+kernels a module gets is decided once, by ``_family`` (the module) and ``_input_ok`` (the input); every entry point
+returns ``None`` for anything else (other widths, projections, bidirectional, no bias, dropout between layers,
+non-HIP / non-fp32 inputs) and the caller runs the module itself.
+
+========  ===================================  =================================  ===========================
+family    envelope                             kernels                            entry point
+========  ===================================  =================================  ===========================
+"256"     one layer, H = 256, d_in <= 7        lstm_kernels.hip, lstm_split_ /    ``lstm_forward``; with
+          (``hip.lstm_supports``); the route   lstm_rows_kernels.hip (packs       heads: ``lstm_heads_forward``
+          inside it comes from ``_plan``       cached on the module)              (``_FusedLSTMHeads``)
+"narrow"  one layer, H = 64 / 128, d_in <= 16  lstm_narrow_kernels.hip (weights   ``lstm_forward``; with
+          (``hip.lstm_narrow_supports``)       in torch layout: no plan, no       heads: ``lstm_heads_forward``
+                                               packs, no planes)                  (``_NarrowLSTMHeads``)
+"stack"   two or more layers of the narrow     layer 0 as "narrow", the layers    ``lstm_stack_forward``
+          envelope, ``dropout == 0``           above on lstm_narrow_stack_*
+          (``hip.lstm_stack_supports``)
+heads     ``Linear(H, n_i)``, sum n_i <= 8,    lstm_kernels.hip (H = 256),        ``heads_forward``
+          on latents of any of the widths      lstm_narrow_heads_kernels.hip
+========  ===================================  =================================  ===========================
+
+A training pass through one layer and heads of at most four outputs is one autograd node whose backward through time
+forms the heads' data gradient itself (``lstm_heads_forward``); the reference's default models are built around
+``nn.LSTM(d_in, 256, batch_first=True)`` (``src/rl8/models/_recurrent.py:201-321``), its example around
+``nn.LSTM(4, 64)``.
 
 """
 
@@ -51,45 +58,36 @@ def _rollout_fuse_heads() -> bool:
     return os.environ.get("RL8_AMD_ROLLOUT_FUSE_HEADS", "1") != "0"
 
 
-def _eligible(lstm: nn.LSTM, x: torch.Tensor) -> bool:
-    return (
-        ENABLED
-        and x.is_cuda
-        and x.dtype == torch.float32
-        and x.ndim == 3
-        and lstm.num_layers == 1
-        and lstm.hidden_size == hip.LSTM_HIDDEN
-        and lstm.batch_first
-        and lstm.bias
-        and not lstm.bidirectional
-        and lstm.proj_size == 0
-        and x.shape[2] == lstm.input_size
-        and hip.lstm_supports(lstm.input_size)
-    )
-
-
 @functools.lru_cache(maxsize=None)
 def _narrow_supported(hidden: int, d_in: int) -> bool:
     """The narrow kernels are compiled for this (hidden, d_in): fixed by the build, asked once per pair."""
     return hip.lstm_narrow_supports(hidden, d_in)
 
 
-def _narrow_eligible(lstm: nn.LSTM, x: torch.Tensor) -> bool:
-    """``_eligible`` at hidden width 64 or 128 and d_in <= 16 (lstm_narrow_kernels.hip)."""
-    return (
-        ENABLED
-        and x.is_cuda
-        and x.dtype == torch.float32
-        and x.ndim == 3
-        and lstm.num_layers == 1
-        and lstm.hidden_size in hip.LSTM_NARROW_HIDDEN
-        and lstm.batch_first
-        and lstm.bias
-        and not lstm.bidirectional
-        and lstm.proj_size == 0
-        and x.shape[2] == lstm.input_size
-        and _narrow_supported(lstm.hidden_size, lstm.input_size)
-    )
+def _family(lstm: nn.LSTM) -> None | str:
+    """The kernels this module's LSTM runs on, the one place that is decided: "256" (one layer of width 256; the
+    routes inside that family are ``_plan``'s), "narrow" (one layer of width 64 / 128, d_in <= 16), "stack" (two or
+    more such layers without dropout between them) or ``None`` (the module itself). Reads ``ENABLED`` as it is now."""
+    if not (ENABLED and lstm.batch_first and lstm.bias and not lstm.bidirectional and lstm.proj_size == 0):
+        return None
+    hidden, d_in = lstm.hidden_size, lstm.input_size
+    if hidden == hip.LSTM_HIDDEN:
+        return "256" if lstm.num_layers == 1 and hip.lstm_supports(d_in) else None
+    if hidden not in hip.LSTM_NARROW_HIDDEN or not _narrow_supported(hidden, d_in):
+        return None
+    if lstm.num_layers == 1:
+        return "narrow"
+    return "stack" if lstm.dropout == 0 and hip.lstm_stack_supports(hidden) else None
+
+
+def _input_ok(lstm: nn.LSTM, x: torch.Tensor) -> bool:
+    """``x`` is what every family's kernels take: float32 [B, L, input_size] on the device."""
+    return x.is_cuda and x.dtype == torch.float32 and x.ndim == 3 and x.shape[2] == lstm.input_size
+
+
+def _family_for(lstm: nn.LSTM, x: torch.Tensor) -> None | str:
+    """``_family(lstm)`` where ``x`` is an input its kernels take, else ``None``: all an entry point asks."""
+    return _family(lstm) if _input_ok(lstm, x) else None
 
 
 def _packs(lstm: nn.LSTM, kind: str):
@@ -222,6 +220,21 @@ class _NarrowLSTM(torch.autograd.Function):
         return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None
 
 
+def _lstm_heads_backward(hs, w_heads, dout, dhs, heads_backward, lstm_backward):
+    """The backward of an LSTM + heads node, ``(g, dw, db)``: the heads' parameter gradients (``heads_backward``:
+    ``hip.linear_heads_backward`` or its narrow form), then the backward through time as ``lstm_backward(dhs, heads)``.
+    Where nothing but the heads reads the latents that kernel forms dL/dh_t from ``heads`` = (dout, w_heads) itself;
+    otherwise the heads' backward writes it out and the other readers' ``dhs`` is added."""
+    flat = hs.view(-1, hs.shape[2])
+    dout = (torch.zeros(flat.shape[0], w_heads.shape[0], dtype=torch.float32, device=flat.device) if dout is None
+            else dout.contiguous().float())
+    if dhs is None:  # the usual case
+        _, dw, db = heads_backward(flat, dout, w_heads, need_dh=False)
+        return lstm_backward(None, (dout, w_heads)), dw, db
+    dh, dw, db = heads_backward(flat, dout, w_heads)
+    return lstm_backward(dh.view_as(hs) + dhs.float(), None), dw, db
+
+
 class _NarrowLSTMHeads(torch.autograd.Function):
     """:class:`_NarrowLSTM` + output heads of a training pass as one node, as :class:`_FusedLSTMHeads` is at 256: the
     heads' data gradient dL/dh_t = dOut x W (n <= 4) is formed inside the backward through time from the 16 bytes
@@ -239,39 +252,13 @@ class _NarrowLSTMHeads(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, dhs, dcn):  # type: ignore[override]
         x, h0, c0, w_hh, hs, gates, cs, w_heads = ctx.saved_tensors
-        flat = hs.view(-1, hs.shape[2])
-        dout = (torch.zeros(flat.shape[0], w_heads.shape[0], dtype=torch.float32, device=flat.device) if dout is None
-                else dout.contiguous().float())
-        if dhs is None:  # nothing but the heads reads the latents: the usual case
-            _, dw, db = hip.linear_heads_narrow_backward(flat, dout, w_heads, need_dh=False)
-            g = hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, None, heads=(dout, w_heads))
-        else:
-            dh, dw, db = hip.linear_heads_narrow_backward(flat, dout, w_heads)
-            g = hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, dh.view_as(hs) + dhs.float())
+        g, dw, db = _lstm_heads_backward(
+            hs, w_heads, dout, dhs, hip.linear_heads_narrow_backward,
+            lambda dhs, heads: hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, dhs, heads=heads))
         return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], dw, db
 
 
 _STACK_PARAMS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
-
-
-def _stack_eligible(lstm: nn.LSTM, x: torch.Tensor) -> bool:
-    """``_narrow_eligible`` with two or more layers and no dropout between them (lstm_narrow_stack_* kernels)."""
-    return (
-        ENABLED
-        and x.is_cuda
-        and x.dtype == torch.float32
-        and x.ndim == 3
-        and lstm.num_layers >= 2
-        and lstm.dropout == 0
-        and lstm.hidden_size in hip.LSTM_NARROW_HIDDEN
-        and lstm.batch_first
-        and lstm.bias
-        and not lstm.bidirectional
-        and lstm.proj_size == 0
-        and x.shape[2] == lstm.input_size
-        and _narrow_supported(lstm.hidden_size, lstm.input_size)
-        and hip.lstm_stack_supports(lstm.hidden_size)
-    )
 
 
 class _StackLSTM(torch.autograd.Function):
@@ -324,7 +311,7 @@ def lstm_stack_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: tor
     or ``None`` when this LSTM / input is not eligible (one layer, other widths, d > 16, no bias, dropout,
     projections, bidirectional, non-HIP / non-fp32 inputs). No gradient flows to ``x``, ``h0``, ``c0`` nor out of
     ``h_n``, ``c_n``."""
-    if not _stack_eligible(lstm, x):
+    if _family_for(lstm, x) != "stack":
         return None
     weights = [getattr(lstm, f"{name}_l{k}") for k in range(lstm.num_layers) for name in _STACK_PARAMS]
     hs, hn, cn = _StackLSTM.apply(
@@ -340,49 +327,36 @@ def lstm_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Ten
     ``None`` when this LSTM / input is not eligible (H = 256 with d <= 7, or H = 64 /
     128 with d <= 16). No gradient flows to ``x``, ``h0``, ``c0`` (rollout-buffer
     data) nor out of ``c_n``."""
-    if _narrow_eligible(lstm, x):
-        hs, cn = _NarrowLSTM.apply(
-            x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
-            lstm.bias_ih_l0, lstm.bias_hh_l0, torch.is_grad_enabled(),
-        )
-        return hs, hs[:, -1], cn
-    if not _eligible(lstm, x):
+    family = _family_for(lstm, x)
+    if family not in ("256", "narrow"):  # (a stack has its own entry and state layout: lstm_stack_forward)
         return None
-    hs, cn = _FusedLSTM.apply(
-        x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
-        lstm.bias_ih_l0, lstm.bias_hh_l0, lstm, torch.is_grad_enabled(), _plan(lstm.input_size, x.shape[0]),
-    )
+    args = (x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
+            lstm.bias_ih_l0, lstm.bias_hh_l0)
+    if family == "narrow":
+        hs, cn = _NarrowLSTM.apply(*args, torch.is_grad_enabled())
+    else:
+        hs, cn = _FusedLSTM.apply(*args, lstm, torch.is_grad_enabled(), _plan(lstm.input_size, x.shape[0]))
     return hs, hs[:, -1], cn  # h_n is h_{L-1}: a view, so a gradient into it reaches dhs by itself
 
 
-class _FusedHeads(torch.autograd.Function):
+class _Heads(torch.autograd.Function):
+    """``Linear(H, n)`` heads, stacked, on latents ``h`` [M, H]: lstm_kernels.hip at H = 256,
+    lstm_narrow_heads_kernels.hip at 64 / 128."""
+
     @staticmethod
     def forward(ctx, h, w, b):  # type: ignore[override]
-        out = hip.linear_heads_forward(h, w, b)
+        forward = hip.linear_heads_forward if h.shape[1] == hip.LSTM_HIDDEN else hip.linear_heads_narrow_forward
+        out = forward(h, w, b)
         ctx.save_for_backward(h, w)
         return out
 
     @staticmethod
     def backward(ctx, dout):  # type: ignore[override]
         h, w = ctx.saved_tensors
-        dh, dw, db = hip.linear_heads_backward(h, dout.contiguous().float(), w)
-        return dh, dw, db
-
-
-class _NarrowHeads(torch.autograd.Function):
-    """:class:`_FusedHeads` for latents of width 64 / 128 (lstm_narrow_heads_kernels.hip)."""
-
-    @staticmethod
-    def forward(ctx, h, w, b):  # type: ignore[override]
-        out = hip.linear_heads_narrow_forward(h, w, b)
-        ctx.save_for_backward(h, w)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):  # type: ignore[override]
-        h, w = ctx.saved_tensors
-        dh, dw, db = hip.linear_heads_narrow_backward(h, dout.contiguous().float(), w, need_dh=ctx.needs_input_grad[0])
-        return dh, dw, db
+        dout = dout.contiguous().float()
+        if h.shape[1] == hip.LSTM_HIDDEN:
+            return hip.linear_heads_backward(h, dout, w)
+        return hip.linear_heads_narrow_backward(h, dout, w, need_dh=ctx.needs_input_grad[0])
 
 
 class _FusedLSTMHeads(torch.autograd.Function):
@@ -406,20 +380,14 @@ class _FusedLSTMHeads(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, dhs, dcn):  # type: ignore[override]
         x, h0, c0, hs, gates, cs, w_heads = ctx.saved_tensors
-        flat = hs.view(-1, hip.LSTM_HIDDEN)
-        dout = (torch.zeros(flat.shape[0], w_heads.shape[0], dtype=torch.float32, device=flat.device) if dout is None
-                else dout.contiguous().float())
         common = dict(wgrad=ctx.plan.wgrad, rows_packed=_packs(ctx.lstm, "rows"), h0_bound=ctx.h0_bound, hs_bound=1.0)
-        if dhs is None:  # nothing but the heads reads the latents: the usual case
-            _, dw, db = hip.linear_heads_backward(flat, dout, w_heads, need_dh=False)
-            g = hip.lstm_backward(x, h0, c0, hs, gates, cs, None, None, heads=(dout, w_heads), **common)
-        else:
-            dh, dw, db = hip.linear_heads_backward(flat, dout, w_heads)
-            g = hip.lstm_backward(x, h0, c0, hs, gates, cs, dh.view_as(hs) + dhs.float(), None, **common)
+        g, dw, db = _lstm_heads_backward(
+            hs, w_heads, dout, dhs, hip.linear_heads_backward,
+            lambda dhs, heads: hip.lstm_backward(x, h0, c0, hs, gates, cs, dhs, None, heads=heads, **common))
         return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], dw, db, None, None
 
 
-def _heads_eligible(heads: list[nn.Linear], max_out: int, hidden: int = hip.LSTM_HIDDEN) -> bool:
+def _heads_eligible(heads: list[nn.Linear], max_out: int, hidden: int) -> bool:
     if any(h.in_features != hidden or h.bias is None or h.weight.dtype != torch.float32 for h in heads):
         return False
     return sum(h.out_features for h in heads) <= max_out
@@ -432,42 +400,24 @@ def _stacked(heads: list[nn.Linear]) -> tuple[torch.Tensor, torch.Tensor, list[i
     return w, b, [h.out_features for h in heads]
 
 
-def _narrow_lstm_heads_forward(lstm: nn.LSTM, heads: list[nn.Linear], x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
-    """:func:`lstm_heads_forward` for a one-layer LSTM of width 64 / 128 (``x`` already found ``_narrow_eligible``)."""
-    if not (FUSE_HEADS and _heads_eligible(heads, hip.ROWS_BACKWARD_HEADS, lstm.hidden_size)
+def lstm_heads_forward(lstm: nn.LSTM, heads: list[nn.Linear], x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
+    """A training pass through a one-layer ``lstm`` and ``Linear(H, n_i)`` heads on its outputs as one autograd node
+    (:class:`_FusedLSTMHeads` at H = 256, :class:`_NarrowLSTMHeads` at 64 / 128):
+    ``([head_i(hs) as [B * L, n_i]], hs [B, L, H], h_n, c_n)``, or ``None`` when this combination is not eligible (no
+    gradient wanted, a stack, more than four head outputs, the heads switched off or -- at 256 -- a plan that does not
+    fuse them): the caller then runs :func:`lstm_forward` / :func:`lstm_stack_forward` and :func:`heads_forward`."""
+    family = _family_for(lstm, x) if torch.is_grad_enabled() else None
+    if family not in ("256", "narrow"):
+        return None
+    plan = _plan(lstm.input_size, x.shape[0]) if family == "256" else None  # (the narrow family reads no plan)
+    if not ((FUSE_HEADS if plan is None else plan.fuse_heads)
+            and _heads_eligible(heads, hip.ROWS_BACKWARD_HEADS, lstm.hidden_size)
             and any(p.requires_grad for p in lstm.parameters())):
         return None
     w, b, widths = _stacked(heads)
-    out, hs, cn = _NarrowLSTMHeads.apply(
-        x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
-        lstm.bias_ih_l0, lstm.bias_hh_l0, w, b,
-    )
-    return list(out.split(widths, dim=1)), hs, hs[:, -1], cn
-
-
-def lstm_heads_forward(lstm: nn.LSTM, heads: list[nn.Linear], x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
-    """A training pass through ``lstm`` and ``Linear(256, n_i)`` heads on its outputs as one autograd node
-    (:class:`_FusedLSTMHeads`): ``([head_i(hs) as [B * L, n_i]], hs [B, L, 256], h_n, c_n)``, or ``None`` when this
-    combination is not eligible (no gradient wanted, more than four head outputs, a plan that does not fuse the
-    heads): the caller then runs :func:`lstm_forward` and :func:`heads_forward`. A one-layer LSTM of width 64 / 128
-    with ``Linear(H, n_i)`` heads has its own node (:class:`_NarrowLSTMHeads`), decided before any width-256 rule."""
-    if not torch.is_grad_enabled():
-        return None
-    if _narrow_eligible(lstm, x):
-        return _narrow_lstm_heads_forward(lstm, heads, x, h0, c0)
-    if not _eligible(lstm, x):
-        return None
-    plan = _plan(lstm.input_size, x.shape[0])
-    if not (plan.fuse_heads and _heads_eligible(heads, hip.ROWS_BACKWARD_HEADS)
-            and any(p.requires_grad for p in lstm.parameters())):
-        return None
-    widths = [h.out_features for h in heads]
-    w = torch.cat([h.weight for h in heads], 0) if len(heads) > 1 else heads[0].weight
-    b = torch.cat([h.bias for h in heads], 0) if len(heads) > 1 else heads[0].bias
-    out, hs, cn = _FusedLSTMHeads.apply(
-        x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
-        lstm.bias_ih_l0, lstm.bias_hh_l0, w, b, lstm, plan,
-    )
+    args = (x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
+            lstm.bias_ih_l0, lstm.bias_hh_l0, w, b)
+    out, hs, cn = _NarrowLSTMHeads.apply(*args) if plan is None else _FusedLSTMHeads.apply(*args, lstm, plan)
     return list(out.split(widths, dim=1)), hs, hs[:, -1], cn
 
 
@@ -485,5 +435,5 @@ def heads_forward(heads: list[nn.Linear], latents: torch.Tensor) -> None | list[
     if sum(widths) > hip.HEADS_MAX_OUT:
         return None
     flat = latents.reshape(-1, hidden)
-    out = (_NarrowHeads if narrow else _FusedHeads).apply(flat.contiguous(), w, b)
+    out = _Heads.apply(flat.contiguous(), w, b)
     return list(out.split(widths, dim=1))

@@ -190,7 +190,8 @@ def _model(kind: str = "discrete", **config):
 
 @pytest.fixture
 def no_device(monkeypatch):
-    """``hip.load`` and the build's queries stubbed; anything that would pack weights or make planes is recorded."""
+    """``hip.load`` and the build's queries stubbed (and the memo of the narrow one dropped, before and after: nothing
+    may keep a stub's answers); anything that would pack weights or make planes is recorded."""
     asked = {"packs": [], "planes": 0, "plans": 0}
 
     def planes(rows, device, copies=1):
@@ -204,11 +205,14 @@ def no_device(monkeypatch):
     monkeypatch.setattr(hip, "load", lambda: None)
     monkeypatch.setattr(hip, "lstm_narrow_supports", lambda hidden, d_in: hidden in (64, 128) and 1 <= d_in <= 16)
     monkeypatch.setattr(hip, "lstm_supports", lambda d_in: 1 <= d_in <= 7)
+    monkeypatch.setattr(hip, "lstm_stack_supports", lambda hidden: hidden in (64, 128))
     monkeypatch.setattr(hip, "lstm_state_planes", planes)
     monkeypatch.setattr(fused_lstm, "_packs", lambda lstm, kind: asked["packs"].append(kind) or torch.zeros(1))
     monkeypatch.setattr(fused_lstm, "_plan", plan)
     monkeypatch.setattr(fused_lstm, "ENABLED", True)
-    return asked
+    fused_lstm._narrow_supported.cache_clear()
+    yield asked
+    fused_lstm._narrow_supported.cache_clear()
 
 
 @pytest.mark.parametrize("hidden", [64, 128])
@@ -241,9 +245,11 @@ def test_lean_rollout_is_not_available_outside_the_narrow_envelope(no_device, mo
     assert not _LeanRollout.available(_algo(monkeypatch, _model("continuous", hidden_size=64), distribution=Normal))
     assert not _LeanRollout.available(_algo(monkeypatch, _model("continuous", hidden_size=128)))
     monkeypatch.setattr(hip, "lstm_narrow_supports", lambda hidden, d_in: False)  # a build without this (hidden, d_in)
+    fused_lstm._narrow_supported.cache_clear()
     assert not _LeanRollout.available(_algo(monkeypatch, _model(hidden_size=64)))
     monkeypatch.setattr(fused_lstm, "ENABLED", False)
     monkeypatch.setattr(hip, "lstm_narrow_supports", lambda hidden, d_in: True)
+    fused_lstm._narrow_supported.cache_clear()
     assert not _LeanRollout.available(_algo(monkeypatch, _model(hidden_size=64)))
 
 

@@ -175,3 +175,77 @@ def test_lean_rollout_takes_its_step_kernel_from_the_plan(envelope, monkeypatch,
         planes = fused_lstm._plan(d_in, lean.n).forward_planes
         assert lean.split == planes and packs == ["split" if planes else "step"]
         assert lean.fuse_heads == (fuse == "1")  # (read when the rollout is set up)
+
+
+# --- which family of kernels an nn.LSTM gets (``fused_lstm._family`` / ``_input_ok``) -----------------------------------
+@pytest.fixture
+def families(monkeypatch):
+    """The build's three envelope queries stubbed with what ``include/rl8_amd.h`` documents."""
+    monkeypatch.setattr(hip, "lstm_supports", lambda d_in: 1 <= d_in <= 7)
+    monkeypatch.setattr(hip, "lstm_narrow_supports", lambda hidden, d_in: hidden in (64, 128) and 1 <= d_in <= 16)
+    monkeypatch.setattr(hip, "lstm_stack_supports", lambda hidden: hidden in (64, 128))
+    fused_lstm._narrow_supported.cache_clear()
+    yield
+    fused_lstm._narrow_supported.cache_clear()  # (before the stubs go: nothing may keep their answers)
+
+
+def _families_by_predicate(enabled, lstm, x) -> tuple[bool, bool, bool]:
+    """``_eligible``, ``_narrow_eligible`` and ``_stack_eligible`` as they stood while each family had its own
+    predicate, clause for clause, on the stubbed envelopes."""
+    wide = bool(
+        enabled and x.is_cuda and x.dtype == torch.float32 and x.ndim == 3 and lstm.num_layers == 1
+        and lstm.hidden_size == 256 and lstm.batch_first and lstm.bias and not lstm.bidirectional
+        and lstm.proj_size == 0 and x.shape[2] == lstm.input_size and 1 <= lstm.input_size <= 7
+    )
+    narrow = bool(
+        enabled and x.is_cuda and x.dtype == torch.float32 and x.ndim == 3 and lstm.num_layers == 1
+        and lstm.hidden_size in (64, 128) and lstm.batch_first and lstm.bias and not lstm.bidirectional
+        and lstm.proj_size == 0 and x.shape[2] == lstm.input_size
+        and (lstm.hidden_size in (64, 128) and 1 <= lstm.input_size <= 16)
+    )
+    stack = bool(
+        enabled and x.is_cuda and x.dtype == torch.float32 and x.ndim == 3 and lstm.num_layers >= 2
+        and lstm.dropout == 0 and lstm.hidden_size in (64, 128) and lstm.batch_first and lstm.bias
+        and not lstm.bidirectional and lstm.proj_size == 0 and x.shape[2] == lstm.input_size
+        and (lstm.hidden_size in (64, 128) and 1 <= lstm.input_size <= 16) and lstm.hidden_size in (64, 128)
+    )
+    return wide, narrow, stack
+
+
+def test_family_matches_the_three_predicates_it_replaced(families, monkeypatch):
+    """Every clause of the old predicates flipped, every answer reached, ``ENABLED`` off as well; and the lean rollout's
+    ``available`` says yes exactly for the one-layer families. The classifier reads a module's attributes, never its
+    weights, so ONE module (inside one default model, for ``available``) has its attributes set row by row."""
+    from rl8_amd import models_recurrent
+    from rl8_amd.algorithms._recurrent import _LeanRollout
+    from rl8_amd.distributions import Categorical
+    from rl8_amd.env import DiscreteDummyEnv
+    from rl8_amd.specs import Categorical as CategoricalSpec, Unbounded
+
+    ns = types.SimpleNamespace
+    model = models_recurrent.DefaultDiscreteRecurrentModel(
+        Unbounded(shape=torch.Size([1]), device="cpu"), CategoricalSpec(2, shape=torch.Size([1]), device="cpu"), hidden_size=8)
+    lstm = model.lstm
+    algo = ns(policy=ns(model=model, distribution_cls=Categorical), _tm={DataKeys.OBS: torch.zeros(2, 1, 1)},
+              env=object.__new__(DiscreteDummyEnv))  # (a DummyEnv, which `available` type-checks; nothing of it is run)
+    # x as the input check sees it: device, dtype, rank, and a last extent that is input_size or one more
+    inputs = list(itertools.product((True, False), (torch.float32, torch.float16), (3, 2), (0, 1)))
+    seen, rows = set(), 0
+    for enabled, hidden, layers, d_in, bias, batch_first, bidirectional, proj, dropout in itertools.product(
+            (True, False), (32, 64, 96, 128, 256), (1, 2, 3), range(1, 18), (True, False), (True, False), (False, True),
+            (0, 16), (0.0, 0.5)):
+        monkeypatch.setattr(fused_lstm, "ENABLED", enabled)
+        lstm.hidden_size, lstm.num_layers, lstm.input_size, lstm.bias = hidden, layers, d_in, bias
+        lstm.batch_first, lstm.bidirectional, lstm.proj_size, lstm.dropout = batch_first, bidirectional, proj, dropout
+        family = fused_lstm._family(lstm)
+        assert _LeanRollout.available(algo) == (family in ("256", "narrow")), vars(lstm)
+        for is_cuda, dtype, ndim, wider in inputs:
+            x = ns(is_cuda=is_cuda, dtype=dtype, ndim=ndim, shape=(4, 3, d_in + wider)[:ndim] + (0,) * (3 - ndim))
+            wide, narrow, stack = old = _families_by_predicate(enabled, lstm, x)
+            assert sum(old) <= 1  # (so the order the old call sites asked them in carried no behaviour)
+            want = "256" if wide else "narrow" if narrow else "stack" if stack else None
+            got = family if fused_lstm._input_ok(lstm, x) else None
+            assert got == want == fused_lstm._family_for(lstm, x), (enabled, vars(lstm), vars(x))
+            seen.add(got)
+            rows += 1
+    assert seen == {None, "256", "narrow", "stack"} and rows >= 40320
