@@ -187,6 +187,10 @@ class Algorithm:
 
     def __init__(self, env_cls: EnvFactory, /, config: None | AlgorithmConfig = None) -> None:
         config = config or AlgorithmConfig()
+        # step()'s caches, the rollout record, the record rows of the minibatch in hand: set before any hook can read them
+        self._flat_full = self._packed = self._views_all = None
+        self._record: None | fused_mlp.RolloutRecord = None
+        self._batch_rows: None | slice | torch.Tensor = None  # (None: none; a slice of the flat full batch; sample ids)
         device = _resolve_device(config.device)
         self.shards = EnvShards()
         max_num_envs = env_cls.max_num_envs if hasattr(env_cls, "max_num_envs") else config.num_envs
@@ -271,9 +275,6 @@ class Algorithm:
         #: still see the rollout's weights -- iteration 0 up to the first optimizer step -- start from it instead
         #: of running the forward kernels again on the same rows (``fused_mlp.RolloutRecord``; bit-identical).
         self.reuse_rollout_forward = os.environ.get("RL8_AMD_REUSE_ROLLOUT", "1") != "0"
-        self._record: None | fused_mlp.RolloutRecord = None
-        self._record_obs_version = -1
-        self._batch_rows: None | tuple[str, None | torch.Tensor] = None
         #: Parity hooks: noise / permutations recorded from a reference run.
         self.injected_noise: None | torch.Tensor = None  # [H, N, ...]
         self.injected_permutations: None | list[torch.Tensor] = None
@@ -344,12 +345,9 @@ class Algorithm:
 
     def _release_step_caches(self) -> None:
         """What was kept for the SGD iterations of the step() that is ending (subclasses add theirs)."""
-        from ..nn import fused_mlp
-
         fused_mlp._TRUSTED_PAIRS.clear()  # (a loss gradient nobody ran a backward on)
-        record = getattr(self, "_record", None)
-        if record is not None and record.towers:  # (ADVICE r4: the 1-KiB-per-row slabs go first when memory is short)
-            record.release_if_tight(self._tm[DataKeys.LOGP].device)
+        if self._record is not None and self._record.towers:  # (ADVICE r4: the 1-KiB-per-row slabs go first when memory is short)
+            self._record.release_if_tight(self._tm[DataKeys.LOGP].device)
 
     def _reset_buffer(self) -> None:
         """``buffer_spec.zero(...)`` then ``obs[:, -1] = final_obs`` (and the final
@@ -459,8 +457,7 @@ class Algorithm:
 
             fused = self._fusable()
             gamma = float(torch.tensor(hp.gamma, dtype=torch.float32))
-            record = self._rollout_record() if fused else None
-            self._record_obs_version = -1
+            record = self._rollout_record(fused)
             dist_cls = self.policy.distribution_cls
             pair = (fused_mlp.expect_pair_gradients() if record is not None and issubclass(dist_cls, Categorical)
                     else contextlib.nullcontext())
@@ -496,19 +493,21 @@ class Algorithm:
             self.state.reward_scale = reward_scale if hp.normalize_rewards else 1.0
             self.injected_noise = None
             if record is not None:  # (a Python-level write to the observations before step() voids the record)
-                self._record_obs_version = tm[DataKeys.OBS]._version
+                record.seal(tm[DataKeys.OBS])
 
         collect_stats["env/resets"] = hp.num_envs * int(env_was_reset)
         collect_stats["env/steps"] = hp.num_envs * hp.horizon
         collect_stats["profiling/collect_ms"] = collect_timer()
         return collect_stats
 
-    def _rollout_record(self) -> None | fused_mlp.RolloutRecord:
+    def _rollout_record(self, fused: bool) -> None | fused_mlp.RolloutRecord:
         """The record this ``collect()`` fills (made once, its slabs reused by every rollout), or ``None``."""
-        if not self.reuse_rollout_forward or not has_fused_loss(self.policy.distribution_cls):
+        rec = self._record
+        if not fused or not self.reuse_rollout_forward or not has_fused_loss(self.policy.distribution_cls):
+            if rec is not None:  # (what an earlier rollout recorded is not this one's: step() must not replay it)
+                rec.unseal()
             return None
         hp = self.hparams
-        rec = self._record
         if rec is None or (rec.steps, rec.rows_per_step) != (hp.horizon, self.local_num_envs):
             rec = self._record = fused_mlp.RolloutRecord(hp.horizon, self.local_num_envs, keep_general=False)
         # heads that need h2 (1 KiB per row) are recorded only when every row is read back: one optimizer step per
@@ -745,22 +744,22 @@ class Algorithm:
             # Time-major storage: dropping the last column and flattening is the
             # contiguous prefix -- no copy, no shuffle (a mean over the whole
             # buffer does not depend on order).
-            if getattr(self, "_flat_full", None) is None:
+            if self._flat_full is None:
                 self._flat_full = {
                     k: tm[k][:H].reshape(local_samples, *tm[k].shape[2:]) for k in self.TRAIN_KEYS
                 }
-            self._batch_rows = ("all", None)
+            self._batch_rows = slice(0, local_samples)
             yield self._flat_full
             return
         local_mb = hp.sgd_minibatch_size // self.shards.world_size
         perm = self._permutation(sgd_iter, local_samples)
-        if getattr(self, "_packed", None) is None:
+        if self._packed is None:
             # the buffer is shuffled num_sgd_iters x num_minibatches times: lay each
             # sample's fields side by side once, then every gather reads one row
             self._packed = hip.PackedSamples(H, [self.buffer[k] for k in self.TRAIN_KEYS])
         for index in torch.split(perm, local_mb):
             index = index.contiguous()
-            self._batch_rows = ("index", index)
+            self._batch_rows = index
             yield dict(zip(self.TRAIN_KEYS, self._packed.gather(index)))
 
     def _iter_view_minibatches(self, sgd_iter: int):
@@ -771,7 +770,7 @@ class Algorithm:
         hp = self.hparams
         H = hp.horizon
         local_samples = self.local_num_envs * H
-        if getattr(self, "_views_all", None) is None:
+        if self._views_all is None:
             views = self.policy.model.apply_view_requirements(self.buffer[:, :-1, ...], kind="all")
             if views.batch_size[0] != local_samples:
                 raise ValueError(
@@ -807,22 +806,15 @@ class Algorithm:
             scale = self.grad_scaler.scale(torch.ones((), device=batch[DataKeys.LOGP].device))
         # Rows the rollout already took through the towers with the weights they still have (iteration 0, before the
         # first optimizer step): start from the record instead of launching the forward again.
-        recorded: None | dict[int, tuple] = None
-        rec, batch_rows = getattr(self, "_record", None), getattr(self, "_batch_rows", None)
-        if (rec is not None and batch_rows is not None and DataKeys.OBS in batch
-                and self._record_obs_version == self._tm[DataKeys.OBS]._version and rec.valid()):
-            obs_tm = self._tm[DataKeys.OBS]
-            rec.require_inputs(obs_tm.data_ptr(), obs_tm.stride(0) * obs_tm.element_size())
-        if (rec is not None and batch_rows is not None and DataKeys.OBS in batch
-                and self._record_obs_version == self._tm[DataKeys.OBS]._version and rec.valid()):
-            recorded = rec.rows(0, rows) if batch_rows[0] == "all" else rec.gather(batch_rows[1])
+        recorded = None
+        if self._record is not None and self._batch_rows is not None and DataKeys.OBS in batch:
+            recorded = self._record.rows_for(self._tm[DataKeys.OBS], self._batch_rows)
         for start in range(0, rows, self.max_rows_per_pass):
             stop = min(rows, start + self.max_rows_per_pass)
             chunk = {k: v[start:stop] for k, v in batch.items()}
             n = stop - start
-            replayed = contextlib.nullcontext() if not recorded else fused_mlp.replay(
-                {k: (key, *[None if t is None else t[start:stop] for t in rest]) for k, (key, *rest) in recorded.items()},
-                chunk[DataKeys.OBS])
+            replayed = contextlib.nullcontext() if recorded is None else fused_mlp.replay(
+                {k: r.slice(start, stop) for k, r in recorded.items()}, chunk[DataKeys.OBS])
             # A two-way Categorical under the fused loss: rl8_ppo_loss_categorical_fwd_bwd_f32 emits logit gradients
             # that are exact negatives of each other, so the policy tower may keep only the gate bits of h2 from the
             # first SGD iteration on (fused_mlp.expect_pair_gradients; still checked on the device in the backward).

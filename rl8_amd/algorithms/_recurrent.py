@@ -431,7 +431,7 @@ class RecurrentAlgorithm(Algorithm):
             from ..nn import fused_lstm
 
             fused_lstm.SHARE_H0_PLANES = True  # until _release_step_caches(): every pass reads the same initial states
-        if whole and getattr(self, "_flat_full", None) is not None:
+        if whole and self._flat_full is not None:
             yield self._flat_full
             return
         # One minibatch that is the whole buffer: its mean does not depend on the order of the sequences (the

@@ -892,18 +892,25 @@ def mlp_pack_w2(w2: torch.Tensor, *, transposed: bool = False) -> torch.Tensor:
     return packed
 
 
-def mlp_tower_forward(
-    x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2_packed: torch.Tensor, b2: torch.Tensor,
-    w3: torch.Tensor, b3: torch.Tensor, *, save: bool = False,
-) -> tuple[torch.Tensor, None | torch.Tensor, None | torch.Tensor]:
-    """x [M, d_in] -> out [M, n_out]; with ``save`` also the post-ReLU activations
-    h1, h2 ([M, 256]) for the backward pass."""
+def _tower_shapes(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                  b3: torch.Tensor) -> tuple[torch.Tensor, int, int, int]:
+    """(dense x, M, d_in, n_out) of a width-256 tower call whose parameters have the shapes that go with them."""
     x = _dense(x.detach(), torch.float32, "x")
     m, d_in = x.shape
     n_out = w3.shape[0]
     for name, t, shape in (("w1", w1, (MLP_HIDDEN, d_in)), ("b1", b1, (MLP_HIDDEN,)), ("b2", b2, (MLP_HIDDEN,)),
                            ("w3", w3, (n_out, MLP_HIDDEN)), ("b3", b3, (n_out,))):
         _shaped(t, shape, name)
+    return x, m, d_in, n_out
+
+
+def mlp_tower_forward(
+    x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2_packed: torch.Tensor, b2: torch.Tensor,
+    w3: torch.Tensor, b3: torch.Tensor, *, save: bool = False,
+) -> tuple[torch.Tensor, None | torch.Tensor, None | torch.Tensor]:
+    """x [M, d_in] -> out [M, n_out]; with ``save`` also the post-ReLU activations
+    h1, h2 ([M, 256]) for the backward pass."""
+    x, m, d_in, n_out = _tower_shapes(x, w1, b1, b2, w3, b3)
     if w2_packed.numel() != MLP_HIDDEN * MLP_HIDDEN:
         raise ValueError("w2_packed must come from mlp_pack_w2")
     out = torch.empty(m, n_out, dtype=torch.float32, device=x.device)
@@ -977,16 +984,9 @@ def mlp_tower_forward_split(
     ``out`` / ``h2_out`` / ``gate_out``: caller-owned dense destinations ([M, n_out] fp32, [M, 256] fp32,
     [M, 8] int32) instead of fresh tensors -- the rollout writes each timestep's rows straight into the slabs the
     first SGD pass reads back (``fused_mlp.RolloutRecord``)."""
-    x = _dense(x.detach(), torch.float32, "x")
-    m, d_in = x.shape
-    n_out = w3.shape[0]
-    for name, t, shape in (("w1", w1, (MLP_HIDDEN, d_in)), ("b1", b1, (MLP_HIDDEN,)), ("b2", b2, (MLP_HIDDEN,)),
-                           ("w3", w3, (n_out, MLP_HIDDEN)), ("b3", b3, (n_out,))):
-        _shaped(t, shape, name)
+    x, m, d_in, n_out = _tower_shapes(x, w1, b1, b2, w3, b3)
     lib = load()
-    if w2_split.dtype == torch.uint8 and w2_split.numel() == int(lib.rl8_mlp_f16_packed_bytes()):
-        fn, fn_name = lib.rl8_mlp_tower_forward_f16_f32, "rl8_mlp_tower_forward_f16_f32"  # fp16 two-plane pack
-    else:
+    if w2_split.dtype != torch.uint8 or w2_split.numel() != int(lib.rl8_mlp_f16_packed_bytes()):  # fp16 two-plane pack
         raise ValueError("w2_split must come from mlp_pack_w2_f16")
     for name, t, dtype, shape in (("out", out, torch.float32, (m, n_out)), ("h2_out", h2_out, torch.float32, (m, MLP_HIDDEN)),
                                   ("gate_out", gate_out, torch.int32, (m, 8))):
@@ -1005,11 +1005,11 @@ def mlp_tower_forward_split(
         if save and save_gate else None
     with _timed(timer_name or ("mlp_tower_forward_save" if save else "mlp_tower_forward"), m):
         _check(
-            fn(
+            lib.rl8_mlp_tower_forward_f16_f32(
                 _ptr(x), m, d_in, _ptr(w1.detach()), _ptr(b1.detach()), _ptr(w2_split), _ptr(b2.detach()),
                 _ptr(w3.detach()), _ptr(b3.detach()), n_out, _ptr(out), _ptr(h1), _ptr(h2), _ptr(gate), _stream(),
             ),
-            fn_name,
+            "rl8_mlp_tower_forward_f16_f32",
         )
     return (out, h1, h2, gate) if save_gate else (out, h1, h2)
 
@@ -1152,28 +1152,28 @@ def mlp_tower_backward(
     return grads
 
 
-_pair_flags: dict[tuple[int, int], torch.Tensor] = {}
-
-
-def _pair_flag(device: torch.device) -> torch.Tensor:
+def _per_stream(cache: dict[tuple[int, int], torch.Tensor], device: torch.device, make) -> torch.Tensor:
+    """``cache``'s tensor for (``device``, the current stream): ``make()`` on first use."""
     key = (device.index if device.index is not None else torch.cuda.current_device(), _stream())
-    flag = _pair_flags.get(key)
-    if flag is None:
-        flag = _pair_flags[key] = torch.zeros(4, dtype=torch.int32, device=device)
-    return flag
+    if key not in cache:
+        cache[key] = make()
+    return cache[key]
 
 
+_pair_flags: dict[tuple[int, int], torch.Tensor] = {}
 _wgrad_ws: dict[tuple[int, int], torch.Tensor] = {}
 
 
+def _pair_flag(device: torch.device) -> torch.Tensor:
+    return _per_stream(_pair_flags, device, lambda: torch.zeros(4, dtype=torch.int32, device=device))
+
+
 def _wgrad_workspace(device: torch.device) -> torch.Tensor:
-    key = (device.index if device.index is not None else torch.cuda.current_device(), _stream())
-    ws = _wgrad_ws.get(key)
-    if ws is None:
+    def make() -> torch.Tensor:
         ws = torch.empty(int(load().rl8_mlp_wgrad_workspace_bytes()) // 4, dtype=torch.float32, device=device)
         ws[-64:].zero_()  # (the guard's lifetime counters live there: include/rl8_amd.h, rl8_mlp_wgrad_workspace_bytes)
-        _wgrad_ws[key] = ws
-    return ws
+        return ws
+    return _per_stream(_wgrad_ws, device, make)
 
 
 def wgrad_guard_counts() -> tuple[int, int]:

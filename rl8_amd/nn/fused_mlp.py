@@ -26,6 +26,7 @@ config), whose casts and elementwise launches dominate at this width.
 
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import functools
 import os
@@ -279,6 +280,24 @@ RECORD_H2_BUDGET_BYTES = _record_h2_budget_bytes()
 RECORD_H2_KEEP_FREE_BYTES = 8 << 30
 
 
+def _param_key(params) -> tuple:
+    """What identifies the values of ``params``: version counters (in-place changes) and addresses (replacement)."""
+    return tuple((p._version, p.data_ptr()) for p in params)
+
+
+@dataclasses.dataclass(frozen=True)
+class _RecordedRows:
+    """One tower's part of a replay: the parameter key of its rows, their outputs, gate bits and h2 (if recorded)."""
+    key: tuple
+    out: torch.Tensor
+    gate: torch.Tensor
+    h2: None | torch.Tensor
+
+    def slice(self, start: int, stop: int) -> "_RecordedRows":
+        return _RecordedRows(self.key, self.out[start:stop], self.gate[start:stop],
+                             None if self.h2 is None else self.h2[start:stop])
+
+
 class _TowerRecord:
     def __init__(self, params: list[torch.Tensor], n_out: int, gate_only: bool, rows: int, device) -> None:
         self.params = params
@@ -286,23 +305,26 @@ class _TowerRecord:
         self.out = torch.empty(rows, n_out, dtype=torch.float32, device=device)
         self.gate = torch.empty(rows, 8, dtype=torch.int32, device=device)
         self.h2 = None if gate_only else torch.empty(rows, hip.MLP_HIDDEN, dtype=torch.float32, device=device)
-        self.key: None | tuple = None
         self.seen: set[int] = set()
         #: address of the input each recorded timestep was evaluated on; a second evaluation of the same tower inside
         #: one ``record.at(t)`` (a model that runs it on obs AND next_obs) spoils the timestep: never replayed
         self.inputs: dict[int, int] = {}
-        self.spoiled = False
+        self.reset(None)
+
+    def reset(self, key: None | tuple) -> None:
+        """Nothing recorded yet, for the parameters ``key`` names (``None``: a rollout that has not reached it)."""
+        self.key, self.spoiled = key, False
+        self.seen.clear()
+        self.inputs.clear()
 
     def current_key(self) -> tuple:
-        return tuple((p._version, p.data_ptr()) for p in self.params)
-
-    def leaves(self) -> list[torch.Tensor]:
-        return [t for t in (self.out, self.gate, self.h2) if t is not None]
+        return _param_key(self.params)
 
 
 class RolloutRecord:
     """Outputs, gate bits (and h2 where needed) of the towers for the ``steps x rows_per_step`` observations of one
-    rollout, in time-major row order. ``at(t)`` is the context ``collect()`` evaluates timestep ``t`` in."""
+    rollout, in time-major row order. ``at(t)`` is the context ``collect()`` evaluates timestep ``t`` in (``record``
+    takes the tower calls made inside it), ``seal`` ends the rollout, ``rows_for`` is all a training pass asks."""
 
     def __init__(self, steps: int, rows_per_step: int, *, keep_general: bool) -> None:
         self.steps, self.rows_per_step = steps, rows_per_step
@@ -310,19 +332,29 @@ class RolloutRecord:
         self.towers: dict[int, _TowerRecord] = {}
         self.t = -1
         self.refused: set[int] = set()
+        self._sealed: None | int = None  # version counter of the observations a finished rollout was recorded on
 
     def begin(self) -> None:
+        self.unseal()
         for tr in self.towers.values():
-            tr.seen.clear()
-            tr.inputs.clear()
-            tr.spoiled = False
-            tr.key = None
+            tr.reset(None)
 
-    def at(self, t: int) -> "_Recording":
-        return _Recording(self, t)
+    def seal(self, obs_tm: torch.Tensor) -> None:
+        """End of the rollout that filled the record from the time-major observations ``obs_tm``."""
+        self._sealed = obs_tm._version
 
-    def bytes(self) -> int:
-        return sum(t.numel() * t.element_size() for tr in self.towers.values() for t in tr.leaves())
+    def unseal(self) -> None:
+        """Nothing is replayed until the next ``seal``: a new rollout has begun, recording or not."""
+        self._sealed = None
+
+    @contextlib.contextmanager
+    def at(self, t: int):
+        global _RECORDING
+        before, _RECORDING, self.t = _RECORDING, self, t
+        try:
+            yield self
+        finally:
+            _RECORDING = before
 
     def _tower(self, layer2: nn.Linear, params: list[torch.Tensor], n_out: int, gate_only: bool, device) -> None | _TowerRecord:
         tr = self.towers.get(id(layer2))
@@ -348,6 +380,31 @@ class RolloutRecord:
             return None
         return tr
 
+    def record(self, l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear], w3: torch.Tensor, b3: torch.Tensor,
+               plan: _TowerPlan, x: torch.Tensor) -> None | torch.Tensor:
+        """Timestep ``self.t`` of the tower, evaluated in the training forward's save mode straight into its slabs:
+        the output, or ``None`` where nothing was recorded (the caller then runs the tower as usual)."""
+        if not plan.recordable or x.shape[0] != self.rows_per_step:
+            return None
+        tr = self._tower(l2, _tower_params(l1, l2, heads), w3.shape[0], plan.gate_only, x.device)
+        if tr is None:
+            return None
+        key = tr.current_key()
+        if tr.key != key:
+            tr.reset(key)
+        if self.t in tr.seen:  # second evaluation in this timestep's context: the slab rows of t would be overwritten
+            tr.spoiled = True
+            return None
+        tr.inputs[self.t] = x.data_ptr()
+        sl = slice(self.t * self.rows_per_step, (self.t + 1) * self.rows_per_step)
+        out = hip.mlp_tower_forward_split(
+            x.contiguous(), l1.weight, l1.bias, _packed(l2, False, True), l2.bias, w3, b3, save=True,
+            save_h1=False, save_gate=True, save_h2=not plan.gate_only, out=tr.out[sl], gate_out=tr.gate[sl],
+            h2_out=None if plan.gate_only else tr.h2[sl], timer_name="mlp_tower_forward_record")[0]
+        tr.seen.add(self.t)
+        replay_stats["recorded_rows"] += self.rows_per_step
+        return out
+
     def release_if_tight(self, device) -> int:
         """End of a ``step()``: give the h2 slabs back (and refuse new ones) when the device is short of memory --
         activations and workspaces allocated by ``step()`` come after the slabs and must not be what runs out.  Returns
@@ -365,10 +422,10 @@ class RolloutRecord:
             self.refused.add(key)
         return released
 
-    def _usable(self, tr: _TowerRecord) -> bool:
-        """The tower saw all the timesteps, once each, with the parameters it has now."""
-        return (tr.key is not None and not tr.spoiled and len(tr.seen) == self.steps
-                and tr.current_key() == tr.key)
+    def _usable(self) -> list[tuple[int, _TowerRecord]]:
+        """The towers that saw all the timesteps, once each, with the parameters they have now."""
+        return [(k, tr) for k, tr in self.towers.items()
+                if tr.key is not None and not tr.spoiled and len(tr.seen) == self.steps and tr.current_key() == tr.key]
 
     def require_inputs(self, base_ptr: int, step_bytes: int) -> None:
         """The caller replays the record against the rows of ONE dense array (the time-major observations, timestep t
@@ -380,65 +437,63 @@ class RolloutRecord:
 
     def valid(self) -> bool:
         """Some recorded tower can still be replayed."""
-        return any(self._usable(tr) for tr in self.towers.values())
+        return bool(self._usable())
 
-    def rows(self, start: int, stop: int) -> dict[int, tuple]:
+    def rows(self, start: int, stop: int) -> dict[int, _RecordedRows]:
         """Record rows ``[start, stop)`` (time-major order) of every usable tower."""
-        return {k: (tr.key, tr.out[start:stop], tr.gate[start:stop], tr.h2[start:stop] if tr.h2 is not None else None)
-                for k, tr in self.towers.items() if self._usable(tr)}
+        return {k: _RecordedRows(tr.key, tr.out, tr.gate, tr.h2).slice(start, stop) for k, tr in self._usable()}
 
-    def gather(self, index: torch.Tensor) -> dict[int, tuple]:
+    def gather(self, index: torch.Tensor) -> dict[int, _RecordedRows]:
         """The same for the samples ``index`` names (reference sample ids ``env * H + t``): one strided gather per
         tower (``rl8_gather_minibatch``) out of the ``[H][N]`` slabs seen as ``[N, H, ...]`` leaves."""
         H, N = self.steps, self.rows_per_step
-        got: dict[int, tuple] = {}
-        for k, tr in self.towers.items():
-            if not self._usable(tr):
-                continue
-            leaves = [t.view(H, N, t.shape[1]).transpose(0, 1) for t in tr.leaves()]
+        got: dict[int, _RecordedRows] = {}
+        for k, tr in self._usable():
+            leaves = [t.view(H, N, t.shape[1]).transpose(0, 1) for t in (tr.out, tr.gate, tr.h2) if t is not None]
             dense = hip.gather_minibatch(index, H, leaves)
-            got[k] = (tr.key, dense[0], dense[1], dense[2] if tr.h2 is not None else None)
+            got[k] = _RecordedRows(tr.key, dense[0], dense[1], dense[2] if tr.h2 is not None else None)
         return got
+
+    def rows_for(self, obs_tm: torch.Tensor, which: slice | torch.Tensor) -> None | dict[int, _RecordedRows]:
+        """The recorded rows of a training batch out of ``obs_tm`` (``which``: a ``slice`` of its flat time-major rows, or
+        sample ids for ``gather``); ``None``: no sealed rollout, observations written to since, or no tower left usable."""
+        if self._sealed != obs_tm._version or not self.valid():
+            return None
+        self.require_inputs(obs_tm.data_ptr(), obs_tm.stride(0) * obs_tm.element_size())
+        return (self.rows(which.start, which.stop) if isinstance(which, slice) else self.gather(which)) or None
 
 
 _RECORDING: None | RolloutRecord = None
-_REPLAY: None | tuple[dict[int, tuple], torch.Tensor] = None
-
-
-class _Recording:
-    def __init__(self, record: RolloutRecord, t: int) -> None:
-        self.record, self.t = record, t
-
-    def __enter__(self):
-        global _RECORDING
-        self._before = _RECORDING
-        self.record.t = self.t
-        _RECORDING = self.record
-        return self.record
-
-    def __exit__(self, *exc):
-        global _RECORDING
-        _RECORDING = self._before
-        return False
+_REPLAY: None | "replay" = None
 
 
 class replay:
     """Context for a grad-enabled pass over ``x`` (a dense ``[m, d]`` tensor): towers found in ``rows`` (from
-    ``RolloutRecord.rows`` / ``.gather``) whose parameters are still the recorded ones skip their forward launch."""
+    ``RolloutRecord.rows_for``) whose parameters are still the recorded ones skip their forward launch."""
 
-    def __init__(self, rows: dict[int, tuple], x: torch.Tensor) -> None:
+    def __init__(self, rows: dict[int, _RecordedRows], x: torch.Tensor) -> None:
         self.rows, self.x = rows, x
 
     def __enter__(self):
         global _REPLAY
         self._before = _REPLAY
-        _REPLAY = (self.rows, self.x)
+        _REPLAY = self
         return self
 
     def __exit__(self, *exc):
         global _REPLAY
         _REPLAY = self._before
         return False
+
+    def hit(self, l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear], x: torch.Tensor, n_out: int,
+            plan: _TowerPlan) -> None | _RecordedRows:
+        """The recorded rows that stand for this tower call (the context's own ``x``, the recorded parameters), or ``None``."""
+        got = self.rows.get(id(l2))
+        ok = (got is not None and x.data_ptr() == self.x.data_ptr() and x.shape == self.x.shape and x.is_contiguous()
+              and got.key == _param_key(_tower_params(l1, l2, heads))
+              and got.out.shape == (x.shape[0], n_out)
+              and (got.h2 is not None or plan.gate_only))  # (a record without h2 serves rank-one calls)
+        return got if ok else None
 
 
 #: Counts for tests / the bench line: towers evaluated from the record, rows recorded.
@@ -466,31 +521,10 @@ def _tower_params(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear]) -> l
     return [l1.weight, l1.bias, l2.weight, l2.bias, *[h.weight for h in heads], *[h.bias for h in heads]]
 
 
-def _match(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[nn.Linear, nn.Linear]:
-    """(layer1, layer2) if ``trunk`` is ``Sequential(MLP(Linear, ReLU, Linear), ReLU)``
-    (optionally followed by the single head) with 256-wide biased layers."""
-    if not isinstance(trunk, nn.Sequential) or len(trunk) < 2:
-        return None
-    mlp, act = trunk[0], trunk[1]
-    if not isinstance(mlp, nn.Sequential) or len(mlp) != 3 or not isinstance(act, nn.ReLU):
-        return None
-    l1, a1, l2 = mlp[0], mlp[1], mlp[2]
-    if not (isinstance(l1, nn.Linear) and isinstance(a1, nn.ReLU) and isinstance(l2, nn.Linear)):
-        return None
-    if l1.out_features != hip.MLP_HIDDEN or l2.out_features != hip.MLP_HIDDEN or l2.in_features != hip.MLP_HIDDEN:
-        return None
-    if l1.in_features > hip.MLP_MAX_IN or l1.bias is None or l2.bias is None:
-        return None
-    if sum(h.out_features for h in heads) > hip.MLP_MAX_OUT or any(h.bias is None for h in heads):
-        return None
-    if any(h.in_features != hip.MLP_HIDDEN for h in heads):
-        return None
-    return l1, l2
-
-
-def _match_narrow(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[nn.Linear, nn.Linear]:
-    """(layer1, layer2) if ``trunk`` is ``Sequential(MLP(Linear, ReLU, Linear), ReLU)`` with biased layers of one
-    width in ``hip.MLP_NARROW_HIDDEN`` and heads that read that width (``mlp_narrow_kernels.hip``)."""
+def _family(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[str, nn.Linear, nn.Linear]:
+    """The one place the module structure is inspected: (family, layer1, layer2) if ``trunk`` is
+    ``Sequential(MLP(Linear, ReLU, Linear), ReLU)`` with biased layers of one width and biased heads (one at least) that
+    read it -- "wide": 256, "narrow": a width in ``hip.MLP_NARROW_HIDDEN`` (``mlp_narrow_kernels.hip``) -- else ``None``."""
     if not isinstance(trunk, nn.Sequential) or len(trunk) < 2:
         return None
     mlp, act = trunk[0], trunk[1]
@@ -500,7 +534,8 @@ def _match_narrow(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[
     if not (isinstance(l1, nn.Linear) and isinstance(a1, nn.ReLU) and isinstance(l2, nn.Linear)):
         return None
     width = l1.out_features
-    if width not in hip.MLP_NARROW_HIDDEN or l2.in_features != width or l2.out_features != width:
+    family = "narrow" if width in hip.MLP_NARROW_HIDDEN else "wide" if width == hip.MLP_HIDDEN else None
+    if family is None or l2.in_features != width or l2.out_features != width:
         return None
     if l1.in_features > hip.MLP_MAX_IN or l1.bias is None or l2.bias is None:
         return None
@@ -508,7 +543,7 @@ def _match_narrow(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[
         return None
     if any(h.in_features != width for h in heads):
         return None
-    return l1, l2
+    return family, l1, l2
 
 
 class _NarrowTower(torch.autograd.Function):
@@ -539,66 +574,36 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
     ``Algorithm``). Checked on the device in the backward either way."""
     if not ENABLED or not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
         return None
-    narrow = _match_narrow(trunk, heads)
-    if narrow is not None:  # (never recorded or replayed: everything below assumes width 256)
-        l1, l2 = narrow
-        if x.shape[1] != l1.in_features:
-            return None
-        w3 = heads[0].weight if len(heads) == 1 else torch.cat([h.weight for h in heads], 0)
-        b3 = heads[0].bias if len(heads) == 1 else torch.cat([h.bias for h in heads], 0)
-        return _NarrowTower.apply(x.contiguous(), l1.weight, l1.bias, l2.weight, l2.bias, w3, b3)
-    layers = _match(trunk, heads)
-    if layers is None or x.shape[1] != layers[0].in_features:
+    found = _family(trunk, heads)
+    if found is None or x.shape[1] != found[1].in_features:
         return None
-    l1, l2 = layers
-    if piecewise_mlp.ENABLED and x.shape[1] == 1:  # opt-in prototype: scalar observations from an exact piecewise-linear table
+    family, l1, l2 = found
+    # opt-in prototype: scalar observations from an exact piecewise-linear table
+    if family == "wide" and piecewise_mlp.ENABLED and x.shape[1] == 1:
         out = piecewise_mlp.tower_forward(l1, l2, heads, x)
         if out is not None:
             return out
-    if len(heads) == 1:
-        w3, b3 = heads[0].weight, heads[0].bias
-    else:
-        w3 = torch.cat([h.weight for h in heads], 0)
-        b3 = torch.cat([h.bias for h in heads], 0)
+    w3 = heads[0].weight if len(heads) == 1 else torch.cat([h.weight for h in heads], 0)
+    b3 = heads[0].bias if len(heads) == 1 else torch.cat([h.bias for h in heads], 0)
+    if family == "narrow":  # (never recorded or replayed: everything below assumes width 256)
+        return _NarrowTower.apply(x.contiguous(), l1.weight, l1.bias, l2.weight, l2.bias, w3, b3)
     if pair_gradients is None:
         pair_gradients = bool(l2.__dict__.get("_rl8_rank_one", False))
-    w3_key = tuple((h.weight._version, h.weight.data_ptr()) for h in heads)
+    w3_key = _param_key(h.weight for h in heads)
     n_out = w3.shape[0]
     plan = _plan(x.shape[1], n_out, bool(pair_gradients))
-    if _RECORDING is not None and not torch.is_grad_enabled() and plan.recordable and x.shape[0] == _RECORDING.rows_per_step:
-        rec = _RECORDING
-        params = _tower_params(l1, l2, heads)
-        tr = rec._tower(l2, params, n_out, plan.gate_only, x.device)
-        if tr is not None:
-            key = tr.current_key()
-            if tr.key != key:
-                tr.key, tr.seen = key, set()
-                tr.inputs.clear()
-                tr.spoiled = False
-            if rec.t in tr.seen:  # second evaluation in this timestep's context: the slab rows of t would be overwritten
-                tr.spoiled = True
-                return _FusedTower.apply(x.contiguous(), l1.weight, l1.bias, l2.weight, l2.bias, w3, b3, l2,
-                                         torch.is_grad_enabled(), plan, w3_key)
-            tr.inputs[rec.t] = x.data_ptr()
-            lo = rec.t * rec.rows_per_step
-            sl = slice(lo, lo + rec.rows_per_step)
-            out = hip.mlp_tower_forward_split(
-                x.contiguous(), l1.weight, l1.bias, _packed(l2, False, True), l2.bias, w3, b3, save=True,
-                save_h1=False, save_gate=True, save_h2=not plan.gate_only, out=tr.out[sl], gate_out=tr.gate[sl],
-                h2_out=None if plan.gate_only else tr.h2[sl], timer_name="mlp_tower_forward_record")[0]
-            tr.seen.add(rec.t)
-            replay_stats["recorded_rows"] += rec.rows_per_step
+    if _RECORDING is not None and not torch.is_grad_enabled():
+        # (``None``: refused a slab, or a second evaluation at this timestep.  Falling through is the plain launch
+        # below: the replay branch needs grad mode on, and recording needs it off.)
+        out = _RECORDING.record(l1, l2, heads, w3, b3, plan, x)
+        if out is not None:
             return out
     if _REPLAY is not None and torch.is_grad_enabled() and plan.recordable:
-        rows, expect = _REPLAY
-        hit = rows.get(id(l2))
-        if (hit is not None and x.data_ptr() == expect.data_ptr() and x.shape == expect.shape and x.is_contiguous()
-                and hit[0] == tuple((p._version, p.data_ptr()) for p in _tower_params(l1, l2, heads))
-                and hit[1].shape == (x.shape[0], n_out)
-                and (hit[3] is not None or plan.gate_only)):  # (a record without h2 serves rank-one calls)
+        got = _REPLAY.hit(l1, l2, heads, x, n_out, plan)
+        if got is not None:
             replay_stats["replayed_towers"] += 1
             replay_stats["replayed_rows"] += x.shape[0]
             return _ReplayedTower.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, w3, b3, l2, plan, w3_key,
-                                        hit[1], hit[2], hit[3])
+                                        got.out, got.gate, got.h2)
     return _FusedTower.apply(x.contiguous(), l1.weight, l1.bias, l2.weight, l2.bias, w3, b3, l2,
                              torch.is_grad_enabled(), plan, w3_key)
