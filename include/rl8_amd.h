@@ -28,7 +28,8 @@
  *     rollout    rl8_rollout_step_{dummy,cartpole,mountain_car,pendulum}_f32, rl8_rollout_step_dummy_heads_f32,
  *                rl8_rollout_scatter_f32 (user envs), rl8_rollout_stats_f32, rl8_*_reset_f32, rl8_*_step_f32 (Env.step()
  *                called by the user), rl8_categorical_sample_logp_f32, rl8_normal_sample_logp_f32 (Distribution.sample())
- *     update     rl8_gae_scan_f32, rl8_advantage_normalise_f32, rl8_ppo_loss_{categorical,normal}_fwd_bwd_f32,
+ *     update     rl8_gae_scan_f32, rl8_advantage_normalise_f32 (their routes: rl8_gae_plan, rl8_advantage_normalise_route),
+ *                rl8_ppo_loss_{categorical,normal}_fwd_bwd_f32,
  *                rl8_pack_samples, rl8_gather_packed, rl8_gather_minibatch
  *     towers     rl8_mlp_tower_forward_f16_f32, rl8_mlp_tower_backward_gate_f16_f32, rl8_mlp_tower_backward_f16_f32,
  *                rl8_mlp_wgrad_gate_bits_f32, rl8_mlp_wgrad_fused_split_f32, rl8_mlp_wgrad_fused_pair_f32,
@@ -291,9 +292,44 @@ int rl8_gae_scan_f32(float *rewards, const float *values, float *adv_out, float 
                      void *scratch, void *stream);
 
 /* adv[:, :H] = (adv - mean) / (std + 1e-8), mean / unbiased std formed from
- * `moments` (device, 3 doubles) (:118-122). */
+ * `moments` (device, 3 doubles) (:118-122).  One sample (N H = 1): the unbiased
+ * std is 0/0 and the advantage comes back NaN, as the reference's does. */
 int rl8_advantage_normalise_f32(float *adv, int64_t n, int64_t h, int layout,
                                 const double *moments, void *stream);
+
+/* The launch plan of rl8_gae_scan_f32 for a shape, a layout and an alignment (aligned16_all != 0: all four of
+ * rewards, values, adv_out and ret_out are 16-byte aligned).  Host arithmetic only: no device is touched, and the
+ * scan launches exactly what this reports.  Routes:
+ *   TIME_VEC4      time-major, four envs per lane through 16-byte accesses (N % 4 == 0, aligned)
+ *   TIME_VEC1      time-major, one env per lane
+ *   ENV_PIPELINED  env-major, whole rows of odd H+1 <= 35 columns, aligned: tiles of 128 envs copied flat through
+ *                  LDS, the next tile's rows requested before this tile's scan; grid capped at what is resident
+ *   ENV_FLAT       env-major, whole rows of odd 37 <= H+1 <= 127 columns, aligned: flat 16-byte tile copies
+ *   ENV_CHUNKED    env-major, everything else (even H+1, H+1 > 127 in chunks of 127 columns, misaligned
+ *                  pointers): rows padded to an odd LDS stride and copied element by element
+ * envs_per_block is the workgroup size of the env-major routes (one lane per env) and lanes x envs per lane of the
+ * time-major ones; chunk, lds_stride (floats, odd) and lds_bytes (dynamic LDS of the launch) are 0 for time-major. */
+#define RL8_GAE_TIME_VEC4 0
+#define RL8_GAE_TIME_VEC1 1
+#define RL8_GAE_ENV_PIPELINED 2
+#define RL8_GAE_ENV_FLAT 3
+#define RL8_GAE_ENV_CHUNKED 4
+typedef struct {
+  int route;
+  int envs_per_block;
+  int chunk;
+  int lds_stride;
+  int64_t lds_bytes;
+  int grid;
+} rl8_gae_plan_t;
+int rl8_gae_plan(int64_t n, int64_t h, int layout, int aligned16_all, rl8_gae_plan_t *out /*host*/);
+
+/* The kernel rl8_advantage_normalise_f32 launches (host arithmetic only), or a negative error code:
+ * FLAT_VEC4 time-major with N H % 4 == 0 and adv 16-byte aligned, FLAT_VEC1 time-major otherwise, ENV_MAJOR. */
+#define RL8_NORM_FLAT_VEC4 0
+#define RL8_NORM_FLAT_VEC1 1
+#define RL8_NORM_ENV_MAJOR 2
+int rl8_advantage_normalise_route(int64_t n, int64_t h, int layout, int aligned16);
 
 /* ---------------------------------------------------------------------- *
  * a-7  ppo_losses + approximate KL, forward AND backward

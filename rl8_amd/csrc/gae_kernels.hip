@@ -386,6 +386,9 @@ __device__ __forceinline__ NormConsts norm_consts(const double *moments) {
   const double mean = s / cnt;
   double var = (sq - s * mean) / (cnt - 1.0);
   var = var > 0.0 ? var : 0.0;
+  // one sample: the unbiased variance is 0/0 and the reference's std_mean gives NaN (so NaN advantages), not a
+  // rounding residue to clamp
+  if (!(cnt > 1.0)) var = __builtin_nan("");
   NormConsts c;
   c.mean = (float)mean;
   c.sd = (float)sqrt(var) + 1e-8f;
@@ -421,81 +424,116 @@ __global__ __launch_bounds__(kBlock) void advantage_normalise_env_major_kernel(
 
 using namespace rl8;
 
+// Every launch decision of the scan, in one place: which kernel, how many envs a workgroup takes, how the H+1 columns
+// are cut into chunks, the LDS row stride and bytes, and the grid.  Host arithmetic only (no device is touched), so the
+// route table can be swept on a CPU; rl8_gae_scan_f32 launches what this says and decides nothing itself.
+RL8_API int rl8_gae_plan(int64_t n, int64_t h, int layout, int aligned16_all, rl8_gae_plan_t *out) {
+  if (!out) return RL8_ENULL;
+  if (n <= 0 || h <= 0) return RL8_ESIZE;
+  if (layout != 0 && layout != 1) return RL8_ECONFIG;
+  rl8_gae_plan_t p = {};
+  if (layout == 1) {
+    const bool vec = (n % 4 == 0) && aligned16_all;
+    p.route = vec ? RL8_GAE_TIME_VEC4 : RL8_GAE_TIME_VEC1;
+    p.envs_per_block = kBlock * (vec ? 4 : 1);
+    // 2 workgroups per CU measured best (5.3 TB/s vs 5.1 at 4/CU, 3.8 at 1/CU).
+    static const int tm_cap = env_int("RL8_GAE_GRID_CAP");
+    p.grid = grid_for(n, p.envs_per_block, tm_cap > 0 ? tm_cap : 2 * kCUs);
+    *out = p;
+    return RL8_OK;
+  }
+  const int64_t cols = h + 1;
+  const int chunk = (int)(cols < 127 ? cols : 127);
+  const int lds_stride = chunk | 1;  // odd => conflict-free column walks
+  // One lane per env; as many envs per block as ~72 KB of LDS allow (2 blocks
+  // per CU), in whole waves.  RL8_GAE_ENVS_PER_BLOCK overrides (tuning).
+  static const int env_override = env_int("RL8_GAE_ENVS_PER_BLOCK");
+  int e = (int)(73728 / ((int64_t)lds_stride * 8) / kWave) * kWave;
+  if (e > 256) e = 256;
+  // (the pipelined flat kernel: 128 envs per workgroup, two workgroups per CU measured best -- 122.6-124.2 us per
+  // 2^20 x 32 against 126.5-128 for the other shapes)
+  const bool pipelined_shape = chunk == cols && (cols & 1) && cols <= 36;
+  if (pipelined_shape && e > 128) e = 128;
+  if (env_override >= kWave && env_override <= 256 && env_override % kWave == 0) e = env_override;
+  if (e < kWave) e = kWave;
+  size_t lds_bytes = (size_t)2 * e * lds_stride * sizeof(float);
+  const bool flat = chunk == cols && lds_stride == cols && (e % 4 == 0) && aligned16_all;
+  int rows = grid_for(n, e);
+  if (flat && pipelined_shape) {
+    p.route = RL8_GAE_ENV_PIPELINED;
+    // as many workgroups as are resident at once (each runs its tiles back to back, the next one's rows in flight):
+    // a second round of workgroups would start with nothing requested
+    static const int per_cu_cap = env_int("RL8_GAE_BLOCKS_PER_CU");
+    int per_cu = (int)((160 * 1024) / (lds_bytes + 16 + 1024));
+    if (per_cu > 2) per_cu = 2;
+    if (per_cu_cap > 0 && per_cu_cap < per_cu) per_cu = per_cu_cap;
+    if (per_cu < 1) per_cu = 1;
+    if (rows > kCUs * per_cu) rows = kCUs * per_cu;
+    // (a lane's sixteen-byte piece of the tile's tail may reach past E * cols floats by up to 12 bytes: + one vector)
+    lds_bytes += 16;
+  } else {
+    p.route = flat ? RL8_GAE_ENV_FLAT : RL8_GAE_ENV_CHUNKED;
+  }
+  p.envs_per_block = e;
+  p.chunk = chunk;
+  p.lds_stride = lds_stride;
+  p.lds_bytes = (int64_t)lds_bytes;
+  p.grid = rows;
+  *out = p;
+  return RL8_OK;
+}
+
+RL8_API int rl8_advantage_normalise_route(int64_t n, int64_t h, int layout, int aligned16) {
+  if (n <= 0 || h <= 0) return RL8_ESIZE;
+  if (layout == 0) return RL8_NORM_ENV_MAJOR;
+  if (layout != 1) return RL8_ECONFIG;
+  return ((n * h) % 4 == 0 && aligned16) ? RL8_NORM_FLAT_VEC4 : RL8_NORM_FLAT_VEC1;
+}
+
 RL8_API int rl8_gae_scan_f32(float *rewards, const float *values, float *adv_out, float *ret_out,
                              int64_t n, int64_t h, int layout, float gamma, float gamma_lambda,
                              float reward_denominator, int write_scaled_rewards,
                              double *moments_out, void *scratch, void *stream) {
   if (!rewards || !values || !adv_out || !ret_out || !moments_out || !scratch) return RL8_ENULL;
-  if (n <= 0 || h <= 0) return RL8_ESIZE;
-  if (layout != 0 && layout != 1) return RL8_ECONFIG;
+  rl8_gae_plan_t p;
+  const bool aligned = aligned16(rewards) && aligned16(values) && aligned16(adv_out) && aligned16(ret_out);
+  if (const int bad = rl8_gae_plan(n, h, layout, aligned, &p)) return bad;
   hipStream_t s = (hipStream_t)stream;
   double *partials = (double *)scratch;
-  int rows;
-  if (layout == 1) {
-    const bool vec = (n % 4 == 0) && aligned16(rewards) && aligned16(values) &&
-                     aligned16(adv_out) && aligned16(ret_out);
-    const int per_block = kBlock * (vec ? 4 : 1);
-    // 2 workgroups per CU measured best (5.3 TB/s vs 5.1 at 4/CU, 3.8 at 1/CU).
-    static const int tm_cap = env_int("RL8_GAE_GRID_CAP");
-    rows = grid_for(n, per_block, tm_cap > 0 ? tm_cap : 2 * kCUs);
-    if (vec)
-      gae_scan_time_major_kernel<4><<<rows, kBlock, 0, s>>>(
-          rewards, values, adv_out, ret_out, n, h, gamma, gamma_lambda, reward_denominator,
-          write_scaled_rewards, partials, moments_out);
-    else
-      gae_scan_time_major_kernel<1><<<rows, kBlock, 0, s>>>(
-          rewards, values, adv_out, ret_out, n, h, gamma, gamma_lambda, reward_denominator,
-          write_scaled_rewards, partials, moments_out);
-  } else {
-    const int64_t cols = h + 1;
-    const int chunk = (int)(cols < 127 ? cols : 127);
-    const int lds_stride = chunk | 1;  // odd => conflict-free column walks
-    // One lane per env; as many envs per block as ~72 KB of LDS allow (2 blocks
-    // per CU), in whole waves.  RL8_GAE_ENVS_PER_BLOCK overrides (tuning).
-    static int env_override = -1;
-    if (env_override < 0) {
-      const char *v = getenv("RL8_GAE_ENVS_PER_BLOCK");
-      env_override = v ? atoi(v) : 0;
-    }
-    int e = (int)(73728 / ((int64_t)lds_stride * 8) / kWave) * kWave;
-    if (e > 256) e = 256;
-    // (the pipelined flat kernel below: 128 envs per workgroup, two workgroups per CU measured best -- 122.6-124.2 us per
-    // 2^20 x 32 against 126.5-128 for the other shapes)
-    const bool pipelined_shape = chunk == cols && (cols & 1) && cols <= 36;
-    if (pipelined_shape && e > 128) e = 128;
-    if (env_override >= kWave && env_override <= 256 && env_override % kWave == 0) e = env_override;
-    if (e < kWave) e = kWave;
-    const size_t lds_bytes = (size_t)2 * e * lds_stride * sizeof(float);
-    const bool flat = chunk == cols && lds_stride == cols && (e % 4 == 0) && aligned16(rewards) &&
-                      aligned16(values) && aligned16(adv_out) && aligned16(ret_out);
+  if (layout == 0) {
     static LdsOptIn lds_attr_set_0;
     if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&gae_scan_env_major_kernel<true>), 160 * 1024)) return e_lds_attr_set_0;
     static LdsOptIn lds_attr_set_1;
     if (const int e_lds_attr_set_1 = allow_dynamic_lds(lds_attr_set_1, reinterpret_cast<const void *>(&gae_scan_env_major_kernel<false>), 160 * 1024)) return e_lds_attr_set_1;
-    rows = grid_for(n, e);
-    if (flat && pipelined_shape) {
+  }
+  switch (p.route) {
+    case RL8_GAE_TIME_VEC4:
+      gae_scan_time_major_kernel<4><<<p.grid, kBlock, 0, s>>>(
+          rewards, values, adv_out, ret_out, n, h, gamma, gamma_lambda, reward_denominator,
+          write_scaled_rewards, partials, moments_out);
+      break;
+    case RL8_GAE_TIME_VEC1:
+      gae_scan_time_major_kernel<1><<<p.grid, kBlock, 0, s>>>(
+          rewards, values, adv_out, ret_out, n, h, gamma, gamma_lambda, reward_denominator,
+          write_scaled_rewards, partials, moments_out);
+      break;
+    case RL8_GAE_ENV_PIPELINED: {
       static LdsOptIn lds_attr9_0;
       if (const int e_lds_attr9_0 = allow_dynamic_lds(lds_attr9_0, reinterpret_cast<const void *>(&gae_scan_env_major_pipelined_kernel<9>), 160 * 1024)) return e_lds_attr9_0;
-      // as many workgroups as are resident at once (each runs its tiles back to back, the next one's rows in flight):
-      // a second round of workgroups would start with nothing requested
-      static const int per_cu_cap = env_int("RL8_GAE_BLOCKS_PER_CU");
-      int per_cu = (int)((160 * 1024) / (lds_bytes + 16 + 1024));
-      if (per_cu > 2) per_cu = 2;
-      if (per_cu_cap > 0 && per_cu_cap < per_cu) per_cu = per_cu_cap;
-      if (per_cu < 1) per_cu = 1;
-      if (rows > kCUs * per_cu) rows = kCUs * per_cu;
-      // (a lane's sixteen-byte piece of the tile's tail may reach past E * cols floats by up to 12 bytes: + one vector)
-      gae_scan_env_major_pipelined_kernel<9><<<rows, e, lds_bytes + 16, s>>>(
+      gae_scan_env_major_pipelined_kernel<9><<<p.grid, p.envs_per_block, (size_t)p.lds_bytes, s>>>(
           rewards, values, adv_out, ret_out, n, h, gamma, gamma_lambda, reward_denominator, write_scaled_rewards, partials,
           moments_out);
-    } else if (flat)
-      gae_scan_env_major_kernel<true><<<rows, e, lds_bytes, s>>>(
+      break;
+    }
+    case RL8_GAE_ENV_FLAT:
+      gae_scan_env_major_kernel<true><<<p.grid, p.envs_per_block, (size_t)p.lds_bytes, s>>>(
           rewards, values, adv_out, ret_out, n, h, gamma, gamma_lambda, reward_denominator,
-          write_scaled_rewards, chunk, lds_stride, partials, moments_out);
-    else
-      gae_scan_env_major_kernel<false><<<rows, e, lds_bytes, s>>>(
+          write_scaled_rewards, p.chunk, p.lds_stride, partials, moments_out);
+      break;
+    default:
+      gae_scan_env_major_kernel<false><<<p.grid, p.envs_per_block, (size_t)p.lds_bytes, s>>>(
           rewards, values, adv_out, ret_out, n, h, gamma, gamma_lambda, reward_denominator,
-          write_scaled_rewards, chunk, lds_stride, partials, moments_out);
+          write_scaled_rewards, p.chunk, p.lds_stride, partials, moments_out);
   }
   return launch_status();
 }
@@ -505,21 +543,21 @@ RL8_API int rl8_advantage_normalise_f32(float *adv, int64_t n, int64_t h, int la
   if (!adv || !moments) return RL8_ENULL;
   if (n <= 0 || h <= 0) return RL8_ESIZE;
   hipStream_t s = (hipStream_t)stream;
-  if (layout == 1) {
+  const int route = rl8_advantage_normalise_route(n, h, layout, aligned16(adv));
+  if (route < 0) return route;
+  if (route == RL8_NORM_ENV_MAJOR) {
+    advantage_normalise_env_major_kernel<<<grid_for(n * (h + 1), kBlock), kBlock, 0, s>>>(adv, n, h,
+                                                                                      moments);
+  } else {
     const int64_t count = n * h;
     static const int cap = env_int("RL8_NORM_GRID_CAP");
-    if (count % 4 == 0 && aligned16(adv))
+    if (route == RL8_NORM_FLAT_VEC4)
       advantage_normalise_flat_kernel<4>
           <<<grid_for(count, kBlock * 4, cap > 0 ? cap : kMaxGrid), kBlock, 0, s>>>(adv, count,
                                                                                    moments);
     else
       advantage_normalise_flat_kernel<1><<<grid_for(count, kBlock), kBlock, 0, s>>>(adv, count,
                                                                                 moments);
-  } else if (layout == 0) {
-    advantage_normalise_env_major_kernel<<<grid_for(n * (h + 1), kBlock), kBlock, 0, s>>>(adv, n, h,
-                                                                                      moments);
-  } else {
-    return RL8_ECONFIG;
   }
   return launch_status();
 }

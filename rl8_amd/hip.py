@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Any, Sequence
+from typing import Any, NamedTuple, Sequence
 
 import torch
 
@@ -91,6 +91,13 @@ class GatherField(C.Structure):
     ]
 
 
+class GaePlanStruct(C.Structure):
+    """``rl8_gae_plan_t`` (include/rl8_amd.h)."""
+
+    _fields_ = [("route", C.c_int), ("envs_per_block", C.c_int), ("chunk", C.c_int), ("lds_stride", C.c_int),
+                ("lds_bytes", C.c_int64), ("grid", C.c_int)]
+
+
 _vp, _i64, _u64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_uint64, C.c_int, C.c_float
 
 # name -> argtypes, mirroring include/rl8_amd.h one to one.
@@ -123,6 +130,8 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_rollout_stats_f32": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp],
     "rl8_gae_scan_f32": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _f32, _f32, _i32, _vp, _vp, _vp],
     "rl8_advantage_normalise_f32": [_vp, _i64, _i64, _i32, _vp, _vp],
+    "rl8_gae_plan": [_i64, _i64, _i32, _i32, C.POINTER(GaePlanStruct)],
+    "rl8_advantage_normalise_route": [_i64, _i64, _i32, _i32],
     "rl8_ppo_loss_categorical_fwd_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(PPOHparams), _vp, _vp, _vp, _vp, _vp],
     "rl8_ppo_loss_normal_fwd_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(PPOHparams), _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_gather_minibatch": [_vp, _i64, _i64, C.POINTER(GatherField), _i32, _vp],
@@ -690,6 +699,37 @@ def rollout_stats(rewards: torch.Tensor, rdr: None | torch.Tensor) -> torch.Tens
 # --------------------------------------------------------------------------- #
 # GAE.
 # --------------------------------------------------------------------------- #
+#: route names of ``rl8_gae_plan`` / ``rl8_advantage_normalise_route``, indexed by their RL8_GAE_* / RL8_NORM_* codes
+GAE_ROUTES = ("TIME_VEC4", "TIME_VEC1", "ENV_PIPELINED", "ENV_FLAT", "ENV_CHUNKED")
+NORMALISE_ROUTES = ("FLAT_VEC4", "FLAT_VEC1", "ENV_MAJOR")
+
+
+class GaePlan(NamedTuple):
+    """What ``rl8_gae_scan_f32`` launches for a shape, a layout and an alignment (``rl8_gae_plan_t``)."""
+
+    route: str
+    envs_per_block: int
+    chunk: int
+    lds_stride: int
+    lds_bytes: int
+    grid: int
+
+
+def gae_plan(n: int, h: int, layout: int, aligned16_all: bool = True) -> GaePlan:
+    """The scan's launch plan; host arithmetic in the library, no device needed."""
+    p = GaePlanStruct()
+    _check(load().rl8_gae_plan(n, h, layout, int(aligned16_all), C.byref(p)), "rl8_gae_plan")
+    return GaePlan(GAE_ROUTES[p.route], p.envs_per_block, p.chunk, p.lds_stride, p.lds_bytes, p.grid)
+
+
+def advantage_normalise_route(n: int, h: int, layout: int, aligned16: bool = True) -> str:
+    """The kernel ``advantage_normalise`` launches; host arithmetic in the library, no device needed."""
+    route = load().rl8_advantage_normalise_route(n, h, layout, int(aligned16))
+    if route < 0:
+        _check(route, "rl8_advantage_normalise_route")
+    return NORMALISE_ROUTES[route]
+
+
 def gae_scan(
     rewards: torch.Tensor, values: torch.Tensor, adv: torch.Tensor, ret: torch.Tensor, *, layout: int,
     n: int, h: int, gamma: float, gamma_lambda: float, reward_denominator: float, write_scaled_rewards: bool,
