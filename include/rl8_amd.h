@@ -84,7 +84,9 @@ extern "C" {
  * 105 round 4 (rl8_gather_minibatch takes index = NULL: all samples in order); 106 round 6 (no signature changed:
  * rl8_lstm_rows_backward_pack writes the fp16 planes of W_hh^T behind the bf16 ones -- rl8_lstm_rows_backward_pack_bytes
  * grew by 1 MiB + 16, and rl8_lstm_rows_backward_heads_f32 reads them; rl8_mlp_backward_f16_supports and
- * rl8_lstm_split_supports report wider envelopes; the weight-gradient workspace's tail words moved). */
+ * rl8_lstm_split_supports report wider envelopes; the weight-gradient workspace's tail words moved).  Added under 106
+ * without a bump (new entries only, nothing existing changed): rl8_rollout_scatter_leaves_f32,
+ * rl8_algotrading_reset_f32, rl8_algotrading_step_f32, rl8_rollout_step_algotrading_f32. */
 #define RL8_ABI_VERSION 106
 int rl8_abi_version(char *arch, int arch_len);
 
@@ -401,6 +403,51 @@ int rl8_pack_samples(const rl8_gather_field *fields /*host*/, int n_fields, int6
                      void *packed, int row_words, void *stream);
 int rl8_gather_packed(const int64_t *index, int64_t m, const void *packed, int row_words,
                       const rl8_gather_field *fields /*host*/, int n_fields, void *stream);
+
+/* ---------------------------------------------------------------------- *
+ * Dict (Composite) observations: rollout bookkeeping and the AlgoTrading env
+ *      src/rl8/algorithms/_feedforward.py:378-393, examples/algotrading/env.py:23-183
+ * rl8_rollout_scatter_leaves_f32: what rl8_rollout_scatter_f32 does for action / logp / value / reward / rdr, and
+ * 1 .. RL8_MAX_GATHER_FIELDS observation leaves copied into their t+1 columns in the same launch.  A leaf is n rows
+ * of row_bytes bytes (any positive count: 1 for bool, 8 for int64, 4 d for f32[d]), source and destination both
+ * contiguous; copied 16 bytes at a time where n * row_bytes and both pointers allow, else 8, 4 or 1.  The float and
+ * action pointers are 4-byte aligned (RL8_EALIGN); action_row_bytes a multiple of 4.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  const void *src;
+  void *dst;
+  int64_t row_bytes;
+} rl8_scatter_leaf;
+
+int rl8_rollout_scatter_leaves_f32(const void *action, int64_t action_row_bytes, const float *logp,
+                                   const float *value, const float *reward,
+                                   const rl8_scatter_leaf *leaves /*host*/, int n_leaves, void *action_col,
+                                   float *logp_col, float *value_col, float *reward_col, const float *rdr_t,
+                                   float *rdr_t1, float gamma, int64_t n, void *stream);
+
+/* AlgoTrading: state SoA [9][N] fp32 in place, rows invested (0 / 1), position, f, k_cyclic, k_market, t, price,
+ * LOG_CHANGE(price), LOG_CHANGE(price, position).  The observation is four leaves: mask [N][3] bytes (hold, buy,
+ * sell allowed), invested [N] int64 and the two log-changes [N] f32 each.
+ * reset (:85-93): f ~ U(0, f_bounds), k_* ~ U(-bounds, bounds), t in 0..9, price ~ U(100, 10000) from the build's
+ * Philox stream, not invested, position 0, mask (1, 1, 0); the four leaf outputs together or all NULL.
+ * step (:131-183): action [N] int64 in {0 hold, 1 buy, 2 sell}, the mask is not enforced (as in the reference);
+ * price' = price * ((1 + k_market) * (1 + k_cyclic * sin(t' f))), accurate sin / log, one rounding per operation.
+ * invested / action pointers 8-byte aligned, floats 4-byte (RL8_EALIGN). */
+int rl8_algotrading_reset_f32(float *state, int64_t n, float f_bounds, float k_cyclic_bounds, float k_market_bounds,
+                              uint64_t seed, uint64_t reset_count, int64_t env_offset, uint8_t *mask_out,
+                              int64_t *invested_out, float *log_change_out, float *log_change_position_out,
+                              void *stream);
+int rl8_algotrading_step_f32(float *state, const int64_t *action, uint8_t *mask_out, int64_t *invested_out,
+                             float *log_change_out, float *log_change_position_out, float *reward_out, int64_t n,
+                             void *stream);
+/* Fused per-timestep kernel (K = 3 sampler on the model's masked logits + the step + bookkeeping), arguments as
+ * rl8_rollout_step_cartpole_f32 with the four leaves' t+1 columns in place of obs_col_next. */
+int rl8_rollout_step_algotrading_f32(const float *logits, const float *value, const float *noise, float *state,
+                                     int64_t *action_col, float *logp_col, float *value_col, float *reward_col,
+                                     uint8_t *mask_next, int64_t *invested_next, float *log_change_next,
+                                     float *log_change_position_next, const float *rdr_t, float *rdr_t1, float gamma,
+                                     int64_t n, uint64_t seed, uint64_t step, int64_t env_offset, int deterministic,
+                                     void *stream);
 
 /* ---------------------------------------------------------------------- *
  * N1  Default policy / value tower, fused

@@ -208,6 +208,9 @@ class Algorithm:
         self.env.env_offset = self.shards.env_offset(local_envs)
         assert_nd_spec(self.env.observation_spec)
         assert_nd_spec(self.env.action_spec)
+        #: leaf names of a composite observation spec, ``None`` for a tensor spec (refuses the specs the buffer cannot
+        #: hold before anything is built on them)
+        self._obs_leaves = self._composite_obs_leaves()
         self.policy = self._make_policy(config, device)
         self.shards.broadcast_parameters_(self.policy.model)
         self.noise = NoiseStream()
@@ -308,17 +311,44 @@ class Algorithm:
     # ------------------------------------------------------------------ #
     # Buffer: time-major storage, env-major views.
     # ------------------------------------------------------------------ #
-    def _allocate_buffer(self, num_envs: int, horizon: int) -> None:
+    #: Dict observations (a ``Composite`` of tensor leaves) are held leaf by leaf; the recurrent algorithm takes
+    #: tensor observations only.
+    composite_observations = True
+
+    #: Leaf dtypes of a composite observation spec.
+    OBS_LEAF_DTYPES = (torch.float32, torch.int64, torch.bool)
+
+    def _composite_obs_leaves(self) -> None | list[str]:
+        """Leaf names of a composite observation spec the buffer can hold (one level of float32 / int64 / bool
+        tensor leaves, each with a non-empty shape), ``None`` for a tensor spec; anything else is refused."""
         obs_spec = self.env.observation_spec
-        if isinstance(obs_spec, Composite) or isinstance(self.env.action_spec, Composite):
+        supported = not isinstance(self.env.action_spec, Composite)
+        if supported and not isinstance(obs_spec, Composite):
+            return None
+        supported = supported and self.composite_observations and len(obs_spec) > 0 and all(
+            not isinstance(leaf, Composite) and leaf.ndim >= 1 and leaf.dtype in self.OBS_LEAF_DTYPES
+            for leaf in obs_spec.values())
+        if not supported:
             raise NotImplementedError(
                 "rl8_amd's rollout buffer holds tensor observation / action specs"
                 " (composite specs are outside the accelerated path)."
             )
+        if len(obs_spec) > hip.MAX_GATHER_FIELDS:
+            raise NotImplementedError(
+                f"a composite observation spec may have at most {hip.MAX_GATHER_FIELDS} leaves"
+                " (what one rollout bookkeeping launch writes)."
+            )
+        return list(obs_spec.keys())
+
+    def _allocate_buffer(self, num_envs: int, horizon: int) -> None:
+        obs_leaves = self._obs_leaves
         #: key -> ``[H+1, N, ...]`` storage of the flat leaves.
         self._tm: dict[str, torch.Tensor] = {}
         #: recurrent-state leaves (``buffer["states"][k]``), same layout.
         self._tm_states: dict[str, torch.Tensor] = {}
+        #: leaves of a composite observation spec (``buffer["obs"][k]``), same layout; ``None`` for a tensor spec,
+        #: whose slab is ``_tm["obs"]``.
+        self._tm_obs: None | dict[str, torch.Tensor] = None if obs_leaves is None else {}
 
         def slab(spec: Any) -> torch.Tensor:
             return torch.zeros(horizon + 1, num_envs, *spec.shape, dtype=spec.dtype, device=spec.device)
@@ -328,12 +358,16 @@ class Algorithm:
         for key in self.buffer_spec:
             spec = self.buffer_spec[key]
             if isinstance(spec, Composite):
-                if key != DataKeys.STATES:
+                if key == DataKeys.OBS and self._tm_obs is not None:
+                    slabs = self._tm_obs
+                elif key == DataKeys.STATES:
+                    slabs = self._tm_states
+                else:
                     raise NotImplementedError(f"composite buffer leaf {key!r} is not supported")
                 nested = {}
                 for sub in spec:
                     storage = slab(spec[sub])
-                    self._tm_states[sub] = storage
+                    slabs[sub] = storage
                     nested[sub] = storage.transpose(0, 1)
                 views[key] = TensorDict(nested, batch_size=[num_envs, horizon + 1])
             else:
@@ -359,7 +393,7 @@ class Algorithm:
                 storage[:h].zero_()
             else:
                 storage.zero_()
-        for storage in self._tm_states.values():
+        for storage in (*self._tm_states.values(), *(self._tm_obs or {}).values()):
             storage[:h].zero_()
 
     # ------------------------------------------------------------------ #
@@ -406,8 +440,9 @@ class Algorithm:
             return True
         return set(views) == {DataKeys.OBS} and all(v.is_identity for v in views.values())
 
-    def _forward(self, obs: torch.Tensor, *, deterministic: bool) -> tuple[TensorDict, torch.Tensor]:
-        """Policy network on a ``[N, obs...]`` slab -> (features, values)."""
+    def _forward(self, obs: torch.Tensor | TensorDict, *, deterministic: bool) -> tuple[TensorDict, torch.Tensor]:
+        """Policy network on a ``[N, obs...]`` slab (a tensordict of them for dict observations) -> (features,
+        values)."""
         sample = self.policy.sample(
             TensorDict({DataKeys.VIEWS: TensorDict({DataKeys.OBS: obs}, batch_size=obs.shape[0])},
                        batch_size=obs.shape[0]),
@@ -440,17 +475,22 @@ class Algorithm:
         H = hp.horizon
         tm = self._tm
         rdr = tm.get(DataKeys.REVERSED_DISCOUNTED_RETURNS)
+        # the observation slabs: one for a tensor spec, one per leaf for a composite one
+        obs_slabs = self._tm_obs if self._tm_obs is not None else {None: tm[DataKeys.OBS]}
         with profile_ms() as collect_timer:
             env_was_reset = False
             carry = (self.state.horizons and hp.horizons_per_env_reset < 0) or (
                 self.state.horizons % hp.horizons_per_env_reset
             )
             if carry:
-                tm[DataKeys.OBS][0].copy_(tm[DataKeys.OBS][H])
+                for storage in obs_slabs.values():
+                    storage[0].copy_(storage[H])
                 if rdr is not None:
                     rdr[0].copy_(rdr[H])
             else:
-                tm[DataKeys.OBS][0].copy_(self.env.reset(config=env_config))
+                first = self.env.reset(config=env_config)
+                for leaf, storage in obs_slabs.items():
+                    storage[0].copy_(first if leaf is None else first[leaf])
                 env_was_reset = True
                 if rdr is not None:
                     rdr[0].zero_()
@@ -462,7 +502,7 @@ class Algorithm:
             pair = (fused_mlp.expect_pair_gradients() if record is not None and issubclass(dist_cls, Categorical)
                     else contextlib.nullcontext())
             for t in range(H):
-                obs_t = tm[DataKeys.OBS][t]
+                obs_t = self._obs_column(t)
                 noise_t = self.injected_noise[t] if self.injected_noise is not None else None
                 step_id = self.noise.next_step()
                 if fused:
@@ -473,7 +513,7 @@ class Algorithm:
                     self._generic_step(obs_t, noise_t, t, gamma, step_id, deterministic)
 
             # Bootstrap value at the last observation (:396-408).
-            if self._identity_views():
+            if self._identity_views() and self._tm_obs is None:
                 _, values = self._forward(tm[DataKeys.OBS][H], deterministic=deterministic)
             else:
                 values = self.policy.sample(
@@ -500,10 +540,18 @@ class Algorithm:
         collect_stats["profiling/collect_ms"] = collect_timer()
         return collect_stats
 
+    def _obs_column(self, t: int) -> torch.Tensor | TensorDict:
+        """Column ``t`` of the observations: the ``[N, ...]`` slab, or a tensordict of the leaves' slabs."""
+        if self._tm_obs is None:
+            return self._tm[DataKeys.OBS][t]
+        return TensorDict({leaf: storage[t] for leaf, storage in self._tm_obs.items()}, batch_size=self.local_num_envs)
+
     def _rollout_record(self, fused: bool) -> None | fused_mlp.RolloutRecord:
-        """The record this ``collect()`` fills (made once, its slabs reused by every rollout), or ``None``."""
+        """The record this ``collect()`` fills (made once, its slabs reused by every rollout), or ``None``.  Dict
+        observations train from views of the buffer, never from the record."""
         rec = self._record
-        if not fused or not self.reuse_rollout_forward or not has_fused_loss(self.policy.distribution_cls):
+        if (not fused or self._tm_obs is not None or not self.reuse_rollout_forward
+                or not has_fused_loss(self.policy.distribution_cls)):
             if rec is not None:  # (what an earlier rollout recorded is not this one's: step() must not replay it)
                 rec.unseal()
             return None
@@ -537,7 +585,8 @@ class Algorithm:
             logp_col=tm[DataKeys.LOGP][t],
             value_col=tm[DataKeys.VALUES][t],
             reward_col=tm[DataKeys.REWARDS][t],
-            obs_col_next=tm[DataKeys.OBS][t + 1],
+            obs_col_next=(tm[DataKeys.OBS][t + 1] if self._tm_obs is None
+                          else {leaf: storage[t + 1] for leaf, storage in self._tm_obs.items()}),
             rdr_t=rdr[t] if rdr is not None else None,
             rdr_t1=rdr[t + 1] if rdr is not None else None,
             gamma=gamma,
@@ -569,6 +618,24 @@ class Algorithm:
             return_views=False,
         )
         out = self.env.step(sample[DataKeys.ACTIONS])
+        if self._tm_obs is not None:
+            obs = out[DataKeys.OBS]
+            hip.rollout_scatter_leaves(
+                sample[DataKeys.ACTIONS].contiguous(),
+                sample[DataKeys.LOGP].contiguous(),
+                sample[DataKeys.VALUES].contiguous(),
+                out[DataKeys.REWARDS].contiguous(),
+                [obs[leaf].contiguous() for leaf in self._tm_obs],
+                tm[DataKeys.ACTIONS][t],
+                tm[DataKeys.LOGP][t],
+                tm[DataKeys.VALUES][t],
+                tm[DataKeys.REWARDS][t],
+                [storage[t + 1] for storage in self._tm_obs.values()],
+                rdr[t] if rdr is not None else None,
+                rdr[t + 1] if rdr is not None else None,
+                gamma,
+            )
+            return
         hip.rollout_scatter(
             sample[DataKeys.ACTIONS].contiguous(),
             sample[DataKeys.LOGP].contiguous(),
@@ -737,7 +804,7 @@ class Algorithm:
         H, tm = hp.horizon, self._tm
         local_samples = self.local_num_envs * H
         self._batch_rows = None
-        if not self._identity_views():
+        if not self._identity_views() or self._tm_obs is not None:
             yield from self._iter_view_minibatches(sgd_iter)
             return
         if hp.num_minibatches == 1:
@@ -763,7 +830,7 @@ class Algorithm:
             yield dict(zip(self.TRAIN_KEYS, self._packed.gather(index)))
 
     def _iter_view_minibatches(self, sgd_iter: int):
-        """Minibatches for models with rolling-window view requirements
+        """Minibatches for models with rolling-window view requirements and for dict observations
         (``src/rl8/algorithms/_feedforward.py:471-482``): the windows of the whole
         buffer are built once per ``step()`` (env-major sample order, like the
         flattened buffer) and indexed per minibatch."""

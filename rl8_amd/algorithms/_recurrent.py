@@ -243,6 +243,8 @@ class RecurrentAlgorithm(Algorithm):
     #: Issue the rollout's per-timestep launches through :class:`_LeanRollout` when the
     #: model / env pair allows it (False: always through ``policy.sample()``).
     lean_rollout: bool = True
+    #: Tensor observation specs only (dict observations belong to the feed-forward algorithm).
+    composite_observations = False
 
     def __init__(self, env_cls: EnvFactory, /, config: None | RecurrentAlgorithmConfig = None) -> None:
         config = config or RecurrentAlgorithmConfig()

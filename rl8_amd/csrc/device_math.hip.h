@@ -63,6 +63,72 @@ __device__ __forceinline__ float pendulum_advance(float &th, float &thdot, float
   return -costs;
 }
 
+// ---- AlgoTrading (examples/algotrading/env.py:131-183) ---------------------
+// One env.  The reference's order: buy, then sell (whose reward reads the position as the buy left it, before the
+// not-invested reset below), then hold on the UPDATED invested flag; then the clock and the price.  Every written
+// operation rounds once (-ffp-contract=off); sinf is the accurate library function, and the logs are correctly rounded
+// (cr_logf): rewards and log-changes are differences of two logs of 7 .. 17, where a last-place error of the library
+// logf is 1e-6 and adds up over a rollout's reversed discounted returns (measured against fp64
+// the kernel errs as far as the reference, 1.1e-6 in the log-changes).  A SELL on a position of 0 (the first step
+// after a reset) pays log(price) - log(0) = +inf, as the reference does.
+struct AlgoTradingState {
+  float invested, position, f, k_cyclic, k_market, t, price, log_change, log_change_position;
+};
+constexpr int kAlgoTradingRows = 9;  // rows of the [9][N] state, in the order of the members above
+
+__device__ __forceinline__ AlgoTradingState algotrading_load(const float *__restrict__ state, int64_t n, int64_t i) {
+  return {state[i],         state[n + i],     state[2 * n + i], state[3 * n + i], state[4 * n + i],
+          state[5 * n + i], state[6 * n + i], state[7 * n + i], state[8 * n + i]};
+}
+
+// (f, k_cyclic and k_market change at a reset only)
+__device__ __forceinline__ void algotrading_store(float *__restrict__ state, int64_t n, int64_t i,
+                                                  const AlgoTradingState &s) {
+  state[i] = s.invested;
+  state[n + i] = s.position;
+  state[5 * n + i] = s.t;
+  state[6 * n + i] = s.price;
+  state[7 * n + i] = s.log_change;
+  state[8 * n + i] = s.log_change_position;
+}
+
+__device__ __forceinline__ float algotrading_advance(AlgoTradingState &s, int64_t action) {
+  const float old_price = s.price;
+  float reward = 0.0f;
+  if (action == 1) {
+    s.invested = 1.0f;
+    s.position = old_price;
+  }
+  if (action == 2) {
+    s.invested = 0.0f;
+    reward = cr_logf(old_price) - cr_logf(s.position);
+  }
+  const bool invested = s.invested == 1.0f;
+  if (!invested) s.position = old_price;
+  if (invested && action == 0) reward = s.log_change;
+  s.t = s.t + 1.0f;
+  const float cyclic = 1.0f + s.k_cyclic * sinf(s.t * s.f);
+  s.price = s.price * ((1.0f + s.k_market) * cyclic);
+  const float log_price = cr_logf(s.price);
+  s.log_change = log_price - cr_logf(old_price);
+  s.log_change_position = log_price - cr_logf(s.position);
+  return reward;
+}
+
+// The four observation leaves of env i: action_mask [3] bytes (hold, buy, sell), invested int64, the two log-changes.
+__device__ __forceinline__ void algotrading_write_obs(const AlgoTradingState &s, int64_t i,
+                                                      uint8_t *__restrict__ mask, int64_t *__restrict__ invested,
+                                                      float *__restrict__ log_change,
+                                                      float *__restrict__ log_change_position) {
+  const bool inv = s.invested == 1.0f;
+  mask[3 * i] = 1;
+  mask[3 * i + 1] = inv ? 0 : 1;
+  mask[3 * i + 2] = inv ? 1 : 0;
+  invested[i] = inv ? 1 : 0;
+  log_change[i] = s.log_change;
+  log_change_position[i] = s.log_change_position;
+}
+
 struct CartPoleState {
   float x, x_dot, theta, theta_dot;
 };

@@ -175,6 +175,55 @@ __global__ __launch_bounds__(kBlock) void rollout_scatter_kernel(
   for (int64_t i = tid; i < o_words; i += stride) obs_col_next[i] = obs[i];
 }
 
+// The same for an Env whose observations are a dict: the five columns as above, and up to RL8_MAX_GATHER_FIELDS
+// observation leaves copied into their t+1 columns in the same launch.  A leaf is n rows of row_bytes bytes, dense on
+// both sides, so it is copied as one run of `units` pieces of `unit` bytes -- 16 where the run's length and both
+// pointers allow it, else 8, 4 or single bytes (a bool[3] leaf of an odd number of envs) -- lane-contiguous either way.
+struct ScatterLeaves {
+  const char *src[RL8_MAX_GATHER_FIELDS];
+  char *dst[RL8_MAX_GATHER_FIELDS];
+  int64_t units[RL8_MAX_GATHER_FIELDS];
+  int unit[RL8_MAX_GATHER_FIELDS];
+  int count;
+};
+
+template <class T>
+__device__ __forceinline__ void copy_units(const char *__restrict__ src, char *__restrict__ dst, int64_t units,
+                                           int64_t tid, int64_t stride) {
+  const T *s = reinterpret_cast<const T *>(src);
+  T *d = reinterpret_cast<T *>(dst);
+  for (int64_t i = tid; i < units; i += stride) d[i] = s[i];
+}
+
+__global__ __launch_bounds__(kBlock) void rollout_scatter_leaves_kernel(
+    const char *__restrict__ action, int64_t action_row_bytes, const float *__restrict__ logp,
+    const float *__restrict__ value, const float *__restrict__ reward, ScatterLeaves leaves,
+    char *__restrict__ action_col, float *__restrict__ logp_col, float *__restrict__ value_col,
+    float *__restrict__ reward_col, const float *__restrict__ rdr_t, float *__restrict__ rdr_t1, float gamma,
+    int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  for (int64_t i = tid; i < n; i += stride) {
+    const float r = reward[i];
+    logp_col[i] = logp[i];
+    value_col[i] = value[i];
+    reward_col[i] = r;
+    if (rdr_t1) rdr_t1[i] = gamma * rdr_t[i] + r;
+  }
+  copy_units<uint32_t>(action, action_col, n * action_row_bytes / 4, tid, stride);
+  for (int f = 0; f < leaves.count; ++f) {
+    const char *src = leaves.src[f];
+    char *dst = leaves.dst[f];
+    const int64_t units = leaves.units[f];
+    switch (leaves.unit[f]) {  // (uniform over the grid)
+      case 16: copy_units<uint4>(src, dst, units, tid, stride); break;
+      case 8: copy_units<uint2>(src, dst, units, tid, stride); break;
+      case 4: copy_units<uint32_t>(src, dst, units, tid, stride); break;
+      default: copy_units<uint8_t>(src, dst, units, tid, stride); break;
+    }
+  }
+}
+
 // ---- fused per-timestep kernels --------------------------------------------
 // Dummy envs: one lane per env.  Reads features (8 B), value (4), state (4),
 // rdr[t] (4) [+ injected noise]; writes action (8 / 4), logp, value, reward,
@@ -437,6 +486,44 @@ RL8_API int rl8_rollout_scatter_f32(const void *action, int64_t action_row_bytes
       static_cast<const char *>(action), action_row_bytes, logp, value, reward, obs, obs_dim,
       static_cast<char *>(action_col), logp_col, value_col, reward_col, obs_col_next, rdr_t, rdr_t1,
       gamma, n);
+  return launch_status();
+}
+
+RL8_API int rl8_rollout_scatter_leaves_f32(const void *action, int64_t action_row_bytes, const float *logp,
+                                           const float *value, const float *reward,
+                                           const rl8_scatter_leaf *leaves, int n_leaves, void *action_col,
+                                           float *logp_col, float *value_col, float *reward_col, const float *rdr_t,
+                                           float *rdr_t1, float gamma, int64_t n, void *stream) {
+  if (!action || !logp || !value || !reward || !leaves || !action_col || !logp_col || !value_col || !reward_col)
+    return RL8_ENULL;
+  if ((rdr_t == nullptr) != (rdr_t1 == nullptr)) return RL8_ENULL;
+  if (n <= 0 || n_leaves <= 0 || n_leaves > RL8_MAX_GATHER_FIELDS || action_row_bytes <= 0 || action_row_bytes % 4)
+    return RL8_ESIZE;
+  for (int f = 0; f < n_leaves; ++f) {
+    if (!leaves[f].src || !leaves[f].dst) return RL8_ENULL;
+    if (leaves[f].row_bytes <= 0) return RL8_ESIZE;
+  }
+  for (const void *p : {action, (const void *)logp, (const void *)value, (const void *)reward,
+                        (const void *)action_col, (const void *)logp_col, (const void *)value_col,
+                        (const void *)reward_col, (const void *)rdr_t, (const void *)rdr_t1})
+    if (reinterpret_cast<uintptr_t>(p) & 3u) return RL8_EALIGN;
+  ScatterLeaves args;
+  args.count = n_leaves;
+  int64_t widest = n * (action_row_bytes / 4);
+  for (int f = 0; f < n_leaves; ++f) {
+    const int64_t bytes = n * leaves[f].row_bytes;
+    const uintptr_t low = reinterpret_cast<uintptr_t>(leaves[f].src) | reinterpret_cast<uintptr_t>(leaves[f].dst) |
+                          (uintptr_t)bytes;
+    const int unit = !(low & 15u) ? 16 : !(low & 7u) ? 8 : !(low & 3u) ? 4 : 1;
+    args.src[f] = static_cast<const char *>(leaves[f].src);
+    args.dst[f] = static_cast<char *>(leaves[f].dst);
+    args.unit[f] = unit;
+    args.units[f] = bytes / unit;
+    if (args.units[f] > widest) widest = args.units[f];
+  }
+  rollout_scatter_leaves_kernel<<<grid_for(widest, kBlock), kBlock, 0, (hipStream_t)stream>>>(
+      static_cast<const char *>(action), action_row_bytes, logp, value, reward, args,
+      static_cast<char *>(action_col), logp_col, value_col, reward_col, rdr_t, rdr_t1, gamma, n);
   return launch_status();
 }
 

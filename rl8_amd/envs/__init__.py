@@ -1,7 +1,8 @@
 """The reference's example environments (``examples/*/env.py``) as batched HIP kernels."""
 
+from .algotrading import AlgoTrading
 from .cartpole import CartPole, CartPoleConfig
 from .mountain_car import MountainCar, MountainCarConfig
 from .pendulum import Pendulum, PendulumConfig
 
-__all__ = ["CartPole", "CartPoleConfig", "MountainCar", "MountainCarConfig", "Pendulum", "PendulumConfig"]
+__all__ = ["AlgoTrading", "CartPole", "CartPoleConfig", "MountainCar", "MountainCarConfig", "Pendulum", "PendulumConfig"]

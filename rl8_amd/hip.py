@@ -91,6 +91,12 @@ class GatherField(C.Structure):
     ]
 
 
+class ScatterLeaf(C.Structure):
+    """``rl8_scatter_leaf`` (include/rl8_amd.h)."""
+
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64)]
+
+
 class GaePlanStruct(C.Structure):
     """``rl8_gae_plan_t`` (include/rl8_amd.h)."""
 
@@ -115,6 +121,12 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_categorical_sample_logp_f32": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _u64, _u64, _i64, _i32, _vp],
     "rl8_normal_sample_logp_f32": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u64, _u64, _i64, _i32, _vp],
     "rl8_rollout_scatter_f32": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _vp],
+    "rl8_rollout_scatter_leaves_f32": [_vp, _i64, _vp, _vp, _vp, C.POINTER(ScatterLeaf), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32,
+                                       _i64, _vp],
+    "rl8_algotrading_reset_f32": [_vp, _i64, _f32, _f32, _f32, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "rl8_algotrading_step_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "rl8_rollout_step_algotrading_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _u64,
+                                         _u64, _i64, _i32, _vp],
     "rl8_rollout_step_dummy_f32": [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _u64, _u64, _i64, _i32, _vp],
     "rl8_rollout_step_dummy_heads_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _u64,
                                          _u64, _i64, _i32, _vp],
@@ -460,6 +472,57 @@ def pendulum_reset(state: torch.Tensor, seed: int, reset_count: int, env_offset:
     _classic_reset("rl8_pendulum_reset_f32", 3, state, seed, reset_count, env_offset, obs_out)
 
 
+#: Rows of AlgoTrading's ``[9, N]`` state (``AlgoTradingState`` in csrc/device_math.hip.h).
+ALGOTRADING_STATE_ROWS = ("invested", "position", "f", "k_cyclic", "k_market", "t", "price", "LOG_CHANGE(price)",
+                          "LOG_CHANGE(price, position)")
+#: Its observation leaves, in the order the kernels take them, with dtype and row width.
+ALGOTRADING_LEAVES = (("action_mask", torch.bool, 3), ("invested", torch.int64, 1), ("LOG_CHANGE(price)", torch.float32, 1),
+                      ("LOG_CHANGE(price, position)", torch.float32, 1))
+
+
+def _algotrading_leaves(name: str, n: int, obs: Any) -> list[torch.Tensor]:
+    """The four leaf tensors of ``obs`` (a mapping by leaf name), checked: dense ``[N, d]`` of the leaf's dtype."""
+    out = []
+    for key, dtype, d in ALGOTRADING_LEAVES:
+        t = obs[key]
+        if t.dtype != dtype or t.numel() != n * d or not t.is_contiguous():
+            raise ValueError(f"{name}: leaf {key!r} must be a dense [N, {d}] {dtype} tensor")
+        out.append(t)
+    return out
+
+
+def algotrading_reset(state: torch.Tensor, f_bounds: float, k_cyclic_bounds: float, k_market_bounds: float, seed: int,
+                      reset_count: int, env_offset: int, obs_out: Any) -> None:
+    """examples/algotrading/env.py:80-129: state ``[9, N]`` drawn in place; ``obs_out`` maps the four leaf names to
+    ``[N, d]`` outputs."""
+    _dense(state, torch.float32, "state")
+    if state.ndim != 2 or state.shape[0] != len(ALGOTRADING_STATE_ROWS):
+        raise ValueError("rl8_algotrading_reset_f32: state must be [9,N]")
+    n = state.shape[1]
+    leaves = _algotrading_leaves("rl8_algotrading_reset_f32", n, obs_out)
+    with _timed("algotrading_reset", n):
+        _check(load().rl8_algotrading_reset_f32(_ptr(state), n, f_bounds, k_cyclic_bounds, k_market_bounds, seed,
+                                                reset_count, env_offset, *(_ptr(t) for t in leaves), _stream()),
+               "rl8_algotrading_reset_f32")
+
+
+def algotrading_step(state: torch.Tensor, action: torch.Tensor, obs_out: Any, reward_out: torch.Tensor) -> None:
+    """examples/algotrading/env.py:131-183: state ``[9, N]`` in place, action ``[N, 1]`` int64, the four leaves of
+    ``obs_out`` and reward_out ``[N, 1]`` written."""
+    _dense(state, torch.float32, "state")
+    _dense(action, torch.int64, "action")
+    _dense(reward_out, torch.float32, "reward_out")
+    if state.ndim != 2 or state.shape[0] != len(ALGOTRADING_STATE_ROWS):
+        raise ValueError("rl8_algotrading_step_f32: state must be [9,N]")
+    n = state.shape[1]
+    if action.numel() != n or reward_out.numel() != n:
+        raise ValueError("rl8_algotrading_step_f32: action [N,1], reward_out [N,1]")
+    leaves = _algotrading_leaves("rl8_algotrading_step_f32", n, obs_out)
+    with _timed("algotrading_step", n):
+        _check(load().rl8_algotrading_step_f32(_ptr(state), _ptr(action), *(_ptr(t) for t in leaves), _ptr(reward_out), n,
+                                               _stream()), "rl8_algotrading_step_f32")
+
+
 # --------------------------------------------------------------------------- #
 # Samplers.
 # --------------------------------------------------------------------------- #
@@ -549,6 +612,45 @@ def rollout_scatter(
         ),
         "rl8_rollout_scatter_f32",
     )
+
+
+def rollout_scatter_leaves(
+    action: torch.Tensor, logp: torch.Tensor, value: torch.Tensor, reward: torch.Tensor,
+    obs: Sequence[torch.Tensor], action_col: torch.Tensor, logp_col: torch.Tensor, value_col: torch.Tensor,
+    reward_col: torch.Tensor, obs_cols_next: Sequence[torch.Tensor], rdr_t: None | torch.Tensor,
+    rdr_t1: None | torch.Tensor, gamma: float,
+) -> None:
+    """``rollout_scatter`` for dict observations: ``obs[i]`` ``[N, ...]`` (any dtype) goes to ``obs_cols_next[i]`` in
+    the same launch as the five other columns."""
+    n = logp.shape[0]
+    for name, t in (("action", action), ("logp", logp), ("value", value), ("reward", reward),
+                    ("action_col", action_col), ("logp_col", logp_col), ("value_col", value_col),
+                    ("reward_col", reward_col), *((f"obs[{i}]", t) for i, t in enumerate(obs)),
+                    *((f"obs_cols_next[{i}]", t) for i, t in enumerate(obs_cols_next))):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if action.dtype != action_col.dtype or action.numel() != action_col.numel():
+        raise ValueError("action and action_col must match")
+    for name, t in (("logp", logp), ("value", value), ("reward", reward), ("logp_col", logp_col),
+                    ("value_col", value_col), ("reward_col", reward_col)):
+        if t.dtype != torch.float32 or t.numel() != n:
+            raise ValueError(f"{name} must hold one float32 per env")
+    if not obs or len(obs) != len(obs_cols_next) or len(obs) > MAX_GATHER_FIELDS:
+        raise ValueError(f"between 1 and {MAX_GATHER_FIELDS} observation leaves, as many columns")
+    leaves = (ScatterLeaf * len(obs))()
+    for i, (src, dst) in enumerate(zip(obs, obs_cols_next)):
+        if src.dtype != dst.dtype or src.numel() != dst.numel() or src.shape[0] != n or src.numel() == 0:
+            raise ValueError(f"obs[{i}] and obs_cols_next[{i}] must match ([N, ...], one dtype)")
+        leaves[i] = ScatterLeaf(_ptr(src), _ptr(dst), src.element_size() * (src.numel() // n))
+    with _timed("rollout_scatter_leaves", n):
+        _check(
+            load().rl8_rollout_scatter_leaves_f32(
+                _ptr(action), action.element_size() * (action.numel() // n), _ptr(logp), _ptr(value), _ptr(reward),
+                leaves, len(obs), _ptr(action_col), _ptr(logp_col), _ptr(value_col), _ptr(reward_col), _ptr(rdr_t),
+                _ptr(rdr_t1), gamma, n, _stream(),
+            ),
+            "rl8_rollout_scatter_leaves_f32",
+        )
 
 
 def rollout_step_dummy(
@@ -663,6 +765,40 @@ def rollout_step_pendulum(
         ),
         "rl8_rollout_step_pendulum_f32",
     )
+
+
+def rollout_step_algotrading(
+    *, logits: torch.Tensor, value: torch.Tensor, noise: None | torch.Tensor, state: torch.Tensor,
+    action_col: torch.Tensor, logp_col: torch.Tensor, value_col: torch.Tensor, reward_col: torch.Tensor,
+    obs_col_next: Any, rdr_t: None | torch.Tensor, rdr_t1: None | torch.Tensor, gamma: float, seed: int, step: int,
+    env_offset: int, deterministic: bool,
+) -> None:
+    """``obs_col_next`` maps the four leaf names to their ``t+1`` columns."""
+    name = "rollout_step_algotrading"
+    n = state.shape[1]
+    _check_step_tensors(name, [logits, value, state, action_col, logp_col, value_col, reward_col, noise, rdr_t, rdr_t1])
+    if state.shape[0] != len(ALGOTRADING_STATE_ROWS) or logits.numel() != 3 * n:
+        raise ValueError(f"{name}: state [9,N], logits [N,1,3]")
+    if action_col.dtype != torch.int64 or action_col.numel() != n:
+        raise ValueError(f"{name}: the action column must be [N,1] int64")
+    for t in (logits, value, state, logp_col, value_col, reward_col, noise, rdr_t, rdr_t1):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"{name}: float32 tensors expected")
+    for t in (value, logp_col, value_col, reward_col, rdr_t, rdr_t1):
+        if t is not None and t.numel() != n:
+            raise ValueError(f"{name}: column shape mismatch")
+    if noise is not None and noise.numel() != 3 * n:
+        raise ValueError(f"{name}: noise shape mismatch")
+    leaves = _algotrading_leaves(name, n, obs_col_next)
+    with _timed(name, n):
+        _check(
+            load().rl8_rollout_step_algotrading_f32(
+                _ptr(logits), _ptr(value), _ptr(noise), _ptr(state), _ptr(action_col), _ptr(logp_col), _ptr(value_col),
+                _ptr(reward_col), *(_ptr(t) for t in leaves), _ptr(rdr_t), _ptr(rdr_t1), gamma, n, seed, step,
+                env_offset, int(deterministic), _stream(),
+            ),
+            "rl8_rollout_step_algotrading_f32",
+        )
 
 
 def buffer_layout(leaf: torch.Tensor) -> tuple[int, int, int]:
