@@ -30,7 +30,7 @@
  *                called by the user), rl8_categorical_sample_logp_f32, rl8_normal_sample_logp_f32 (Distribution.sample())
  *     update     rl8_gae_scan_f32, rl8_advantage_normalise_f32 (their routes: rl8_gae_plan, rl8_advantage_normalise_route),
  *                rl8_ppo_loss_{categorical,normal}_fwd_bwd_f32,
- *                rl8_pack_samples, rl8_gather_packed, rl8_gather_minibatch
+ *                rl8_pack_samples, rl8_gather_packed, rl8_gather_minibatch, rl8_gather_sequences (dict observations)
  *     towers     rl8_mlp_tower_forward_f16_f32, rl8_mlp_tower_backward_gate_f16_f32, rl8_mlp_tower_backward_f16_f32,
  *                rl8_mlp_wgrad_gate_bits_f32, rl8_mlp_wgrad_fused_split_f32, rl8_mlp_wgrad_fused_pair_f32,
  *                rl8_mlp_pack_w2_f16, rl8_mlp_pack_w2_f16_gate, rl8_mlp_dout_pair_check, the *_supports / *_bytes /
@@ -40,6 +40,7 @@
  *                rl8_linear_heads_{forward,forward_pair,backward}_f32
  *     recurrent, hidden width 64 / 128 (model_config={"hidden_size": 64}): rl8_lstm_narrow_{forward,backward,reduce}_f32,
  *                rl8_lstm_narrow_backward_heads_f32 (one layer, heads of <= 4 outputs: the one-node training pass),
+ *                rl8_lstm_narrow_input_grad_f32 (dL/dx of layer 0, for models with an encoder in front of the LSTM),
  *                rl8_lstm_stack_* (layers 1..), rl8_linear_heads_narrow_{forward,forward_pair,backward}_f32,
  *                rl8_rollout_step_dummy_heads_narrow_f32 (the lean rollout's last launch of a timestep)
  *   PRODUCT, fallback (shapes outside the plane kernels' envelope -- d_in > 16, n_out > 8, hidden != 256 go to eager --
@@ -383,12 +384,20 @@ typedef struct {
   int64_t env_stride;  /* in elements */
   int64_t time_stride; /* in elements */
   int32_t row_elems;   /* trailing elements per (env, t) cell */
-  int32_t elem_bytes;  /* 4 or 8 */
+  int32_t elem_bytes;  /* 4 or 8 (rl8_gather_sequences: 1 as well) */
 } rl8_gather_field;
 
 #define RL8_MAX_GATHER_FIELDS 8
 
 int rl8_gather_minibatch(const int64_t *index, int64_t m, int64_t h,
+                         const rl8_gather_field *fields /*host*/, int n_fields, void *stream);
+
+/* Whole sequences, for the recurrent algorithm on dict observations: sequence q = env * (h / seq_len) + s is samples
+ * q seq_len + j, j < seq_len (the reference's numbering); row i seq_len + j of every dst receives
+ * src[env][s seq_len + j] for q = seq_index[i] (seq_index = NULL: q = i, every sequence in order, num_seqs of them).
+ * elem_bytes 1, 4 or 8 (RL8_ECONFIG otherwise), any row_elems >= 1: a bool[3] leaf is 3 bytes per row and moves byte
+ * by byte.  h a multiple of seq_len; src / dst aligned to elem_bytes (RL8_EALIGN). */
+int rl8_gather_sequences(const int64_t *seq_index, int64_t num_seqs, int seq_len, int64_t h,
                          const rl8_gather_field *fields /*host*/, int n_fields, void *stream);
 
 /* The same gather for a buffer that is shuffled many times per step()
@@ -812,7 +821,8 @@ int rl8_mlp_narrow_reduce_f32(const float *workspace, int64_t m, int hidden, int
  *   saved; writes the gate gradients and one partial slab of weight gradients per sequence chunk into `workspace`
  *   (rl8_lstm_narrow_workspace_bytes(b, l, ...) bytes, no initialisation); rl8_lstm_narrow_reduce_f32 then sums the
  *   slabs in a fixed order (fp64) into grads_out = [dW_ih (4H d_in) | dW_hh (4H H) | db (4H)] floats, db being the
- *   gradient of b_ih and of b_hh alike: bitwise reproducible.  No gradient for x, h0 or c0; c_n is not differentiable.
+ *   gradient of b_ih and of b_hh alike: bitwise reproducible.  No gradient for h0 or c0 (for x: the call of
+ *   rl8_lstm_narrow_input_grad_f32 below, where wanted); c_n is not differentiable.
  * Pointers 4-byte aligned, workspace 16-byte aligned; b >= 1, 1 <= l < 2^31 / (256 H); RL8_ESIZE for widths outside
  * the compiled set. */
 int rl8_lstm_narrow_supports(int hidden, int d_in);
@@ -835,6 +845,15 @@ int rl8_lstm_narrow_backward_heads_f32(const float *x, int64_t b, int l, int d_i
                                        const float *w_hh, int hidden, const float *hs, const float *gates,
                                        const float *cs, const float *heads_dout, const float *heads_w, float *workspace,
                                        void *stream);
+
+/* dL/dx of layer 0, for models with learned parameters in front of the LSTM (an embedding, an encoder):
+ * dx[n][k] = sum_j dz[n][j] w_ih[j][k] over the n = b l row-steps, j < 4H, k < d_in, from the gate gradients dz that
+ * rl8_lstm_narrow_backward_f32 / rl8_lstm_narrow_backward_heads_f32 left at the front of `workspace` (call it after
+ * either, with the same b, l, hidden, d_in; before or after the reduce).  w_ih [4H][d_in] in torch layout, dx
+ * [b][l][d_in] (exactly b l d_in floats are written).  fp32 MFMA in a fixed k order: bitwise reproducible and
+ * independent of the grid.  workspace 16-byte aligned, w_ih and dx 4-byte; sizes as for the other narrow entries. */
+int rl8_lstm_narrow_input_grad_f32(const float *workspace, int64_t b, int l, int d_in, const float *w_ih, int hidden,
+                                   float *dx, void *stream);
 
 /* ---- Output heads of the narrow recurrent models: Linear(H, n) layers on h [m][H], H = 64 or 128, evaluated together
  * (lstm_narrow_heads_kernels.hip): w [n_out][H] (the heads' weights stacked), b [n_out], n_out <= 8.

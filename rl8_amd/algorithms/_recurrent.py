@@ -17,7 +17,11 @@ shuffled -- its mean does not depend on the order of the sequences: they are lai
 sequence-major once per ``step()`` in buffer order and every SGD iteration reads
 that copy (the reference draws ``randperm`` and gathers per iteration,
 ``src/rl8/_utils.py:211-225``; ``bench.py --recurrent --minibatches 4`` times the
-shuffled path). A training pass through the default models is ONE autograd node
+shuffled path). Dict observations (a one-level ``Composite``, the feed-forward
+algorithm's leaf rules) are held leaf by leaf; their sequences are gathered by
+``rl8_gather_sequences``, which also takes byte-wide leaves (bool masks), and the
+model receives a tensordict of ``[B, L, ...]`` leaves. A training pass through the
+default models is ONE autograd node
 (``nn/fused_lstm.py:lstm_heads_forward``: ``_FusedLSTMHeads`` at hidden width 256,
 ``_NarrowLSTMHeads`` at 64 / 128): the heads' data gradient is formed inside the
 backward-through-time kernel.
@@ -144,6 +148,8 @@ class _LeanRollout:
         from ..nn import fused_lstm
 
         model = algo.policy.model
+        if DataKeys.OBS not in algo._tm:  # dict observations (held leaf by leaf): the lean launches read ONE slab
+            return False
         if type(model) is not DefaultDiscreteRecurrentModel or not isinstance(algo.env, DummyEnv):
             return False
         if algo.policy.distribution_cls is not Categorical or model.action_spec.shape[0] != 1:
@@ -243,8 +249,9 @@ class RecurrentAlgorithm(Algorithm):
     #: Issue the rollout's per-timestep launches through :class:`_LeanRollout` when the
     #: model / env pair allows it (False: always through ``policy.sample()``).
     lean_rollout: bool = True
-    #: Tensor observation specs only (dict observations belong to the feed-forward algorithm).
-    composite_observations = False
+    #: Dict observations under the feed-forward algorithm's leaf rules, with a model of the caller's (``model`` or
+    #: ``model_cls``): there is no default recurrent model for a dict.
+    composite_observations = True
 
     def __init__(self, env_cls: EnvFactory, /, config: None | RecurrentAlgorithmConfig = None) -> None:
         config = config or RecurrentAlgorithmConfig()
@@ -279,7 +286,26 @@ class RecurrentAlgorithm(Algorithm):
     def _make_state(self) -> RecurrentAlgorithmState:
         return RecurrentAlgorithmState()
 
+    def _composite_obs_leaves(self) -> None | list[str]:
+        leaves = super()._composite_obs_leaves()
+        config = self._recurrent_config
+        if leaves is not None and config.model is None and config.model_cls is None:
+            raise NotImplementedError(
+                "rl8_amd has no default recurrent model for dict observations: pass `model` or `model_cls`"
+                " (composite specs are outside the accelerated path)."
+            )
+        return leaves
+
     # -- helpers ----------------------------------------------------------------
+    def _obs_batch(self, t: int) -> TensorDict:
+        """Column ``t`` of the observations as the model's ``[N, 1]`` input batch: the slab, or a tensordict of the
+        leaves' slabs for dict observations."""
+        n = self.local_num_envs
+        if self._tm_obs is None:
+            return TensorDict({DataKeys.OBS: self._tm[DataKeys.OBS][t].unsqueeze(1)}, batch_size=[n, 1])
+        obs = TensorDict({leaf: storage[t].unsqueeze(1) for leaf, storage in self._tm_obs.items()}, batch_size=[n, 1])
+        return TensorDict({DataKeys.OBS: obs}, batch_size=[n, 1])
+
     def _state_slabs(self, t: int) -> TensorDict:
         """States at column ``t`` as a ``[N, 1, layers, hidden]`` tensordict."""
         n = self.local_num_envs
@@ -304,6 +330,8 @@ class RecurrentAlgorithm(Algorithm):
         H, N = hp.horizon, self.local_num_envs
         tm, stm = self._tm, self._tm_states
         rdr = tm.get(DataKeys.REVERSED_DISCOUNTED_RETURNS)
+        # the observation slabs: one for a tensor spec, one per leaf for a composite one
+        obs_slabs = self._tm_obs if self._tm_obs is not None else {None: tm[DataKeys.OBS]}
         self._flat_full = None  # (a sequence-major copy of the buffer this collect() overwrites)
         self._release_step_caches()
         with profile_ms() as collect_timer:
@@ -312,11 +340,14 @@ class RecurrentAlgorithm(Algorithm):
                 self.state.horizons % hp.horizons_per_env_reset
             )
             if carry:
-                tm[DataKeys.OBS][0].copy_(tm[DataKeys.OBS][H])
+                for storage in obs_slabs.values():
+                    storage[0].copy_(storage[H])
                 if rdr is not None:
                     rdr[0].copy_(rdr[H])
             else:
-                tm[DataKeys.OBS][0].copy_(self.env.reset(config=env_config))
+                first = self.env.reset(config=env_config)
+                for leaf, storage in obs_slabs.items():
+                    storage[0].copy_(first if leaf is None else first[leaf])
                 env_was_reset = True
                 if rdr is not None:
                     rdr[0].zero_()
@@ -344,7 +375,7 @@ class RecurrentAlgorithm(Algorithm):
                     if not ((t + 1) % hp.seq_len):
                         self.state.seqs += 1
                     continue
-                in_batch = TensorDict({DataKeys.OBS: tm[DataKeys.OBS][t].unsqueeze(1)}, batch_size=[N, 1])
+                in_batch = self._obs_batch(t)
                 if fused:
                     sample, new_states = self.policy.sample(
                         in_batch, self._state_slabs(t), deterministic=deterministic, inplace=False,
@@ -360,22 +391,32 @@ class RecurrentAlgorithm(Algorithm):
                         requires_grad=False, return_actions=True, return_logp=True, return_values=True,
                     )
                     out = self.env.step(sample[DataKeys.ACTIONS])
-                    hip.rollout_scatter(
-                        sample[DataKeys.ACTIONS].contiguous(), sample[DataKeys.LOGP].contiguous(),
-                        sample[DataKeys.VALUES].contiguous(), out[DataKeys.REWARDS].contiguous(),
-                        out[DataKeys.OBS].contiguous(), tm[DataKeys.ACTIONS][t], tm[DataKeys.LOGP][t],
-                        tm[DataKeys.VALUES][t], tm[DataKeys.REWARDS][t], tm[DataKeys.OBS][t + 1],
-                        rdr[t] if rdr is not None else None, rdr[t + 1] if rdr is not None else None, gamma,
-                    )
+                    if self._tm_obs is not None:
+                        obs = out[DataKeys.OBS]
+                        hip.rollout_scatter_leaves(
+                            sample[DataKeys.ACTIONS].contiguous(), sample[DataKeys.LOGP].contiguous(),
+                            sample[DataKeys.VALUES].contiguous(), out[DataKeys.REWARDS].contiguous(),
+                            [obs[leaf].contiguous() for leaf in self._tm_obs], tm[DataKeys.ACTIONS][t],
+                            tm[DataKeys.LOGP][t], tm[DataKeys.VALUES][t], tm[DataKeys.REWARDS][t],
+                            [storage[t + 1] for storage in self._tm_obs.values()],
+                            rdr[t] if rdr is not None else None, rdr[t + 1] if rdr is not None else None, gamma,
+                        )
+                    else:
+                        hip.rollout_scatter(
+                            sample[DataKeys.ACTIONS].contiguous(), sample[DataKeys.LOGP].contiguous(),
+                            sample[DataKeys.VALUES].contiguous(), out[DataKeys.REWARDS].contiguous(),
+                            out[DataKeys.OBS].contiguous(), tm[DataKeys.ACTIONS][t], tm[DataKeys.LOGP][t],
+                            tm[DataKeys.VALUES][t], tm[DataKeys.REWARDS][t], tm[DataKeys.OBS][t + 1],
+                            rdr[t] if rdr is not None else None, rdr[t + 1] if rdr is not None else None, gamma,
+                        )
                 for k, v in stm.items():  # :428
                     v[t + 1].copy_(new_states[k])
                 if not ((t + 1) % hp.seq_len):
                     self.state.seqs += 1
 
             # Bootstrap value at the last observation and state (:433-446).
-            in_batch = TensorDict({DataKeys.OBS: tm[DataKeys.OBS][H].unsqueeze(1)}, batch_size=[N, 1])
             sample, _ = self.policy.sample(
-                in_batch, self._state_slabs(H), deterministic=deterministic, inplace=False,
+                self._obs_batch(H), self._state_slabs(H), deterministic=deterministic, inplace=False,
                 requires_grad=False, return_actions=False, return_logp=False, return_values=True,
             )
             tm[DataKeys.VALUES][H].copy_(sample[DataKeys.VALUES])
@@ -421,7 +462,7 @@ class RecurrentAlgorithm(Algorithm):
 
     def _iter_minibatches(self, sgd_iter: int):
         """Minibatches of SEQUENCES: per-sample leaves as ``[B*L, ...]`` in
-        (sequence, step) order, observations as ``[B, L, ...]``, and each
+        (sequence, step) order (dict observations: a dict of such leaves), and each
         sequence's initial recurrent states ``[B, layers, hidden]``."""
         hp = self.hparams
         H, L = hp.horizon, hp.seq_len
@@ -447,8 +488,15 @@ class RecurrentAlgorithm(Algorithm):
             sample_ids = (seq_index[:, None] * L + steps[None, :]).reshape(-1).contiguous()
             # (the whole buffer in order: a transposition through LDS tiles, every byte moved once -- the indexed
             # gather reads a 64-byte sector per 4-byte cell of a time-major leaf)
-            gathered = hip.gather_minibatch(None if whole else sample_ids, H, [self.buffer[k] for k in self.TRAIN_KEYS])
-            batch = dict(zip(self.TRAIN_KEYS, gathered))
+            keys = [k for k in self.TRAIN_KEYS if k != DataKeys.OBS or self._tm_obs is None]
+            gathered = hip.gather_minibatch(None if whole else sample_ids, H, [self.buffer[k] for k in keys])
+            batch: dict[str, Any] = dict(zip(keys, gathered))
+            if self._tm_obs is not None:
+                # the leaves of a dict observation, byte-wide ones (bool masks) included: whole sequences in one launch
+                obs = self.buffer[DataKeys.OBS]
+                leaves = hip.gather_sequences(None if whole else seq_index.contiguous(), L, H,
+                                              [obs[leaf] for leaf in self._tm_obs])
+                batch[DataKeys.OBS] = dict(zip(self._tm_obs, leaves))
             first_ids = (seq_index * L).contiguous()
             states = hip.gather_minibatch(
                 first_ids, H, [self.buffer[DataKeys.STATES][k] for k in state_keys]
@@ -479,7 +527,11 @@ class RecurrentAlgorithm(Algorithm):
             stop = min(num_seqs, start + seqs_per_pass)
             b = stop - start
             rows = slice(start * L, stop * L)
-            obs = batch[DataKeys.OBS][rows].reshape(b, L, *batch[DataKeys.OBS].shape[1:])
+            if self._tm_obs is None:
+                obs = batch[DataKeys.OBS][rows].reshape(b, L, *batch[DataKeys.OBS].shape[1:])
+            else:
+                obs = TensorDict({leaf: v[rows].reshape(b, L, *v.shape[1:]) for leaf, v in batch[DataKeys.OBS].items()},
+                                 batch_size=[b, L])
             states = TensorDict(
                 {k: v[start:stop].unsqueeze(1) for k, v in batch["_states"].items()}, batch_size=[b, 1]
             )
@@ -564,7 +616,8 @@ class RecurrentAlgorithm(Algorithm):
         )
         # validate() must not leave anything behind in the buffer
         self._reset_buffer()
-        self._tm[DataKeys.OBS][self.hparams.horizon].zero_()
+        for storage in (self._tm_obs or {None: self._tm[DataKeys.OBS]}).values():
+            storage[self.hparams.horizon].zero_()
         for v in self._tm_states.values():
             v.zero_()
 

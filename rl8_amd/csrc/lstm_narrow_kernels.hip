@@ -31,7 +31,8 @@
 // 64 gate columns) workgroup with k over rows -- fp32 over 64 rows, fp64 beyond -- and
 // writes one slab per chunk; lstm_narrow_reduce_kernel adds the slabs in chunk order
 // in fp64.  Every grid is a function of b alone, so the gradients repeat bit for bit.
-// No gradient is formed for x, h0 or c0.
+// No gradient is formed for h0 or c0; the one for x is a launch of its own (lstm_narrow_input_grad_kernel, below the
+// stack kernels) for callers with learned parameters in front of the LSTM.
 //
 // LDS: forward [R][H + KIN + 4] (R = 32 / 16 rows at H = 64 / 128: 9-11 KiB), backward [32][4H + 4] (33 / 66 KiB),
 // weight gradient 64 rows of dz (64 columns) and of [h | x | 1] (<= 61 KiB).
@@ -858,6 +859,93 @@ int launch_stack_backward(hipStream_t s, const float *x, int64_t b, int l, const
   return launch_status();
 }
 
+// ---- Input gradient of layer 0 (a model with learned parameters in front of the LSTM: an embedding, an encoder):
+// dx[n][d_in] = dz[n][4H] x W_ih over n = b l row-steps, from the dz either backward entry left in the workspace.
+// One 16-column output tile (W_ih zero-padded from d_in in registers), 32 row-steps per workgroup tile as in
+// lstm_narrow_stack_dx_kernel.  There are only two 16 x 16 output blocks per tile, so the waves split k instead of the
+// columns: wave w multiplies gate columns [64w, 64w + 64) of both row blocks -- its A operand is 16 bytes per lane
+// straight from HBM (lane l: row l & 15, columns 64w + 16g + 4 (l >> 4) + e: the k-group layout of the operand maps
+// above, no LDS staging), the next tile's loads in flight during the products -- and leaves a [32][KIN] partial in
+// LDS; the partials are then added in wave order.  Every k order is fixed (within a wave g, e ascending on the MFMA's
+// fma chain, then waves ascending), so dx does not depend on the grid and repeats bit for bit.
+// HBM per row-step: 4H floats in, d_in out (1 KiB + 4 d_in bytes at H = 64, 2 KiB + 4 d_in at H = 128).
+// LDS: [H / 16][32][KIN + 4] floats (4 / 10 KiB at H = 64, 8 / 20 KiB at H = 128 for KIN = 4 / 16).
+template <int H, int KIN>
+__global__ __launch_bounds__(Geo<H>::kThreads, Geo<H>::kWgPerCU) void lstm_narrow_input_grad_kernel(
+    int64_t n, int d_in, const float *__restrict__ w_ih, const float *__restrict__ dz, float *__restrict__ dx) {
+  using G = Geo<H>;
+  constexpr int MT = kStackRows / 16, R = kStackRows, W = G::kWaves, KG = 4, PS = KIN + 4;
+  static_assert(16 * KG * W == 4 * H, "64 gate columns per wave");
+  __shared__ float part[W * R * PS];  // [W][R][PS]: each wave's partial sums
+  const int tid = threadIdx.x, lane = tid & 63, qq = lane >> 4, l16 = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  float wt[4 * KG];  // B operand: wt[4g + e] = W_ih[64 wave + 16g + 4qq + e][l16], zero past d_in
+#pragma unroll
+  for (int g = 0; g < KG; ++g)
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      wt[4 * g + e] = l16 < d_in ? w_ih[(int64_t)(64 * wave + 16 * g + 4 * qq + e) * d_in + l16] : 0.0f;
+
+  const int v_z = (l16 * 4 * H + 64 * wave + 4 * qq) * 4;  // row l16 of a 16-row block, this lane's 16 bytes of group 0
+  const int64_t tiles = (n + R - 1) / R;
+  u32x4 pv[MT][KG];  // (the next tile's operands in registers; rows past n fall outside the descriptor: zeros)
+  auto fetch = [&](int64_t ti) {
+    const int64_t n0 = ti * R;
+    const int rows = (int)(n - n0 < R ? n - n0 : R);
+    const __amdgpu_buffer_rsrc_t zr = buffer_rsrc(dz + n0 * 4 * H, (uint32_t)rows * 4 * H * 4);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int g = 0; g < KG; ++g)
+        pv[mt][g] = __builtin_amdgcn_raw_buffer_load_b128(zr, v_z + (16 * mt * 4 * H + 16 * g) * 4, 0, 0);
+  };
+  if ((int64_t)blockIdx.x < tiles) fetch(blockIdx.x);
+  for (int64_t ti = blockIdx.x; ti < tiles; ti += gridDim.x) {
+    const int64_t n0 = ti * R;
+    const int rows = (int)(n - n0 < R ? n - n0 : R);
+    u32x4 a[MT][KG];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int g = 0; g < KG; ++g) a[mt][g] = pv[mt][g];
+    if (ti + gridDim.x < tiles) fetch(ti + gridDim.x);  // lands during the products and the sum
+    f32x4 acc[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int g = 0; g < KG; ++g)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+          acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[mt][g][e]), wt[4 * g + e], acc[mt], 0, 0, 0);
+    __syncthreads();  // the previous tile's sum has read the partials
+    if (l16 < KIN) {
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part[(wave * R + 16 * mt + 4 * qq + r) * PS + l16] = acc[mt][r];
+    }
+    __syncthreads();
+    // (rows past n fall outside the descriptor: stores dropped)
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(dx + n0 * d_in, (uint32_t)(rows * d_in) * 4);
+    for (int o = tid; o < R * KIN; o += G::kThreads) {
+      const int row = o / KIN, col = o % KIN;
+      float s = part[row * PS + col];
+#pragma unroll
+      for (int w = 1; w < W; ++w) s += part[(w * R + row) * PS + col];
+      if (col < d_in) buffer_store_f32(s, xr, (row * d_in + col) * 4, 0);
+    }
+  }
+}
+
+template <int H, int KIN>
+int launch_input_grad(hipStream_t s, int64_t n, int d_in, const float *w_ih, const float *dz, float *dx) {
+  lstm_narrow_input_grad_kernel<H, KIN><<<stack_grid<H>(n), Geo<H>::kThreads, 0, s>>>(n, d_in, w_ih, dz, dx);
+  return launch_status();
+}
+
 inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 inline int slab_count(int hidden, int64_t b) {
@@ -981,6 +1069,22 @@ RL8_API int rl8_lstm_narrow_reduce_f32(const float *workspace, int64_t b, int l,
                                                                   lstm_narrow::slab_count(hidden, b), floats,
                                                                   grads_out);
   return launch_status();
+}
+
+// dL/dx of layer 0 from the dz that either backward entry above left at the front of `workspace`.
+RL8_API int rl8_lstm_narrow_input_grad_f32(const float *workspace, int64_t b, int l, int d_in, const float *w_ih,
+                                           int hidden, float *dx, void *stream) {
+  if (!workspace || !w_ih || !dx) return RL8_ENULL;
+  if (!lstm_narrow_sizes_ok(b, l, hidden) || !rl8_lstm_narrow_supports(hidden, d_in)) return RL8_ESIZE;
+  if (!aligned16(workspace) || !lstm_narrow::aligned4(w_ih) || !lstm_narrow::aligned4(dx)) return RL8_EALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = b * l;
+  const bool narrow_in = d_in <= 4;
+  if (hidden == 64)
+    return narrow_in ? lstm_narrow::launch_input_grad<64, 4>(s, n, d_in, w_ih, workspace, dx)
+                     : lstm_narrow::launch_input_grad<64, 16>(s, n, d_in, w_ih, workspace, dx);
+  return narrow_in ? lstm_narrow::launch_input_grad<128, 4>(s, n, d_in, w_ih, workspace, dx)
+                   : lstm_narrow::launch_input_grad<128, 16>(s, n, d_in, w_ih, workspace, dx);
 }
 
 // ---- Stacked LSTMs: one upper layer (its input is H floats wide) per call.

@@ -159,6 +159,38 @@ __global__ __launch_bounds__(kBlock) void gather_minibatch_kernel(
   }
 }
 
+// Whole sequences of seq_len samples (the recurrent algorithm's minibatches), leaves of 1-, 4- or 8-byte elements:
+// sequence q = env * (h / seq_len) + s is samples q seq_len + j, j < seq_len, and row i seq_len + j of every
+// destination receives src[env][s seq_len + j].  One lane per gathered row and field; a row of a byte-wide leaf (the
+// bool[3] action mask: 3 bytes, no word alignment) moves byte by byte.
+__global__ __launch_bounds__(kBlock) void gather_sequences_kernel(
+    const int64_t *__restrict__ seq_index, int64_t rows, int seq_len, int64_t h, GatherArgs args) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock, per_env = h / seq_len;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < rows; i += stride) {
+    const int64_t slot = i / seq_len, j = i - slot * seq_len;
+    const int64_t q = seq_index ? seq_index[slot] : slot;  // (seq_index = NULL: every sequence in order)
+    const int64_t env = q / per_env, t = (q - env * per_env) * seq_len + j;
+#pragma unroll 1
+    for (int f = 0; f < args.n_fields; ++f) {
+      const rl8_gather_field &fd = args.f[f];
+      const int64_t src0 = env * fd.env_stride + t * fd.time_stride;
+      if (fd.elem_bytes == 4) {
+        const uint32_t *src = static_cast<const uint32_t *>(fd.src) + src0;
+        uint32_t *dst = static_cast<uint32_t *>(fd.dst) + i * fd.row_elems;
+        for (int c = 0; c < fd.row_elems; ++c) dst[c] = src[c];
+      } else if (fd.elem_bytes == 8) {
+        const uint64_t *src = static_cast<const uint64_t *>(fd.src) + src0;
+        uint64_t *dst = static_cast<uint64_t *>(fd.dst) + i * fd.row_elems;
+        for (int c = 0; c < fd.row_elems; ++c) dst[c] = src[c];
+      } else {
+        const uint8_t *src = static_cast<const uint8_t *>(fd.src) + src0;
+        uint8_t *dst = static_cast<uint8_t *>(fd.dst) + i * fd.row_elems;
+        for (int c = 0; c < fd.row_elems; ++c) dst[c] = src[c];
+      }
+    }
+  }
+}
+
 // K5b: packed sample rows.  A shuffled minibatch reads every field of a sample
 // from a different random address: five 4/8-byte reads, five 32/64-byte sectors,
 // ~12x the algorithmic bytes (PMC).  When a buffer is going to be shuffled
@@ -433,6 +465,27 @@ RL8_API int rl8_gather_minibatch(const int64_t *index, int64_t m, int64_t h,
   }
   if (args.n_fields > 0)
     gather_minibatch_kernel<<<grid_for(m, kBlock), kBlock, 0, s>>>(index, m, h, args);
+  return launch_status();
+}
+
+RL8_API int rl8_gather_sequences(const int64_t *seq_index, int64_t num_seqs, int seq_len, int64_t h,
+                                 const rl8_gather_field *fields, int n_fields, void *stream) {
+  if (!fields) return RL8_ENULL;
+  if (num_seqs <= 0 || seq_len <= 0 || h <= 0 || h % seq_len || n_fields <= 0 || n_fields > RL8_MAX_GATHER_FIELDS)
+    return RL8_ESIZE;
+  GatherArgs args;
+  args.n_fields = n_fields;
+  for (int f = 0; f < n_fields; ++f) {
+    const rl8_gather_field &fd = fields[f];
+    if (!fd.src || !fd.dst) return RL8_ENULL;
+    if (fd.elem_bytes != 1 && fd.elem_bytes != 4 && fd.elem_bytes != 8) return RL8_ECONFIG;
+    if (fd.row_elems <= 0) return RL8_ESIZE;
+    const uintptr_t mask = (uintptr_t)fd.elem_bytes - 1;
+    if ((reinterpret_cast<uintptr_t>(fd.src) & mask) || (reinterpret_cast<uintptr_t>(fd.dst) & mask)) return RL8_EALIGN;
+    args.f[f] = fd;
+  }
+  const int64_t rows = num_seqs * seq_len;
+  gather_sequences_kernel<<<grid_for(rows, kBlock), kBlock, 0, (hipStream_t)stream>>>(seq_index, rows, seq_len, h, args);
   return launch_status();
 }
 

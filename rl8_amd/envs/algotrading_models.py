@@ -1,0 +1,85 @@
+"""Built-in models for :class:`~rl8_amd.envs.AlgoTrading`.
+
+``LSTMTrader`` is the recurrent one: an embedding of ``invested`` and the two price log-changes go through an LSTM
+whose latents feed a logits head and a value head. At hidden width 64 / 128 a training pass is one fused autograd
+node (``nn/fused_lstm.py:lstm_heads_forward``) that also returns the gradient of the LSTM's input, which is what
+trains the embedding; at any other width the ``nn.LSTM`` module itself runs, so the embedding always has a gradient.
+
+"""
+
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from ..data import DataKeys, Device
+from ..models_recurrent import RecurrentModel, _lstm_state_spec, _run_lstm_heads, _small_head
+from ..specs import TensorSpec
+from ..tensordict import TensorDict
+
+
+class LSTMTrader(RecurrentModel):
+    """``Embedding(2, invested_embed_dim)`` on ``invested``, concatenated with ``LOG_CHANGE(price, position)`` and
+    ``LOG_CHANGE(price)`` -> ``LSTM(invested_embed_dim + 2, hidden_size)`` -> a small-initialised ``Linear(hidden, 3)``
+    logits head, masked by ``log(action_mask)``, and a ``Linear(hidden, 1)`` value head."""
+
+    def __init__(
+        self,
+        observation_spec: TensorSpec,
+        action_spec: TensorSpec,
+        /,
+        *,
+        invested_embed_dim: int = 2,
+        hidden_size: int = 64,
+    ) -> None:
+        super().__init__(observation_spec, action_spec, invested_embed_dim=invested_embed_dim, hidden_size=hidden_size)
+        self.state_spec = _lstm_state_spec(1, hidden_size, action_spec.device)
+        self.invested_embedding = nn.Embedding(2, invested_embed_dim)
+        self.lstm = nn.LSTM(invested_embed_dim + 2, hidden_size, num_layers=1, batch_first=True)
+        self.feature_head = _small_head(hidden_size, 3)
+        self.vf_head = nn.Linear(hidden_size, 1)
+        self._value: None | torch.Tensor = None
+
+    def forward(self, batch: TensorDict, states: TensorDict, /) -> tuple[TensorDict, TensorDict]:
+        from ..nn import fused_lstm
+
+        obs = batch[DataKeys.OBS]
+        invested = obs["invested"]  # [B, T, 1] int64
+        b, t = invested.shape[:2]
+        x = torch.cat(
+            [
+                self.invested_embedding(invested.reshape(b, t)),
+                obs["LOG_CHANGE(price, position)"],
+                obs["LOG_CHANGE(price)"],
+            ],
+            dim=-1,
+        )
+        heads = [self.feature_head, self.vf_head]
+        if fused_lstm._family(self.lstm) in ("narrow", "stack"):
+            # the fused families that return dL/dx: the embedding is trained through the kernels
+            outs, new_states = _run_lstm_heads(self.lstm, heads, x, states)
+        else:
+            # (no fused family forms a gradient for x at this width: the module, as models_recurrent._run_lstm runs it)
+            h_0 = states[DataKeys.HIDDEN_STATES][:, 0, ...].permute(1, 0, 2).contiguous()
+            c_0 = states[DataKeys.CELL_STATES][:, 0, ...].permute(1, 0, 2).contiguous()
+            with torch.backends.cudnn.flags(enabled=False):
+                latents, (h_n, c_n) = self.lstm(x, (h_0, c_0))
+            outs = [head(latents) for head in heads]
+            new_states = TensorDict(
+                {DataKeys.HIDDEN_STATES: h_n.permute(1, 0, 2), DataKeys.CELL_STATES: c_n.permute(1, 0, 2)}, batch_size=b
+            )
+        mask = torch.clamp(torch.log(obs["action_mask"].float()), min=torch.finfo(torch.float32).min)
+        logits = outs[0].reshape(-1, 1, 3) + mask.reshape(-1, 1, 3)
+        self._value = outs[1].reshape(-1, 1)
+        return TensorDict({"logits": logits}, batch_size=logits.size(0), device=x.device), new_states
+
+    def to(self, device: Device) -> "LSTMTrader":  # type: ignore[override]
+        self._value = None
+        return super().to(device)  # type: ignore[return-value]
+
+    def value_function(self) -> torch.Tensor:
+        assert self._value is not None
+        return self._value
+
+
+__all__ = ["LSTMTrader"]

@@ -147,6 +147,7 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_ppo_loss_categorical_fwd_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(PPOHparams), _vp, _vp, _vp, _vp, _vp],
     "rl8_ppo_loss_normal_fwd_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(PPOHparams), _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_gather_minibatch": [_vp, _i64, _i64, C.POINTER(GatherField), _i32, _vp],
+    "rl8_gather_sequences": [_vp, _i64, _i32, _i64, C.POINTER(GatherField), _i32, _vp],
     "rl8_pack_samples": [_vp, _i32, _i64, _i64, _vp, _i32, _vp],
     "rl8_gather_packed": [_vp, _i64, _vp, _i32, _vp, _i32, _vp],
     "rl8_lstm_supports": [_i32],
@@ -208,6 +209,7 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_lstm_narrow_backward_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_lstm_narrow_reduce_f32": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
     "rl8_lstm_narrow_backward_heads_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rl8_lstm_narrow_input_grad_f32": [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp],
     "rl8_linear_heads_narrow_workspace_bytes": [_i64, _i32, _i32],
     "rl8_linear_heads_narrow_forward_f32": [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp],
     "rl8_linear_heads_narrow_forward_pair_f32": [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp],
@@ -1002,6 +1004,44 @@ def gather_minibatch(index: None | torch.Tensor, h: int, leaves: Sequence[torch.
     return outs
 
 
+def gather_sequences(seq_index: None | torch.Tensor, seq_len: int, h: int,
+                     leaves: Sequence[torch.Tensor]) -> list[torch.Tensor]:
+    """Whole sequences of ``seq_len`` samples out of [N, T, ...] buffer leaves (any stride over env / time, dense over
+    the rest; elements of 1, 4 or 8 bytes: bool masks beside int64 and float32 leaves): sequence
+    ``q = env * (h // seq_len) + s`` is samples ``q * seq_len + j`` (the reference's numbering). ``seq_index`` [S]
+    int64, or None for every sequence in order (``S = N * h // seq_len``). Returns dense ``[S * seq_len, ...]``
+    tensors of the leaves' dtypes, row ``i * seq_len + j`` holding ``leaf[env, s * seq_len + j]``."""
+    if seq_len < 1 or h < 1 or h % seq_len:
+        raise ValueError(f"gather_sequences: h={h} must be a positive multiple of seq_len={seq_len}")
+    if seq_index is None:
+        num_seqs = leaves[0].shape[0] * (h // seq_len)
+    else:
+        _dense(seq_index, torch.int64, "seq_index")
+        num_seqs = seq_index.numel()
+    if len(leaves) > MAX_GATHER_FIELDS:
+        raise ValueError(f"at most {MAX_GATHER_FIELDS} leaves per gather")
+    rows = num_seqs * seq_len
+    fields = (GatherField * len(leaves))()
+    outs = []
+    for i, leaf in enumerate(leaves):
+        if leaf.ndim < 2 or leaf.shape[1] < h:
+            raise ValueError(f"leaves must be [N, T >= {h}, ...]")
+        trailing = leaf.shape[2:]
+        row, expect = 1, 1
+        for d, st in zip(reversed(trailing), reversed(leaf.stride()[2:])):
+            if d != 1 and st != expect:
+                raise ValueError("leaf trailing dims must be dense")
+            expect *= d
+            row *= d
+        dst = torch.empty((rows, *trailing), dtype=leaf.dtype, device=leaf.device)
+        fields[i] = GatherField(_ptr(leaf), _ptr(dst), leaf.stride(0), leaf.stride(1), row, leaf.element_size())
+        outs.append(dst)
+    with _timed("gather_sequences", rows):
+        _check(load().rl8_gather_sequences(_ptr(seq_index) if seq_index is not None else None, num_seqs, seq_len, h,
+                                           fields, len(leaves), _stream()), "rl8_gather_sequences")
+    return outs
+
+
 class PackedSamples:
     """The training fields of every sample of a rollout buffer, side by side in
     the reference's sample order (``rl8_pack_samples``); ``gather(index)`` returns
@@ -1635,11 +1675,16 @@ def lstm_narrow_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_i
 
 def lstm_narrow_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_hh: torch.Tensor, hs: torch.Tensor,
                          gates: torch.Tensor, cs: torch.Tensor, dhs: None | torch.Tensor, *,
-                         heads: None | tuple[torch.Tensor, torch.Tensor] = None) -> dict[str, torch.Tensor]:
+                         heads: None | tuple[torch.Tensor, torch.Tensor] = None,
+                         w_ih: None | torch.Tensor = None) -> dict[str, torch.Tensor]:
     """Gradients ("w_ih", "w_hh", "b": of b_ih and b_hh alike) for dL/dhs ``dhs`` [B, L, H], from what
     :func:`lstm_narrow_forward` saved: backward through time, partial slabs per sequence chunk summed in a fixed
-    order (deterministic). No gradient for x, h0, c0. ``heads`` = (dout [B * L, n], w [n, H]), n <= 4, instead of
-    ``dhs`` (None): dL/dh_t = dout x w is formed inside the backward through time (rl8_lstm_narrow_backward_heads_f32)."""
+    order (deterministic). No gradient for h0, c0. ``heads`` = (dout [B * L, n], w [n, H]), n <= 4, instead of
+    ``dhs`` (None): dL/dh_t = dout x w is formed inside the backward through time (rl8_lstm_narrow_backward_heads_f32).
+    ``w_ih`` [4H, d_in] given: one more launch (rl8_lstm_narrow_input_grad_f32, timed as "lstm_narrow_input_grad")
+    forms "dx" [B, L, d_in] = dz x w_ih, the gradient of x, from the gate gradients in the workspace, which are then
+    returned as well ("dz" [B, L, 4, H], a view of the workspace). Without it: no gradient for x, nothing more launched
+    or allocated."""
     if (heads is None) == (dhs is None):
         raise ValueError("lstm_narrow_backward: either dhs or heads")
     x, h0, c0, w_hh, hs, gates, cs = (t.detach() for t in (x, h0, c0, w_hh, hs, gates, cs))
@@ -1671,8 +1716,17 @@ def lstm_narrow_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_
     with _timed("lstm_narrow_reduce", b * l):
         _check(lib.rl8_lstm_narrow_reduce_f32(_ptr(ws), b, l, hidden, d_in, _ptr(grads), _stream()),
                "rl8_lstm_narrow_reduce_f32")
-    w_ih, w_hh_grad, db = torch.split(grads, sizes)
-    return {"w_ih": w_ih.view(4 * hidden, d_in), "w_hh": w_hh_grad.view(4 * hidden, hidden), "b": db}
+    w_ih_grad, w_hh_grad, db = torch.split(grads, sizes)
+    out = {"w_ih": w_ih_grad.view(4 * hidden, d_in), "w_hh": w_hh_grad.view(4 * hidden, hidden), "b": db}
+    if w_ih is not None:
+        w_ih = _shaped(w_ih.detach(), (4 * hidden, d_in), "w_ih")
+        dx = torch.empty(b, l, d_in, dtype=torch.float32, device=x.device)
+        with _timed("lstm_narrow_input_grad", b * l):
+            _check(lib.rl8_lstm_narrow_input_grad_f32(_ptr(ws), b, l, d_in, _ptr(w_ih), hidden, _ptr(dx), _stream()),
+                   "rl8_lstm_narrow_input_grad_f32")
+        out["dx"] = dx
+        out["dz"] = ws[:b * l * 4 * hidden].view(b, l, 4, hidden)
+    return out
 
 
 # --------------------------------------------------------------------------- #

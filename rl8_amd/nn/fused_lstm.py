@@ -26,6 +26,11 @@ forms the heads' data gradient itself (``lstm_heads_forward``); the reference's 
 ``nn.LSTM(d_in, 256, batch_first=True)`` (``src/rl8/models/_recurrent.py:201-321``), its example around
 ``nn.LSTM(4, 64)``.
 
+The "narrow" and "stack" families return the gradient of their input ``x`` where it requires one -- a model with
+learned parameters in front of the LSTM, such as ``rl8_amd.envs.LSTMTrader``'s embedding -- from one more launch on
+the gate gradients the backward through time has left (``rl8_lstm_narrow_input_grad_f32``); an ``x`` that is
+rollout-buffer data costs nothing. The "256" family forms no input gradient.
+
 """
 
 from __future__ import annotations
@@ -198,26 +203,33 @@ class _FusedLSTM(torch.autograd.Function):
         return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None, None, None
 
 
+def _input_grad_args(ctx, w_ih: torch.Tensor) -> dict[str, torch.Tensor]:
+    """``hip.lstm_narrow_backward``'s ``w_ih=`` (layer 0's: it then returns "dx") exactly when the node's ``x``
+    requires a gradient; nothing otherwise: the call, its launches and its allocations are those of a pass without."""
+    return {"w_ih": w_ih} if ctx.needs_input_grad[0] else {}
+
+
 class _NarrowLSTM(torch.autograd.Function):
     """A hidden-64 / 128 LSTM: the weights are read in torch layout (nothing packed, nothing cached); a training
-    pass saves the gates and cell states for the backward through time."""
+    pass saves the gates and cell states for the backward through time. Where ``x`` requires a gradient (learned
+    parameters in front of the LSTM) the backward adds one launch, dL/dx = dz x W_ih (``_input_grad_args``)."""
 
     @staticmethod
     def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, grad_mode):  # type: ignore[override]
-        need_grad = grad_mode and any(ctx.needs_input_grad[3:7])
+        need_grad = grad_mode and (any(ctx.needs_input_grad[3:7]) or ctx.needs_input_grad[0])
         hs, _, cn, gates, cs = hip.lstm_narrow_forward(x, h0, c0, w_ih, w_hh, b_ih, b_hh, save=need_grad)
         ctx.set_materialize_grads(False)
         if need_grad:
-            ctx.save_for_backward(x, h0, c0, w_hh, hs, gates, cs)
+            ctx.save_for_backward(x, h0, c0, w_ih, w_hh, hs, gates, cs)
         ctx.mark_non_differentiable(cn)
         return hs, cn
 
     @staticmethod
     def backward(ctx, dhs, dcn):  # type: ignore[override]
-        x, h0, c0, w_hh, hs, gates, cs = ctx.saved_tensors
+        x, h0, c0, w_ih, w_hh, hs, gates, cs = ctx.saved_tensors
         dhs = torch.zeros_like(hs) if dhs is None else dhs.contiguous().float()
-        g = hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, dhs)
-        return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None
+        g = hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, dhs, **_input_grad_args(ctx, w_ih))
+        return g.get("dx"), None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None
 
 
 def _lstm_heads_backward(hs, w_heads, dout, dhs, heads_backward, lstm_backward):
@@ -238,24 +250,26 @@ def _lstm_heads_backward(hs, w_heads, dout, dhs, heads_backward, lstm_backward):
 class _NarrowLSTMHeads(torch.autograd.Function):
     """:class:`_NarrowLSTM` + output heads of a training pass as one node, as :class:`_FusedLSTMHeads` is at 256: the
     heads' data gradient dL/dh_t = dOut x W (n <= 4) is formed inside the backward through time from the 16 bytes
-    per row-step it is made of, instead of being written as [B, L, H] by the heads' backward and read back."""
+    per row-step it is made of, instead of being written as [B, L, H] by the heads' backward and read back. dL/dx
+    as in :class:`_NarrowLSTM`, where ``x`` requires it."""
 
     @staticmethod
     def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, w_heads, b_heads):  # type: ignore[override]
         hs, _, cn, gates, cs = hip.lstm_narrow_forward(x, h0, c0, w_ih, w_hh, b_ih, b_hh, save=True)
         out = hip.linear_heads_narrow_forward(hs.view(-1, hs.shape[2]), w_heads, b_heads)
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(x, h0, c0, w_hh, hs, gates, cs, w_heads)
+        ctx.save_for_backward(x, h0, c0, w_ih, w_hh, hs, gates, cs, w_heads)
         ctx.mark_non_differentiable(cn)
         return out, hs, cn
 
     @staticmethod
     def backward(ctx, dout, dhs, dcn):  # type: ignore[override]
-        x, h0, c0, w_hh, hs, gates, cs, w_heads = ctx.saved_tensors
+        x, h0, c0, w_ih, w_hh, hs, gates, cs, w_heads = ctx.saved_tensors
         g, dw, db = _lstm_heads_backward(
             hs, w_heads, dout, dhs, hip.linear_heads_narrow_backward,
-            lambda dhs, heads: hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, dhs, heads=heads))
-        return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], dw, db
+            lambda dhs, heads: hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, dhs, heads=heads,
+                                                        **_input_grad_args(ctx, w_ih)))
+        return g.get("dx"), None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], dw, db
 
 
 _STACK_PARAMS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
@@ -265,12 +279,13 @@ class _StackLSTM(torch.autograd.Function):
     """A stack of hidden-64 / 128 layers as one node: layer 0 on the narrow kernels, every upper layer on the stack
     kernels, each reading the lower layer's ``hs`` where the kernel left it (no torch op between the layers). The
     weights are read in torch layout, nothing packed or cached. ``h0`` / ``c0`` and the returned states are
-    [layers, B, H]; a training pass saves every layer's ``hs``, gates and cell states."""
+    [layers, B, H]; a training pass saves every layer's ``hs``, gates and cell states. dL/dx comes from layer 0 as
+    in :class:`_NarrowLSTM`, where ``x`` requires it."""
 
     @staticmethod
     def forward(ctx, x, h0, c0, grad_mode, *weights):  # type: ignore[override]
         layers = len(weights) // 4
-        need_grad = grad_mode and any(ctx.needs_input_grad[4:])
+        need_grad = grad_mode and (any(ctx.needs_input_grad[4:]) or ctx.needs_input_grad[0])
         b, l, hidden = x.shape[0], x.shape[1], h0.shape[2]
         hn, cn = torch.empty_like(h0), torch.empty_like(c0)
         zin = torch.empty(b, l, 4, hidden, dtype=torch.float32, device=x.device)  # the projections' scratch
@@ -299,18 +314,18 @@ class _StackLSTM(torch.autograd.Function):
             g = hip.lstm_stack_backward(saved[5 * (k - 1) + 2], h0[k], c0[k], w_ih, w_hh, hs, gates, cs, dhs)
             grads[4 * k:4 * k + 4] = g["w_ih"], g["w_hh"], g["b"], g["b"]
             dhs = g["dx"]  # dL/dx of layer k is dL/dhs of layer k - 1: nothing else reads that layer's outputs
-        _, w_hh, hs, gates, cs = saved[:5]
-        g = hip.lstm_narrow_backward(x, h0[0], c0[0], w_hh, hs, gates, cs, dhs)
+        w_ih, w_hh, hs, gates, cs = saved[:5]
+        g = hip.lstm_narrow_backward(x, h0[0], c0[0], w_hh, hs, gates, cs, dhs, **_input_grad_args(ctx, w_ih))
         grads[:4] = g["w_ih"], g["w_hh"], g["b"], g["b"]
-        return (None, None, None, None, *grads)
+        return (g.get("dx"), None, None, None, *grads)
 
 
 def lstm_stack_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
     """``lstm(x, (h0, c0))`` for a stack of two or more layers of width 64 / 128: ``x`` [B, L, d], ``h0`` / ``c0``
     [B, layers, H] (the rollout buffer's layout) -> ``(hs_top [B, L, H], h_n [B, layers, H], c_n [B, layers, H])``,
     or ``None`` when this LSTM / input is not eligible (one layer, other widths, d > 16, no bias, dropout,
-    projections, bidirectional, non-HIP / non-fp32 inputs). No gradient flows to ``x``, ``h0``, ``c0`` nor out of
-    ``h_n``, ``c_n``."""
+    projections, bidirectional, non-HIP / non-fp32 inputs). ``x`` receives its gradient where it requires one (layer
+    0's dz x W_ih, one more launch); none flows to ``h0``, ``c0`` nor out of ``h_n``, ``c_n``."""
     if _family_for(lstm, x) != "stack":
         return None
     weights = [getattr(lstm, f"{name}_l{k}") for k in range(lstm.num_layers) for name in _STACK_PARAMS]
@@ -325,8 +340,10 @@ def lstm_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Ten
     """``lstm(x, (h0[None], c0[None]))`` for ``x`` [B, L, d], ``h0`` / ``c0`` [B, H]
     through the fused kernels: ``(hs [B, L, H], h_n [B, H], c_n [B, H])``, or
     ``None`` when this LSTM / input is not eligible (H = 256 with d <= 7, or H = 64 /
-    128 with d <= 16). No gradient flows to ``x``, ``h0``, ``c0`` (rollout-buffer
-    data) nor out of ``c_n``."""
+    128 with d <= 16). No gradient flows to ``h0``, ``c0`` (rollout-buffer data) nor
+    out of ``c_n``. At H = 64 / 128 ``x`` receives its gradient where it requires one
+    (an encoder in front of the LSTM: one more launch, dz x W_ih); at H = 256 no
+    gradient flows to ``x``."""
     family = _family_for(lstm, x)
     if family not in ("256", "narrow"):  # (a stack has its own entry and state layout: lstm_stack_forward)
         return None
@@ -405,7 +422,8 @@ def lstm_heads_forward(lstm: nn.LSTM, heads: list[nn.Linear], x: torch.Tensor, h
     (:class:`_FusedLSTMHeads` at H = 256, :class:`_NarrowLSTMHeads` at 64 / 128):
     ``([head_i(hs) as [B * L, n_i]], hs [B, L, H], h_n, c_n)``, or ``None`` when this combination is not eligible (no
     gradient wanted, a stack, more than four head outputs, the heads switched off or -- at 256 -- a plan that does not
-    fuse them): the caller then runs :func:`lstm_forward` / :func:`lstm_stack_forward` and :func:`heads_forward`."""
+    fuse them): the caller then runs :func:`lstm_forward` / :func:`lstm_stack_forward` and :func:`heads_forward`.
+    The gradient of ``x`` is as in :func:`lstm_forward`: formed at H = 64 / 128 where ``x`` requires it, none at 256."""
     family = _family_for(lstm, x) if torch.is_grad_enabled() else None
     if family not in ("256", "narrow"):
         return None
