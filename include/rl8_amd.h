@@ -31,6 +31,10 @@
  *     update     rl8_gae_scan_f32, rl8_advantage_normalise_f32 (their routes: rl8_gae_plan, rl8_advantage_normalise_route),
  *                rl8_ppo_loss_{categorical,normal}_fwd_bwd_f32,
  *                rl8_pack_samples, rl8_gather_packed, rl8_gather_minibatch, rl8_gather_sequences (dict observations)
+ *     windows    (feed-forward models with padded rolling-window view requirements on "obs" / ("obs", leaf), and dict
+ *                observations; RL8_AMD_WINDOW_KERNELS=0 puts both back on torch ops) rl8_window_last (collect(): the
+ *                model's input at every timestep and at the bootstrap value), rl8_gather_windows (step(): the
+ *                observation views of every minibatch)
  *     towers     rl8_mlp_tower_forward_f16_f32, rl8_mlp_tower_backward_gate_f16_f32, rl8_mlp_tower_backward_f16_f32,
  *                rl8_mlp_wgrad_gate_bits_f32, rl8_mlp_wgrad_fused_split_f32, rl8_mlp_wgrad_fused_pair_f32,
  *                rl8_mlp_pack_w2_f16, rl8_mlp_pack_w2_f16_gate, rl8_mlp_dout_pair_check, the *_supports / *_bytes /
@@ -87,7 +91,8 @@ extern "C" {
  * grew by 1 MiB + 16, and rl8_lstm_rows_backward_heads_f32 reads them; rl8_mlp_backward_f16_supports and
  * rl8_lstm_split_supports report wider envelopes; the weight-gradient workspace's tail words moved).  Added under 106
  * without a bump (new entries only, nothing existing changed): rl8_rollout_scatter_leaves_f32,
- * rl8_algotrading_reset_f32, rl8_algotrading_step_f32, rl8_rollout_step_algotrading_f32. */
+ * rl8_algotrading_reset_f32, rl8_algotrading_step_f32, rl8_rollout_step_algotrading_f32, rl8_gather_windows,
+ * rl8_window_last. */
 #define RL8_ABI_VERSION 106
 int rl8_abi_version(char *arch, int arch_len);
 
@@ -399,6 +404,36 @@ int rl8_gather_minibatch(const int64_t *index, int64_t m, int64_t h,
  * by byte.  h a multiple of seq_len; src / dst aligned to elem_bytes (RL8_EALIGN). */
 int rl8_gather_sequences(const int64_t *seq_index, int64_t num_seqs, int seq_len, int64_t h,
                          const rl8_gather_field *fields /*host*/, int n_fields, void *stream);
+
+/* Padded rolling windows                src/rl8/views.py:54-123 (pad_last_sequence, pad_whole_sequence), 240-321
+ * A field is a buffer leaf as in rl8_gather_field (elem_bytes 1, 4 or 8, any row_elems >= 1) and a window length
+ * size = shift + 1 >= 1.  Cell j < size of the window that ends at step t of an env is step t' = t - (size - 1) + j:
+ *   dst[i][j][:] = src[env][t'][:] and mask[i][j] = 0 where t' >= 0, zeros and mask[i][j] = 1 where t' < 0
+ * (dst dense [rows][size][row_elems], mask dense [rows][size] bytes).  size = 1 is the plain gather, dst [rows]
+ * [row_elems], and its mask is not read (NULL is fine); fields of different sizes share one launch, so the unwindowed
+ * leaves of a dict observation ride along.
+ * rl8_gather_windows: row i is sample s = index[i] (env = s / h, t = s % h), index = NULL: s = i, every sample in
+ *   order; m rows.  What PaddedRollingWindow.apply_all followed by an index gives.
+ * rl8_window_last: row i is env i at the given step t >= 0 (the caller keeps t within the leaf); n rows.  What
+ *   pad_last_sequence gives on the leaf's first t + 1 steps.  Lanes run over envs within a window cell, so each source
+ *   column of a time-major slab is read as one contiguous run.
+ * RL8_ENULL: fields, a src or a dst is NULL.  RL8_ESIZE: m, h, n < 1, t < 0, n_fields outside 1 ..
+ * RL8_MAX_GATHER_FIELDS, row_elems < 1, size < 1.  RL8_ECONFIG: elem_bytes not 1, 4 or 8; size > 1 without a mask.
+ * RL8_EALIGN: src or dst not aligned to elem_bytes. */
+typedef struct {
+  const void *src;
+  void *dst;
+  uint8_t *mask;       /* [rows][size]; NULL when size == 1 */
+  int64_t env_stride;  /* in elements */
+  int64_t time_stride; /* in elements */
+  int32_t row_elems;   /* trailing elements per (env, t) cell */
+  int32_t elem_bytes;  /* 1, 4 or 8 */
+  int32_t size;        /* shift + 1 */
+} rl8_window_field;
+
+int rl8_gather_windows(const int64_t *index, int64_t m, int64_t h, const rl8_window_field *fields /*host*/,
+                       int n_fields, void *stream);
+int rl8_window_last(int64_t t, int64_t n, const rl8_window_field *fields /*host*/, int n_fields, void *stream);
 
 /* The same gather for a buffer that is shuffled many times per step()
  * (num_sgd_iters x num_minibatches): rl8_pack_samples lays the fields of every

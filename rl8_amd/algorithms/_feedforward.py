@@ -59,6 +59,7 @@ from ..policies import Policy
 from ..schedulers import EntropyScheduler, LRScheduler, ScheduleKind
 from ..specs import Composite, Unbounded
 from ..tensordict import TensorDict
+from ..views import WindowPlan, window_plan
 
 #: Rows pushed through the policy network per forward/backward pass inside one
 #: minibatch.  The bf16-plane towers keep 1 KiB (h2) + 32 B (gate bits) per row and
@@ -188,7 +189,7 @@ class Algorithm:
     def __init__(self, env_cls: EnvFactory, /, config: None | AlgorithmConfig = None) -> None:
         config = config or AlgorithmConfig()
         # step()'s caches, the rollout record, the record rows of the minibatch in hand: set before any hook can read them
-        self._flat_full = self._packed = self._views_all = None
+        self._flat_full = self._packed = self._views_all = self._window_full = None
         self._record: None | fused_mlp.RolloutRecord = None
         self._batch_rows: None | slice | torch.Tensor = None  # (None: none; a slice of the flat full batch; sample ids)
         device = _resolve_device(config.device)
@@ -424,7 +425,8 @@ class Algorithm:
     # ------------------------------------------------------------------ #
     def _fusable(self) -> bool:
         """One-launch-per-timestep path: a built-in env exposing
-        ``fused_rollout_step`` with the distribution its kernel implements."""
+        ``fused_rollout_step`` with the distribution its kernel implements, and identity views (a windowed model
+        takes ``env.step`` + the bookkeeping launch on every env; its input comes from ``rl8_window_last``)."""
         if not hasattr(self.env, "fused_rollout_step") or not self._identity_views():
             return False
         dist_cls = self.policy.distribution_cls
@@ -440,12 +442,23 @@ class Algorithm:
             return True
         return set(views) == {DataKeys.OBS} and all(v.is_identity for v in views.values())
 
-    def _forward(self, obs: torch.Tensor | TensorDict, *, deterministic: bool) -> tuple[TensorDict, torch.Tensor]:
-        """Policy network on a ``[N, obs...]`` slab (a tensordict of them for dict observations) -> (features,
-        values)."""
+    def _window_plan(self) -> None | WindowPlan:
+        """The kernel route for the model's observation views (``views.window_plan``; ``None``: torch ops), asked once
+        per ``collect()`` and once per ``step()``."""
+        return window_plan(self.policy.model, self.env.observation_spec)
+
+    def _window_views_last(self, plan: WindowPlan, t: int) -> TensorDict:
+        """The model's input at column ``t``: every window that ends there, from one ``rl8_window_last`` launch."""
+        return plan.views(hip.window_last(t, plan.sources(self.buffer[DataKeys.OBS]), plan.sizes))
+
+    def _forward(self, obs: torch.Tensor | TensorDict, *, deterministic: bool,
+                 views: None | TensorDict = None) -> tuple[TensorDict, torch.Tensor]:
+        """Policy network on a ``[N, obs...]`` slab (a tensordict of them for dict observations), or on prebuilt
+        ``views`` -> (features, values)."""
+        if views is None:
+            views = TensorDict({DataKeys.OBS: obs}, batch_size=obs.shape[0])
         sample = self.policy.sample(
-            TensorDict({DataKeys.VIEWS: TensorDict({DataKeys.OBS: obs}, batch_size=obs.shape[0])},
-                       batch_size=obs.shape[0]),
+            TensorDict({DataKeys.VIEWS: views}, batch_size=views.batch_size),
             kind="last",
             deterministic=deterministic,
             inplace=False,
@@ -496,6 +509,8 @@ class Algorithm:
                     rdr[0].zero_()
 
             fused = self._fusable()
+            # windowed views: built by one launch per column instead of torch ops on buffer[:, :t + 1]
+            plan = None if self._identity_views() else self._window_plan()
             gamma = float(torch.tensor(hp.gamma, dtype=torch.float32))
             record = self._rollout_record(fused)
             dist_cls = self.policy.distribution_cls
@@ -510,11 +525,14 @@ class Algorithm:
                         features, values = self._forward(obs_t, deterministic=deterministic)
                     self._fused_step(features, values, noise_t, t, gamma, step_id, deterministic)
                 else:
-                    self._generic_step(obs_t, noise_t, t, gamma, step_id, deterministic)
+                    self._generic_step(obs_t, noise_t, t, gamma, step_id, deterministic,
+                                       views=None if plan is None else self._window_views_last(plan, t))
 
             # Bootstrap value at the last observation (:396-408).
             if self._identity_views() and self._tm_obs is None:
                 _, values = self._forward(tm[DataKeys.OBS][H], deterministic=deterministic)
+            elif plan is not None:
+                _, values = self._forward(None, deterministic=deterministic, views=self._window_views_last(plan, H))
             else:
                 values = self.policy.sample(
                     self.buffer, kind="last", deterministic=deterministic, inplace=False, requires_grad=False,
@@ -548,9 +566,9 @@ class Algorithm:
 
     def _rollout_record(self, fused: bool) -> None | fused_mlp.RolloutRecord:
         """The record this ``collect()`` fills (made once, its slabs reused by every rollout), or ``None``.  Dict
-        observations train from views of the buffer, never from the record."""
+        observations and windowed views train from views of the buffer, never from the record."""
         rec = self._record
-        if (not fused or self._tm_obs is not None or not self.reuse_rollout_forward
+        if (not fused or self._tm_obs is not None or not self._identity_views() or not self.reuse_rollout_forward
                 or not has_fused_loss(self.policy.distribution_cls)):
             if rec is not None:  # (what an earlier rollout recorded is not this one's: step() must not replay it)
                 rec.unseal()
@@ -598,16 +616,17 @@ class Algorithm:
 
     def _generic_step(
         self, obs_t: torch.Tensor, noise: None | torch.Tensor, t: int, gamma: float, step_id: int,
-        deterministic: bool,
+        deterministic: bool, views: None | TensorDict = None,
     ) -> None:
         """Any ``Env`` / ``Distribution``: policy.sample -> env.step -> one
-        bookkeeping launch."""
+        bookkeeping launch.  ``views``: the model's input at column ``t`` when the window kernels built it."""
         tm = self._tm
         rdr = tm.get(DataKeys.REVERSED_DISCOUNTED_RETURNS)
         self.policy.injected_noise = noise
         self.noise.step = step_id  # policy.sample advances it again by one
         sample = self.policy.sample(
-            self.buffer[:, : (t + 1), ...],
+            self.buffer[:, : (t + 1), ...] if views is None else TensorDict(
+                {DataKeys.VIEWS: views}, batch_size=views.batch_size, device=self.buffer.device),
             kind="last",
             deterministic=deterministic,
             inplace=False,
@@ -772,7 +791,7 @@ class Algorithm:
             self.state.buffered = False
             self.injected_permutations = None
             self._flat_full = None
-            self._views_all = None
+            self._views_all = self._window_full = None
             self._packed = None
             self._release_step_caches()
             step_stats = stat_tracker.items()
@@ -833,11 +852,14 @@ class Algorithm:
         """Minibatches for models with rolling-window view requirements and for dict observations
         (``src/rl8/algorithms/_feedforward.py:471-482``): the windows of the whole
         buffer are built once per ``step()`` (env-major sample order, like the
-        flattened buffer) and indexed per minibatch."""
+        flattened buffer) and indexed per minibatch.  With a window plan (``views.window_plan``) nothing is built up
+        front: one ``rl8_gather_windows`` launch per minibatch reads the windows straight out of the buffer, and a
+        whole-buffer minibatch is gathered once per ``step()``."""
         hp = self.hparams
         H = hp.horizon
         local_samples = self.local_num_envs * H
-        if self._views_all is None:
+        plan = self._window_plan()
+        if plan is None and self._views_all is None:
             views = self.policy.model.apply_view_requirements(self.buffer[:, :-1, ...], kind="all")
             if views.batch_size[0] != local_samples:
                 raise ValueError(
@@ -854,7 +876,16 @@ class Algorithm:
         for index in torch.split(perm, local_mb):
             gathered = hip.gather_minibatch(index.contiguous(), H, [self.buffer[k] for k in keys])
             batch: dict[str, Any] = dict(zip(keys, gathered))
-            batch[DataKeys.VIEWS] = self._views_all[index]
+            if plan is None:
+                batch[DataKeys.VIEWS] = self._views_all[index]
+            elif hp.num_minibatches == 1:
+                if self._window_full is None:  # (every sample in order: gathered once, reused by the SGD iterations)
+                    obs = self.buffer[DataKeys.OBS]
+                    self._window_full = plan.views(hip.gather_windows(None, H, plan.sources(obs), plan.sizes))
+                batch[DataKeys.VIEWS] = self._window_full
+            else:
+                obs = self.buffer[DataKeys.OBS]
+                batch[DataKeys.VIEWS] = plan.views(hip.gather_windows(index.contiguous(), H, plan.sources(obs), plan.sizes))
             yield batch
 
     def _minibatch_forward_backward(

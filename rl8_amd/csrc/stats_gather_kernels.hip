@@ -191,6 +191,69 @@ __global__ __launch_bounds__(kBlock) void gather_sequences_kernel(
   }
 }
 
+// Padded rolling windows (src/rl8/views.py:54-123, 240-321): cell j of a window of `size` ending at step t is step
+// t' = t - (size - 1) + j of the same env, zeros and mask = 1 where t' < 0.  A field of size 1 is the plain gather (no
+// mask), so the unwindowed leaves of a dict observation ride in the same launch.
+struct WindowArgs {
+  rl8_window_field f[RL8_MAX_GATHER_FIELDS];
+  int n_fields;
+};
+
+// One window cell: `row_elems` elements to dst[cell], from src + src0 (elements) or zeros.
+template <class T>
+__device__ __forceinline__ void window_cell(const rl8_window_field &fd, int64_t cell, int64_t src0, bool padded) {
+  T *dst = static_cast<T *>(fd.dst) + cell * fd.row_elems;
+  if (padded) {
+    for (int c = 0; c < fd.row_elems; ++c) dst[c] = T(0);
+  } else {
+    const T *src = static_cast<const T *>(fd.src) + src0;
+    for (int c = 0; c < fd.row_elems; ++c) dst[c] = src[c];
+  }
+}
+
+__device__ __forceinline__ void window_cell(const rl8_window_field &fd, int64_t cell, int64_t env, int64_t t) {
+  const bool padded = t < 0;
+  const int64_t src0 = env * fd.env_stride + t * fd.time_stride;
+  if (fd.elem_bytes == 4) window_cell<uint32_t>(fd, cell, src0, padded);
+  else if (fd.elem_bytes == 8) window_cell<uint64_t>(fd, cell, src0, padded);
+  else window_cell<uint8_t>(fd, cell, src0, padded);  // (a bool[3] row: 3 bytes, no word alignment)
+  if (fd.mask) fd.mask[cell] = padded ? 1 : 0;
+}
+
+// Training: one lane per gathered window cell, field after field: a sample's cells sit in neighbouring lanes, so the
+// writes of a wave are one dense run and every cell's random read (this is a shuffle) is in flight at once; the index
+// is re-read from cache by the lanes of a sample.
+__global__ __launch_bounds__(kBlock) void gather_windows_kernel(
+    const int64_t *__restrict__ index, int64_t m, int64_t h, WindowArgs args) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+#pragma unroll 1
+  for (int f = 0; f < args.n_fields; ++f) {
+    const rl8_window_field &fd = args.f[f];
+    const int64_t cells = m * fd.size;
+    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < cells; k += stride) {
+      const int64_t i = k / fd.size, j = k - i * fd.size;
+      const int64_t s = index ? index[i] : i;  // (index = NULL: every sample in order)
+      const int64_t env = s / h, t = s - env * h;
+      window_cell(fd, k, env, t - (fd.size - 1) + j);
+    }
+  }
+}
+
+// Rollout: the window ending at the given step of every env.  Lanes run over envs within one window cell j, so on a
+// time-major slab each of the `size` source columns is read as one contiguous run.
+__global__ __launch_bounds__(kBlock) void window_last_kernel(int64_t t, int64_t n, WindowArgs args) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+#pragma unroll 1
+  for (int f = 0; f < args.n_fields; ++f) {
+    const rl8_window_field &fd = args.f[f];
+    const int64_t cells = n * fd.size;
+    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < cells; k += stride) {
+      const int64_t j = k / n, env = k - j * n;
+      window_cell(fd, env * fd.size + j, env, t - (fd.size - 1) + j);
+    }
+  }
+}
+
 // K5b: packed sample rows.  A shuffled minibatch reads every field of a sample
 // from a different random address: five 4/8-byte reads, five 32/64-byte sectors,
 // ~12x the algorithmic bytes (PMC).  When a buffer is going to be shuffled
@@ -486,6 +549,48 @@ RL8_API int rl8_gather_sequences(const int64_t *seq_index, int64_t num_seqs, int
   }
   const int64_t rows = num_seqs * seq_len;
   gather_sequences_kernel<<<grid_for(rows, kBlock), kBlock, 0, (hipStream_t)stream>>>(seq_index, rows, seq_len, h, args);
+  return launch_status();
+}
+
+// Argument checks shared by the two window entries.
+static int window_args(const rl8_window_field *fields, int n_fields, WindowArgs *args) {
+  if (!fields) return RL8_ENULL;
+  if (n_fields <= 0 || n_fields > RL8_MAX_GATHER_FIELDS) return RL8_ESIZE;
+  args->n_fields = n_fields;
+  for (int f = 0; f < n_fields; ++f) {
+    const rl8_window_field &fd = fields[f];
+    if (!fd.src || !fd.dst) return RL8_ENULL;
+    if (fd.elem_bytes != 1 && fd.elem_bytes != 4 && fd.elem_bytes != 8) return RL8_ECONFIG;
+    if (fd.row_elems <= 0 || fd.size < 1) return RL8_ESIZE;
+    if (fd.size > 1 && !fd.mask) return RL8_ECONFIG;
+    const uintptr_t low = (uintptr_t)fd.elem_bytes - 1;
+    if ((reinterpret_cast<uintptr_t>(fd.src) & low) || (reinterpret_cast<uintptr_t>(fd.dst) & low)) return RL8_EALIGN;
+    args->f[f] = fd;
+    if (fd.size == 1) args->f[f].mask = nullptr;  // (a plain gather has no mask)
+  }
+  return RL8_OK;
+}
+
+RL8_API int rl8_gather_windows(const int64_t *index, int64_t m, int64_t h, const rl8_window_field *fields,
+                               int n_fields, void *stream) {
+  if (!fields) return RL8_ENULL;
+  if (m <= 0 || h <= 0) return RL8_ESIZE;
+  WindowArgs args;
+  if (const int st = window_args(fields, n_fields, &args)) return st;
+  int64_t cells = 0;  // the widest field sizes the grid; the others stride over it
+  for (int f = 0; f < n_fields; ++f) cells = cells > m * args.f[f].size ? cells : m * args.f[f].size;
+  gather_windows_kernel<<<grid_for(cells, kBlock), kBlock, 0, (hipStream_t)stream>>>(index, m, h, args);
+  return launch_status();
+}
+
+RL8_API int rl8_window_last(int64_t t, int64_t n, const rl8_window_field *fields, int n_fields, void *stream) {
+  if (!fields) return RL8_ENULL;
+  if (t < 0 || n <= 0) return RL8_ESIZE;
+  WindowArgs args;
+  if (const int st = window_args(fields, n_fields, &args)) return st;
+  int64_t cells = 0;  // the widest field sizes the grid; the others stride over it
+  for (int f = 0; f < n_fields; ++f) cells = cells > n * args.f[f].size ? cells : n * args.f[f].size;
+  window_last_kernel<<<grid_for(cells, kBlock), kBlock, 0, (hipStream_t)stream>>>(t, n, args);
   return launch_status();
 }
 

@@ -91,6 +91,21 @@ class GatherField(C.Structure):
     ]
 
 
+class WindowField(C.Structure):
+    """``rl8_window_field`` (include/rl8_amd.h)."""
+
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("dst", C.c_void_p),
+        ("mask", C.c_void_p),
+        ("env_stride", C.c_int64),
+        ("time_stride", C.c_int64),
+        ("row_elems", C.c_int32),
+        ("elem_bytes", C.c_int32),
+        ("size", C.c_int32),
+    ]
+
+
 class ScatterLeaf(C.Structure):
     """``rl8_scatter_leaf`` (include/rl8_amd.h)."""
 
@@ -148,6 +163,8 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_ppo_loss_normal_fwd_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(PPOHparams), _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_gather_minibatch": [_vp, _i64, _i64, C.POINTER(GatherField), _i32, _vp],
     "rl8_gather_sequences": [_vp, _i64, _i32, _i64, C.POINTER(GatherField), _i32, _vp],
+    "rl8_gather_windows": [_vp, _i64, _i64, C.POINTER(WindowField), _i32, _vp],
+    "rl8_window_last": [_i64, _i64, C.POINTER(WindowField), _i32, _vp],
     "rl8_pack_samples": [_vp, _i32, _i64, _i64, _vp, _i32, _vp],
     "rl8_gather_packed": [_vp, _i64, _vp, _i32, _vp, _i32, _vp],
     "rl8_lstm_supports": [_i32],
@@ -1039,6 +1056,74 @@ def gather_sequences(seq_index: None | torch.Tensor, seq_len: int, h: int,
     with _timed("gather_sequences", rows):
         _check(load().rl8_gather_sequences(_ptr(seq_index) if seq_index is not None else None, num_seqs, seq_len, h,
                                            fields, len(leaves), _stream()), "rl8_gather_sequences")
+    return outs
+
+
+def _window_fields(rows: int, leaves: Sequence[torch.Tensor], sizes: Sequence[int]):
+    """The ``rl8_window_field`` array of ``[N, T, ...]`` leaves with window lengths ``sizes``, and the fresh outputs
+    it points at: per leaf ``(inputs [rows, size, ...], padding_mask [rows, size] bool)``, or ``(dst [rows, ...],
+    None)`` for ``size == 1``."""
+    if not leaves or len(leaves) != len(sizes) or len(leaves) > MAX_GATHER_FIELDS:
+        raise ValueError(f"between 1 and {MAX_GATHER_FIELDS} leaves per launch, one window length each")
+    fields = (WindowField * len(leaves))()
+    outs: list[tuple[torch.Tensor, None | torch.Tensor]] = []
+    for i, (leaf, size) in enumerate(zip(leaves, sizes)):
+        if leaf.ndim < 2:
+            raise ValueError("leaves must be [N, T, ...]")
+        if size < 1:
+            raise ValueError(f"window length {size} must be at least 1")
+        trailing = leaf.shape[2:]
+        row, expect = 1, 1
+        for d, st in zip(reversed(trailing), reversed(leaf.stride()[2:])):
+            if d != 1 and st != expect:
+                raise ValueError("leaf trailing dims must be dense")
+            expect *= d
+            row *= d
+        if leaf.element_size() not in (1, 4, 8):
+            raise TypeError("leaf elements must be 1, 4 or 8 bytes wide")
+        if size == 1:
+            dst, mask = torch.empty((rows, *trailing), dtype=leaf.dtype, device=leaf.device), None
+        else:
+            dst = torch.empty((rows, size, *trailing), dtype=leaf.dtype, device=leaf.device)
+            mask = torch.empty((rows, size), dtype=torch.bool, device=leaf.device)
+        fields[i] = WindowField(_ptr(leaf), _ptr(dst), _ptr(mask), leaf.stride(0), leaf.stride(1), row,
+                                leaf.element_size(), size)
+        outs.append((dst, mask))
+    return fields, outs
+
+
+def gather_windows(index: None | torch.Tensor, h: int, leaves: Sequence[torch.Tensor],
+                   sizes: Sequence[int]) -> list[tuple[torch.Tensor, None | torch.Tensor]]:
+    """Padded rolling windows of a minibatch: ``index`` [M] int64 of reference sample ids (``env * h + t``; ``None``:
+    every sample in order, ``M = N * h``), ``leaves`` [N, T, ...] buffer leaves (any stride over env / time, dense
+    over the rest; float32, int64 or bool) and one window length ``shift + 1`` per leaf. Per leaf ``(inputs [M, size,
+    ...], padding_mask [M, size])`` -- what ``PaddedRollingWindow.apply_all(leaf[:, :h], size)[index]`` holds -- or
+    ``(leaf's rows [M, ...], None)`` for ``size == 1``. One launch."""
+    if h < 1:
+        raise ValueError(f"gather_windows: h={h} must be positive")
+    if index is None:
+        m = leaves[0].shape[0] * h
+    else:
+        _dense(index, torch.int64, "index")
+        m = index.numel()
+    fields, outs = _window_fields(m, leaves, sizes)
+    with _timed("gather_windows", m):
+        _check(load().rl8_gather_windows(_ptr(index) if index is not None else None, m, h, fields, len(outs), _stream()),
+               "rl8_gather_windows")
+    return outs
+
+
+def window_last(t: int, leaves: Sequence[torch.Tensor],
+                sizes: Sequence[int]) -> list[tuple[torch.Tensor, None | torch.Tensor]]:
+    """The windows that end at step ``t`` of every env: per leaf what ``pad_last_sequence(leaf[:, :t + 1], size)``
+    holds (``(inputs [N, size, ...], padding_mask [N, size])``), or ``(leaf[:, t] as a dense copy, None)`` for
+    ``size == 1``. One launch."""
+    if not leaves or any(not 0 <= t < leaf.shape[1] for leaf in leaves):
+        raise ValueError(f"window_last: step {t} outside the leaves")
+    n = leaves[0].shape[0]
+    fields, outs = _window_fields(n, leaves, sizes)
+    with _timed("window_last", n):
+        _check(load().rl8_window_last(t, n, fields, len(outs), _stream()), "rl8_window_last")
     return outs
 
 

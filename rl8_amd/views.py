@@ -13,11 +13,18 @@ padded with zeros in front plus a mask (no samples dropped).
 Windows are built with ``Tensor.unfold`` -- a stride trick, no data movement
 until a consumer asks for a dense tensor -- on any device.
 
+``window_plan`` decides, once per model, whether the observation views can be
+built by the gather kernels instead (``rl8_window_last`` during the rollout,
+``rl8_gather_windows`` per minibatch): padded windows on ``"obs"`` /
+``("obs", leaf)`` only. Everything else keeps the torch route above.
+
 """
 
 from __future__ import annotations
 
-from typing import Callable, Literal
+import os
+from dataclasses import dataclass
+from typing import Any, Callable, Literal, Sequence
 
 import torch
 
@@ -176,3 +183,115 @@ class ViewRequirement:
     def drop_size(self) -> int:
         """Samples lost at the start of every row by the method."""
         return self.method.drop_size(self.shift + 1)
+
+
+# --------------------------------------------------------------------------- #
+# The kernel route for observation views.
+# --------------------------------------------------------------------------- #
+#: What one gather launch takes (``RL8_MAX_GATHER_FIELDS`` of include/rl8_amd.h).
+MAX_WINDOW_FIELDS = 8
+
+#: Leaf dtypes the window kernels move (4-, 8- and 1-byte elements).
+WINDOW_DTYPES = (torch.float32, torch.int64, torch.bool)
+
+
+@dataclass(frozen=True)
+class WindowLeaf:
+    """One field of a window launch: the observation leaf (``None``: the tensor observation itself) and its window
+    length ``shift + 1``. ``size > 1`` becomes ``{"inputs", "padding_mask"}`` in the views, ``size == 1`` stays a
+    tensor."""
+
+    name: None | str
+    size: int
+
+
+@dataclass(frozen=True)
+class WindowPlan:
+    """Which observation leaves a model reads and with which window, in launch order; the views tensordict built
+    from a launch's outputs has the keys ``Model.apply_view_requirements`` gives."""
+
+    leaves: tuple[WindowLeaf, ...]
+
+    @property
+    def sizes(self) -> list[int]:
+        return [leaf.size for leaf in self.leaves]
+
+    def sources(self, obs: torch.Tensor | TensorDict) -> list[torch.Tensor]:
+        """The buffer leaves of the fields, in launch order, out of ``buffer["obs"]``."""
+        return [obs if leaf.name is None else obs[leaf.name] for leaf in self.leaves]
+
+    def layout(self) -> dict[str, Any]:
+        """Key structure of the views: ``None`` for a tensor, ``{"inputs": None, "padding_mask": None}`` for a
+        window, nested by leaf name for dict observations."""
+        def entry(leaf: WindowLeaf) -> Any:
+            return None if leaf.size == 1 else {DataKeys.INPUTS: None, DataKeys.PADDING_MASK: None}
+
+        if len(self.leaves) == 1 and self.leaves[0].name is None:
+            return {DataKeys.OBS: entry(self.leaves[0])}
+        return {DataKeys.OBS: {leaf.name: entry(leaf) for leaf in self.leaves}}
+
+    def views(self, outs: Sequence[tuple[torch.Tensor, None | torch.Tensor]]) -> TensorDict:
+        """The views tensordict from one launch's ``(inputs, padding_mask | None)`` per field."""
+        rows = outs[0][0].shape[0]
+
+        def entry(out: tuple[torch.Tensor, None | torch.Tensor]) -> torch.Tensor | TensorDict:
+            inputs, mask = out
+            if mask is None:
+                return inputs
+            window = TensorDict({}, batch_size=[rows], device=inputs.device)
+            window[DataKeys.INPUTS] = inputs
+            window[DataKeys.PADDING_MASK] = mask
+            return window
+
+        if len(self.leaves) == 1 and self.leaves[0].name is None:
+            obs: Any = entry(outs[0])
+        else:
+            obs = TensorDict({leaf.name: entry(out) for leaf, out in zip(self.leaves, outs)}, batch_size=[rows],
+                             device=outs[0][0].device)
+        return TensorDict({DataKeys.OBS: obs}, batch_size=[rows], device=outs[0][0].device)
+
+
+def window_kernels_enabled() -> bool:
+    """``RL8_AMD_WINDOW_KERNELS=0`` keeps every view on the torch route (read per call)."""
+    return os.environ.get("RL8_AMD_WINDOW_KERNELS", "1") != "0"
+
+
+def window_plan(model: Any, observation_spec: Any, /) -> None | WindowPlan:
+    """The kernel route for ``model``'s observation views, or ``None`` for the torch route.
+
+    The kernels take over when every view key is ``"obs"`` or ``("obs", leaf)``, every leaf read is a float32, int64
+    or bool tensor leaf (one level of nesting at most), every ``shift > 0`` uses ``padded_rolling_window`` and at
+    most ``MAX_WINDOW_FIELDS`` fields result. Keys apply in the order of ``model.view_requirements``, as
+    ``Model.apply_view_requirements`` assigns them: ``"obs"`` sets every leaf, a later ``("obs", leaf)`` overwrites
+    that leaf.
+
+    """
+    from .specs import Composite
+
+    if not window_kernels_enabled():
+        return None
+    requirements = getattr(model, "view_requirements", None)
+    if not requirements:  # (recurrent models take observations as they are)
+        return None
+    composite = isinstance(observation_spec, Composite)
+    if composite:
+        names = list(observation_spec.keys())
+        specs = [observation_spec[name] for name in names]
+    else:
+        names, specs = [None], [observation_spec]
+    if any(isinstance(spec, Composite) or getattr(spec, "dtype", None) not in WINDOW_DTYPES for spec in specs):
+        return None
+    sizes: dict[None | str, int] = {}
+    for key, requirement in requirements.items():
+        if requirement.shift > 0 and requirement.method is not PaddedRollingWindow:
+            return None
+        if key == DataKeys.OBS:
+            sizes = {name: requirement.shift + 1 for name in names}
+        elif (composite and isinstance(key, tuple) and len(key) == 2 and key[0] == DataKeys.OBS
+              and key[1] in names):
+            sizes[key[1]] = requirement.shift + 1
+        else:
+            return None
+    if not 1 <= len(sizes) <= MAX_WINDOW_FIELDS:
+        return None
+    return WindowPlan(tuple(WindowLeaf(name, size) for name, size in sizes.items()))
