@@ -31,6 +31,7 @@
  *     update     rl8_gae_scan_f32, rl8_advantage_normalise_f32 (their routes: rl8_gae_plan, rl8_advantage_normalise_route),
  *                rl8_ppo_loss_{categorical,normal}_fwd_bwd_f32,
  *                rl8_pack_samples, rl8_gather_packed, rl8_gather_minibatch, rl8_gather_sequences (dict observations)
+ *                (their routes: rl8_rollout_stats_plan, rl8_gather_minibatch_plan, rl8_pack_plan)
  *     windows    (feed-forward models with padded rolling-window view requirements on "obs" / ("obs", leaf), and dict
  *                observations; RL8_AMD_WINDOW_KERNELS=0 puts both back on torch ops) rl8_window_last (collect(): the
  *                model's input at every timestep and at the bootstrap value), rl8_gather_windows (step(): the
@@ -92,8 +93,10 @@ extern "C" {
  * rl8_lstm_split_supports report wider envelopes; the weight-gradient workspace's tail words moved).  Added under 106
  * without a bump (new entries only, nothing existing changed): rl8_rollout_scatter_leaves_f32,
  * rl8_algotrading_reset_f32, rl8_algotrading_step_f32, rl8_rollout_step_algotrading_f32, rl8_gather_windows,
- * rl8_window_last. */
-#define RL8_ABI_VERSION 106
+ * rl8_window_last.  107 (no signature changed: min / max of rl8_rollout_stats_f32 are NaN when a reward is, where they
+ * used to drop it; rl8_gather_minibatch checks every field before its first launch; new queries
+ * rl8_rollout_stats_plan, rl8_gather_minibatch_plan, rl8_pack_plan). */
+#define RL8_ABI_VERSION 107
 int rl8_abi_version(char *arch, int arch_len);
 
 /* Scratch the reductions need (bytes); the caller allocates it once per stream
@@ -277,10 +280,31 @@ int rl8_rollout_step_pendulum_f32(int squashed, const float *mean, const float *
  *   [10] sum(rdr[:,1:]) [11] sum(rdr[:,1:]^2)
  * (raw moments, so that shards can be combined with one all-reduce each for
  * SUM / MIN / MAX before the host forms mean and unbiased std).
+ * Rewards that are not finite follow the reference's torch ops: the sums follow IEEE 754, min / max of a set that holds
+ * a NaN are NaN (torch.min / torch.max propagate it), and infinities are ordinary extrema.
  * ---------------------------------------------------------------------- */
 int rl8_rollout_stats_f32(const float *rewards, const float *rdr, int64_t n, int64_t h,
                           int64_t env_stride, int64_t time_stride, double *stats_out,
                           void *scratch, void *stream);
+
+/* What rl8_rollout_stats_f32 launches for a shape, its strides (in elements) and an alignment (aligned16_all != 0:
+ * rewards, and rdr where given, are 16-byte aligned).  Host arithmetic only: no device is touched, and the entry
+ * launches exactly what this reports.
+ *   STATS_VEC4  four adjacent envs per lane through 16-byte loads: env_stride == 1, N % 4 == 0, time_stride % 4 == 0,
+ *               aligned
+ *   STATS_VEC1  one env per lane, any strides
+ * grid: workgroups of 256 lanes (one partial row each); trips: the env groups the busiest lane visits, more than one
+ * when the grid is capped (2048 workgroups; RL8_STATS_GRID_CAP in the environment, read once per process, lowers the
+ * cap of the VEC4 route). */
+#define RL8_STATS_VEC4 0
+#define RL8_STATS_VEC1 1
+typedef struct {
+  int route;
+  int grid;
+  int64_t trips;
+} rl8_stats_plan_t;
+int rl8_rollout_stats_plan(int64_t n, int64_t h, int64_t env_stride, int64_t time_stride, int aligned16_all,
+                           rl8_stats_plan_t *out /*host*/);
 
 /* ---------------------------------------------------------------------- *
  * a-5  generalized_advantage_estimate src/rl8/nn/functional.py:50-123
@@ -380,8 +404,10 @@ int rl8_ppo_loss_normal_fwd_bwd_f32(const float *mean, const float *log_std, con
  * Elements are 4 or 8 bytes wide (f32 / int64).
  * index = NULL (ABI 105): every sample of the buffer in order, s = 0 .. m - 1 with m = N h -- the sequence-major
  * copy of a time-major buffer that the recurrent algorithm trains on -- as a transposition through LDS tiles
- * (each byte read and written once, where the indexed kernel moves 6x that for 4-byte leaves); rows of at most
- * 128 bytes summed over the fields, else RL8_ESIZE.
+ * (each byte read and written once, where the indexed kernel moves 6x that for 4-byte leaves).  A tile row holds 128
+ * bytes, so consecutive fields go in groups that fit, one launch per group; a field of more than 128 bytes per row
+ * closes the current group and takes the indexed kernels with the implicit index i.  m a multiple of h (RL8_ESIZE).
+ * Every field is checked before the first launch.
  * ---------------------------------------------------------------------- */
 typedef struct {
   const void *src;
@@ -396,6 +422,20 @@ typedef struct {
 
 int rl8_gather_minibatch(const int64_t *index, int64_t m, int64_t h,
                          const rl8_gather_field *fields /*host*/, int n_fields, void *stream);
+
+/* The kernels rl8_gather_minibatch launches (host arithmetic only; `indexed` != 0: an index is given).  The pointers in
+ * `fields` are judged for alignment and for NULL, never dereferenced.  routes_out / groups_out: n_fields ints each.
+ *   GATHER_GENERAL    one lane per sample, element by element; all such fields share one launch
+ *   GATHER_WIDE_ROWS  one wave per row in 16-byte pieces, one launch per field: rows of 256 bytes and up in whole
+ *                     16-byte pieces, src and dst 16-byte aligned, env and time strides multiples of 16 bytes
+ *   GATHER_TILED      index = NULL and at most 128 bytes per row: the tiled transposition, one launch per group of
+ *                     consecutive fields; groups_out[f] is the field's group (0, 1, ...), -1 on the other routes
+ * launches_out: tiled groups + wide fields + one if any field is general.  Error codes as rl8_gather_minibatch. */
+#define RL8_GATHER_GENERAL 0
+#define RL8_GATHER_WIDE_ROWS 1
+#define RL8_GATHER_TILED 2
+int rl8_gather_minibatch_plan(int indexed, int64_t m, int64_t h, const rl8_gather_field *fields /*host*/, int n_fields,
+                              int *routes_out /*host*/, int *groups_out /*host*/, int *launches_out /*host*/);
 
 /* Whole sequences, for the recurrent algorithm on dict observations: sequence q = env * (h / seq_len) + s is samples
  * q seq_len + j, j < seq_len (the reference's numbering); row i seq_len + j of every dst receives
@@ -447,6 +487,18 @@ int rl8_pack_samples(const rl8_gather_field *fields /*host*/, int n_fields, int6
                      void *packed, int row_words, void *stream);
 int rl8_gather_packed(const int64_t *index, int64_t m, const void *packed, int row_words,
                       const rl8_gather_field *fields /*host*/, int n_fields, void *stream);
+
+/* The launch of the tiled transposition behind rl8_pack_samples and rl8_gather_minibatch(index = NULL) (host arithmetic
+ * only): a workgroup moves tiles of 64 envs x tile_steps timesteps through lds_bytes of dynamic LDS (rows of
+ * row_words + 1 words); `tiles` of them, taken by `grid` workgroups in a strided loop.  row_words a multiple of 4 in
+ * 4 .. 32 (RL8_ESIZE). */
+typedef struct {
+  int tile_steps;
+  int lds_bytes;
+  int64_t tiles;
+  int grid;
+} rl8_pack_plan_t;
+int rl8_pack_plan(int64_t n, int64_t h, int row_words, rl8_pack_plan_t *out /*host*/);
 
 /* ---------------------------------------------------------------------- *
  * Dict (Composite) observations: rollout bookkeeping and the AlgoTrading env

@@ -281,7 +281,8 @@ ORACLE_API void oracle_rdr_step(const float *rdr_t, const float *reward, float *
 /* ------------------------------------------------------------------------ */
 /* rewards, rdr: env-major [n][h+1].  out[0..8] = returns min,max,mean,std,
  * rewards min,max,mean,std, std(rdr[:,1:]).  std is unbiased; torch's CPU
- * std_mean accumulates float data in double, as done here. */
+ * std_mean accumulates float data in double, as done here.  min / max of a set
+ * that holds a NaN are NaN, as torch.min / torch.max give. */
 ORACLE_API void oracle_rollout_stats(const float *rewards, const float *rdr, int64_t n,
                                      int64_t h, double *out) {
   double ret_min = INFINITY, ret_max = -INFINITY, rew_min = INFINITY, rew_max = -INFINITY;
@@ -292,12 +293,12 @@ ORACLE_API void oracle_rollout_stats(const float *rewards, const float *rdr, int
     for (int64_t t = 0; t < h; ++t) {
       float r = rewards[i * stride + t];
       ret = ret + r;
-      if (r < rew_min) rew_min = r;
-      if (r > rew_max) rew_max = r;
+      if (r < rew_min || r != r) rew_min = r; /* torch.min / torch.max keep a NaN: once in, `r < NaN` never */
+      if (r > rew_max || r != r) rew_max = r; /* replaces it */
       rew_sum += r;
     }
-    if (ret < ret_min) ret_min = ret;
-    if (ret > ret_max) ret_max = ret;
+    if (ret < ret_min || ret != ret) ret_min = ret;
+    if (ret > ret_max || ret != ret) ret_max = ret;
     ret_sum += ret;
   }
   const double ret_mean = ret_sum / (double)n;

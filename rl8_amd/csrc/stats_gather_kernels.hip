@@ -21,6 +21,20 @@ namespace rl8 {
 // with 16-byte loads per column.  VEC == 1: any strides, one env per lane.
 constexpr int kStatsBatch = 8;  // time steps whose loads are issued together
 
+// min / max that keep a NaN, as torch.min / torch.max do (fminf, fmaxf and a bare `<` drop it): a NaN on either side
+// comes out, infinities are ordinary extrema.  Every fold below -- lane, wave, block, last block -- goes through these,
+// except the per-reward one of a lane, which keeps fminf / fmaxf and tracks a NaN beside them.
+template <class T>
+__device__ __forceinline__ T nan_min(T a, T b) { return (a < b || a != a) ? a : b; }
+template <class T>
+__device__ __forceinline__ T nan_max(T a, T b) { return (a > b || a != a) ? a : b; }
+struct NanMinOp {
+  __device__ __forceinline__ static double apply(double a, double b) { return nan_min(a, b); }
+};
+struct NanMaxOp {
+  __device__ __forceinline__ static double apply(double a, double b) { return nan_max(a, b); }
+};
+
 template <int VEC, bool RDR>
 __global__ __launch_bounds__(kBlock) void rollout_stats_kernel(
     const float *__restrict__ rewards, const float *__restrict__ rdr, int64_t n, int64_t h,
@@ -35,6 +49,9 @@ __global__ __launch_bounds__(kBlock) void rollout_stats_kernel(
 #pragma unroll
     for (int i = 0; i < VEC; ++i) ret[i] = 0.0f;
     float rmin = INFINITY, rmax = -INFINITY;
+    // fminf / fmaxf drop a NaN (and fold two rewards per min3 / max3), so one is tracked beside them: the largest
+    // (bits << 1) of the rewards, an unsigned max like the float ones, is above 0xff000000 iff one of them is a NaN
+    uint32_t nan_key = 0u;
     // The sums are taken in ascending t whatever the batching below: a batch
     // only decides how many loads are in the air before the first add (one
     // load per wait leaves the pass at latency, 2.8 of 8 TB/s on cold rows).
@@ -54,6 +71,7 @@ __global__ __launch_bounds__(kBlock) void rollout_stats_kernel(
         sums[3] += (double)r[i] * (double)r[i];
         rmin = fminf(rmin, r[i]);
         rmax = fmaxf(rmax, r[i]);
+        nan_key = max(nan_key, __float_as_uint(r[i]) << 1);
       }
       if constexpr (RDR) {
 #pragma unroll
@@ -80,22 +98,23 @@ __global__ __launch_bounds__(kBlock) void rollout_stats_kernel(
       if constexpr (RDR) fetch(rdr, t + 1, d);
       fold(r, d);
     }
-    mins[1] = (double)rmin < mins[1] ? (double)rmin : mins[1];
-    maxs[1] = (double)rmax > maxs[1] ? (double)rmax : maxs[1];
+    if (nan_key > 0xff000000u) rmin = rmax = NAN;
+    mins[1] = nan_min((double)rmin, mins[1]);
+    maxs[1] = nan_max((double)rmax, maxs[1]);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
       sums[0] += (double)ret[i];
       sums[1] += (double)ret[i] * (double)ret[i];
-      mins[0] = ret[i] < mins[0] ? (double)ret[i] : mins[0];
-      maxs[0] = ret[i] > maxs[0] ? (double)ret[i] : maxs[0];
+      mins[0] = nan_min((double)ret[i], mins[0]);
+      maxs[0] = nan_max((double)ret[i], maxs[0]);
     }
   }
   double a4[4] = {sums[0], sums[1], sums[2], sums[3]};
   block_reduce<4, SumOp>(a4, smem);
   double b2[2] = {sums[4], sums[5]};
   block_reduce<2, SumOp>(b2, smem);
-  block_reduce<2, MinOp>(mins, smem);
-  block_reduce<2, MaxOp>(maxs, smem);
+  block_reduce<2, NanMinOp>(mins, smem);
+  block_reduce<2, NanMaxOp>(maxs, smem);
   if (threadIdx.x == 0) {
     double *row = partials + (int64_t)blockIdx.x * kPartialWidth;
     const double vals[10] = {a4[0], a4[1], mins[0], maxs[0], a4[2], a4[3], mins[1], maxs[1],
@@ -113,14 +132,14 @@ __global__ __launch_bounds__(kBlock) void rollout_stats_kernel(
   fold_partial_rows<10>(partials, rows, [&](const double(&row)[10]) {
     sums[0] += row[0]; sums[1] += row[1]; sums[2] += row[4];
     sums[3] += row[5]; sums[4] += row[8]; sums[5] += row[9];
-    mins[0] = row[2] < mins[0] ? row[2] : mins[0];
-    maxs[0] = row[3] > maxs[0] ? row[3] : maxs[0];
-    mins[1] = row[6] < mins[1] ? row[6] : mins[1];
-    maxs[1] = row[7] > maxs[1] ? row[7] : maxs[1];
+    mins[0] = nan_min(row[2], mins[0]);
+    maxs[0] = nan_max(row[3], maxs[0]);
+    mins[1] = nan_min(row[6], mins[1]);
+    maxs[1] = nan_max(row[7], maxs[1]);
   });
   block_reduce<6, SumOp>(sums, smem);
-  block_reduce<2, MinOp>(mins, smem);
-  block_reduce<2, MaxOp>(maxs, smem);
+  block_reduce<2, NanMinOp>(mins, smem);
+  block_reduce<2, NanMaxOp>(maxs, smem);
   if (threadIdx.x == 0) {
     out[0] = nn;  out[1] = sums[0]; out[2] = sums[1]; out[3] = mins[0]; out[4] = maxs[0];
     out[5] = nh;  out[6] = sums[2]; out[7] = sums[3]; out[8] = mins[1]; out[9] = maxs[1];
@@ -438,17 +457,35 @@ RL8_API int64_t rl8_scratch_bytes(void) {
              (int64_t)sizeof(unsigned);
 }
 
+// The one place the statistics route is decided.  RL8_STATS_GRID_CAP (read once per process; at most the scratch's
+// partial rows) lowers the four-envs-per-lane grid so that a small shape takes further trips through the env loop.
+RL8_API int rl8_rollout_stats_plan(int64_t n, int64_t h, int64_t env_stride, int64_t time_stride, int aligned16_all,
+                                   rl8_stats_plan_t *out) {
+  if (!out) return RL8_ENULL;
+  if (n <= 0 || h <= 0 || env_stride <= 0 || time_stride <= 0) return RL8_ESIZE;
+  static const int cap_env = env_int("RL8_STATS_GRID_CAP");
+  const int cap = cap_env > 0 && cap_env < kMaxGrid ? cap_env : kMaxGrid;
+  const bool vec = env_stride == 1 && n % 4 == 0 && time_stride % 4 == 0 && aligned16_all != 0;
+  const int per_lane = vec ? 4 : 1;
+  out->route = vec ? RL8_STATS_VEC4 : RL8_STATS_VEC1;
+  out->grid = vec ? grid_for(n, kBlock * 4, cap) : grid_for(n, kBlock);
+  const int64_t per_trip = (int64_t)out->grid * kBlock * per_lane;
+  out->trips = (n + per_trip - 1) / per_trip;
+  return RL8_OK;
+}
+
 RL8_API int rl8_rollout_stats_f32(const float *rewards, const float *rdr, int64_t n, int64_t h,
                                   int64_t env_stride, int64_t time_stride, double *stats_out,
                                   void *scratch, void *stream) {
   if (!rewards || !stats_out || !scratch) return RL8_ENULL;
-  if (n <= 0 || h <= 0 || env_stride <= 0 || time_stride <= 0) return RL8_ESIZE;
+  rl8_stats_plan_t plan;
+  if (const int bad = rl8_rollout_stats_plan(n, h, env_stride, time_stride, aligned16(rewards) && (!rdr || aligned16(rdr)),
+                                             &plan))
+    return bad;
   hipStream_t s = (hipStream_t)stream;
   double *partials = (double *)scratch;
-  const bool vec = env_stride == 1 && n % 4 == 0 && time_stride % 4 == 0 && aligned16(rewards) &&
-                   (!rdr || aligned16(rdr));
-  static const int cap = env_int("RL8_STATS_GRID_CAP");
-  const dim3 grid = vec ? grid_for(n, kBlock * 4, cap > 0 ? cap : kMaxGrid) : grid_for(n, kBlock);
+  const bool vec = plan.route == RL8_STATS_VEC4;
+  const dim3 grid = plan.grid;
   auto launch = [&](auto kernel) {
     kernel<<<grid, kBlock, 0, s>>>(rewards, rdr, n, h, env_stride, time_stride, partials,
                                    stats_out);
@@ -464,67 +501,72 @@ static int packed_args(const rl8_gather_field *fields, int n_fields, int row_wor
 template <bool DENSE>
 static int launch_pack_tiled(const PackedArgs &args, int64_t n, int64_t h, uint32_t *packed, hipStream_t stream);
 
-RL8_API int rl8_gather_minibatch(const int64_t *index, int64_t m, int64_t h,
-                                 const rl8_gather_field *fields, int n_fields, void *stream) {
-  if (!fields) return RL8_ENULL;
+// The one place the routes of rl8_gather_minibatch are decided: per field GENERAL, WIDE_ROWS or TILED (and for TILED the
+// group, a run of consecutive fields that share one tile launch), and the number of launches.
+//   index = NULL (every sample in order, m = n h): a tiled transposition, each byte read and written once.  A tile's row
+//     holds at most 4 kMaxPackedVecs words, so the fields go in groups that fit, in the order given; a field wider than
+//     that closes the current group and takes the routes below with the implicit index i.
+//   wide rows: whole 16-byte pieces, 256 bytes and up, every row start of source and destination 16-byte aligned.
+//   general: everything else, all such fields in one launch.
+RL8_API int rl8_gather_minibatch_plan(int indexed, int64_t m, int64_t h, const rl8_gather_field *fields, int n_fields,
+                                      int *routes_out, int *groups_out, int *launches_out) {
+  if (!fields || !routes_out || !groups_out || !launches_out) return RL8_ENULL;
   if (m <= 0 || h <= 0 || n_fields <= 0 || n_fields > RL8_MAX_GATHER_FIELDS) return RL8_ESIZE;
-  rl8_gather_field rest[RL8_MAX_GATHER_FIELDS];
-  if (!index) {
-    // Every sample of the buffer in order (m = n h): a tiled transposition, each byte read and written once.  A tile's
-    // row holds at most 4 kMaxPackedVecs words, so the fields go in groups that fit (in the order given); a field wider
-    // than that on its own takes the general kernels below with the implicit index i (the recurrent
-    // algorithm's whole-buffer copy returned RL8_ESIZE for observations of 28 floats and more).
-    if (m % h) return RL8_ESIZE;
-    constexpr int kTileWords = 4 * kMaxPackedVecsDecl;
-    int n_rest = 0, first = 0, words = 0;
-    auto flush = [&](int stop) -> int {
-      if (stop == first) return RL8_OK;
-      PackedArgs tiled;
-      if (const int st = packed_args(fields + first, stop - first, (words + 3) / 4 * 4, true, true, &tiled)) return st;
-      return launch_pack_tiled<true>(tiled, m / h, h, nullptr, (hipStream_t)stream);
-    };
-    for (int f = 0; f < n_fields; ++f) {
-      const rl8_gather_field &fd = fields[f];
-      if (!fd.src || !fd.dst) return RL8_ENULL;
-      if (fd.elem_bytes != 4 && fd.elem_bytes != 8) return RL8_ECONFIG;
-      if (fd.row_elems <= 0) return RL8_ESIZE;
-      const int w = fd.row_elems * (fd.elem_bytes / 4);
-      if (w > kTileWords) {  // (closes the current group: groups are runs of consecutive fields)
-        if (const int st = flush(f)) return st;
-        first = f + 1, words = 0;
-        rest[n_rest++] = fd;
-        continue;
-      }
-      if (words + w > kTileWords) {
-        if (const int st = flush(f)) return st;
-        first = f, words = 0;
-      }
-      words += w;
-    }
-    if (const int st = flush(n_fields)) return st;
-    if (n_rest == 0) return launch_status();
-    fields = rest;
-    n_fields = n_rest;
-  }
-  GatherArgs args;
-  args.n_fields = 0;
-  hipStream_t s = (hipStream_t)stream;
+  if (!indexed && m % h) return RL8_ESIZE;
+  constexpr int kTileWords = 4 * kMaxPackedVecsDecl;
+  int groups = 0, words = 0, wide_fields = 0, general_fields = 0;  // (words: of the open tiled group; 0 = none open)
   for (int f = 0; f < n_fields; ++f) {
     const rl8_gather_field &fd = fields[f];
     if (!fd.src || !fd.dst) return RL8_ENULL;
     if (fd.elem_bytes != 4 && fd.elem_bytes != 8) return RL8_ECONFIG;
     if (fd.row_elems <= 0) return RL8_ESIZE;
     const int64_t row_bytes = (int64_t)fd.row_elems * fd.elem_bytes;
-    const bool wide = row_bytes >= 256 && row_bytes % 16 == 0 && aligned16(fd.src) &&
-                      aligned16(fd.dst) && (fd.env_stride * fd.elem_bytes) % 16 == 0 &&
-                      (fd.time_stride * fd.elem_bytes) % 16 == 0;
-    if (wide) {
+    if (!indexed && row_bytes <= 4 * kTileWords) {
+      const int w = (int)(row_bytes / 4);
+      if (words == 0 || words + w > kTileWords) ++groups, words = 0;
+      words += w;
+      routes_out[f] = RL8_GATHER_TILED;
+      groups_out[f] = groups - 1;
+      continue;
+    }
+    words = 0;  // (closes the open group: groups are runs of consecutive fields)
+    const bool wide = row_bytes >= 256 && row_bytes % 16 == 0 && aligned16(fd.src) && aligned16(fd.dst) &&
+                      (fd.env_stride * fd.elem_bytes) % 16 == 0 && (fd.time_stride * fd.elem_bytes) % 16 == 0;
+    routes_out[f] = wide ? RL8_GATHER_WIDE_ROWS : RL8_GATHER_GENERAL;
+    groups_out[f] = -1;
+    wide ? ++wide_fields : ++general_fields;
+  }
+  *launches_out = groups + wide_fields + (general_fields > 0 ? 1 : 0);
+  return RL8_OK;
+}
+
+RL8_API int rl8_gather_minibatch(const int64_t *index, int64_t m, int64_t h,
+                                 const rl8_gather_field *fields, int n_fields, void *stream) {
+  int routes[RL8_MAX_GATHER_FIELDS], groups[RL8_MAX_GATHER_FIELDS], launches = 0;
+  if (const int bad = rl8_gather_minibatch_plan(index != nullptr, m, h, fields, n_fields, routes, groups, &launches))
+    return bad;
+  hipStream_t s = (hipStream_t)stream;
+  GatherArgs args;
+  args.n_fields = 0;
+  for (int f = 0; f < n_fields;) {
+    const rl8_gather_field &fd = fields[f];
+    if (routes[f] == RL8_GATHER_TILED) {
+      int stop = f, words = 0;
+      for (; stop < n_fields && routes[stop] == RL8_GATHER_TILED && groups[stop] == groups[f]; ++stop)
+        words += fields[stop].row_elems * (fields[stop].elem_bytes / 4);
+      PackedArgs tiled;
+      if (const int st = packed_args(fields + f, stop - f, (words + 3) / 4 * 4, true, true, &tiled)) return st;
+      if (const int st = launch_pack_tiled<true>(tiled, m / h, h, nullptr, s)) return st;
+      f = stop;
+      continue;
+    }
+    if (routes[f] == RL8_GATHER_WIDE_ROWS) {
       gather_wide_rows_kernel<<<grid_for(m, kWavesPerBlock), kBlock, 0, s>>>(index, m, h, fd);
-      const int st = launch_status();
-      if (st != RL8_OK) return st;
+      if (const int st = launch_status()) return st;
     } else {
       args.f[args.n_fields++] = fd;
     }
+    ++f;
   }
   if (args.n_fields > 0)
     gather_minibatch_kernel<<<grid_for(m, kBlock), kBlock, 0, s>>>(index, m, h, args);
@@ -613,23 +655,34 @@ static int packed_args(const rl8_gather_field *fields, int n_fields, int row_wor
   return RL8_OK;
 }
 
-// The tiled transposition behind rl8_pack_samples (packed rows) and rl8_gather_minibatch(index = NULL) (dense fields).
-template <bool DENSE>
-static int launch_pack_tiled(const PackedArgs &args, int64_t n, int64_t h, uint32_t *packed, hipStream_t stream) {
-  // timesteps per tile: 36 KiB of LDS (16 steps of 32-byte rows), four workgroups per CU -- measured at 2^20 x 32:
-  // 18 KiB 463 us, 36 KiB 471, 72 KiB (32 steps, two per CU) 632, the lane-per-sample kernel 967
-  const int per_step = kPackEnvs * (args.row_words + 1) * 4;
+// The launch shape of the tiled transposition, shared by rl8_pack_samples and rl8_gather_minibatch(index = NULL).
+// timesteps per tile: 36 KiB of LDS (16 steps of 32-byte rows), four workgroups per CU -- measured at 2^20 x 32:
+// 18 KiB 463 us, 36 KiB 471, 72 KiB (32 steps, two per CU) 632, the lane-per-sample kernel 967
+RL8_API int rl8_pack_plan(int64_t n, int64_t h, int row_words, rl8_pack_plan_t *out) {
+  if (!out) return RL8_ENULL;
+  if (n <= 0 || h <= 0 || row_words <= 0 || row_words % 4 || row_words > 4 * kMaxPackedVecs) return RL8_ESIZE;
+  const int per_step = kPackEnvs * (row_words + 1) * 4;
   static const int lds_kib = env_int("RL8_PACK_TILE_KIB") > 0 ? env_int("RL8_PACK_TILE_KIB") : 36;
   int tile_steps = (lds_kib * 1024 + per_step - 1) / per_step;
   tile_steps = tile_steps > kPackSteps ? kPackSteps : tile_steps < 1 ? 1 : tile_steps;
   if (tile_steps > h) tile_steps = (int)h;
-  const int64_t tiles = ((n + kPackEnvs - 1) / kPackEnvs) * ((h + tile_steps - 1) / tile_steps);
   const int lds = tile_steps * per_step;
+  const int per_cu = (160 * 1024) / (lds + 512) < 1 ? 1 : (160 * 1024) / (lds + 512);
+  out->tile_steps = tile_steps;
+  out->lds_bytes = lds;
+  out->tiles = ((n + kPackEnvs - 1) / kPackEnvs) * ((h + tile_steps - 1) / tile_steps);
+  out->grid = (int)(out->tiles < (int64_t)per_cu * kCUs ? out->tiles : (int64_t)per_cu * kCUs);
+  return RL8_OK;
+}
+
+// The tiled transposition behind rl8_pack_samples (packed rows) and rl8_gather_minibatch(index = NULL) (dense fields).
+template <bool DENSE>
+static int launch_pack_tiled(const PackedArgs &args, int64_t n, int64_t h, uint32_t *packed, hipStream_t stream) {
+  rl8_pack_plan_t plan;
+  if (const int bad = rl8_pack_plan(n, h, args.row_words, &plan)) return bad;
   static LdsOptIn lds_pack;
   if (const int e = allow_dynamic_lds(lds_pack, reinterpret_cast<const void *>(&pack_samples_tiled_kernel<DENSE>), 160 * 1024)) return e;
-  const int per_cu = (160 * 1024) / (lds + 512) < 1 ? 1 : (160 * 1024) / (lds + 512);
-  const int grid = (int)(tiles < (int64_t)per_cu * kCUs ? tiles : (int64_t)per_cu * kCUs);
-  pack_samples_tiled_kernel<DENSE><<<grid, kBlock, lds, stream>>>(n, h, packed, args, tile_steps);
+  pack_samples_tiled_kernel<DENSE><<<plan.grid, kBlock, plan.lds_bytes, stream>>>(n, h, packed, args, plan.tile_steps);
   return launch_status();
 }
 

@@ -119,6 +119,18 @@ class GaePlanStruct(C.Structure):
                 ("lds_bytes", C.c_int64), ("grid", C.c_int)]
 
 
+class StatsPlanStruct(C.Structure):
+    """``rl8_stats_plan_t`` (include/rl8_amd.h)."""
+
+    _fields_ = [("route", C.c_int), ("grid", C.c_int), ("trips", C.c_int64)]
+
+
+class PackPlanStruct(C.Structure):
+    """``rl8_pack_plan_t`` (include/rl8_amd.h)."""
+
+    _fields_ = [("tile_steps", C.c_int), ("lds_bytes", C.c_int), ("tiles", C.c_int64), ("grid", C.c_int)]
+
+
 _vp, _i64, _u64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_uint64, C.c_int, C.c_float
 
 # name -> argtypes, mirroring include/rl8_amd.h one to one.
@@ -155,6 +167,7 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_rollout_step_pendulum_f32": [_i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(PendulumCfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _u64, _u64, _i64, _i32, _vp],
     "rl8_rollout_step_cartpole_f32": [_vp, _vp, _vp, _vp, C.POINTER(CartPoleCfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _u64, _u64, _i64, _i32, _vp],
     "rl8_rollout_stats_f32": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp],
+    "rl8_rollout_stats_plan": [_i64, _i64, _i64, _i64, _i32, C.POINTER(StatsPlanStruct)],
     "rl8_gae_scan_f32": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _f32, _f32, _i32, _vp, _vp, _vp],
     "rl8_advantage_normalise_f32": [_vp, _i64, _i64, _i32, _vp, _vp],
     "rl8_gae_plan": [_i64, _i64, _i32, _i32, C.POINTER(GaePlanStruct)],
@@ -162,11 +175,14 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_ppo_loss_categorical_fwd_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(PPOHparams), _vp, _vp, _vp, _vp, _vp],
     "rl8_ppo_loss_normal_fwd_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(PPOHparams), _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_gather_minibatch": [_vp, _i64, _i64, C.POINTER(GatherField), _i32, _vp],
+    "rl8_gather_minibatch_plan": [_i32, _i64, _i64, C.POINTER(GatherField), _i32, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                  C.POINTER(C.c_int)],
     "rl8_gather_sequences": [_vp, _i64, _i32, _i64, C.POINTER(GatherField), _i32, _vp],
     "rl8_gather_windows": [_vp, _i64, _i64, C.POINTER(WindowField), _i32, _vp],
     "rl8_window_last": [_i64, _i64, C.POINTER(WindowField), _i32, _vp],
     "rl8_pack_samples": [_vp, _i32, _i64, _i64, _vp, _i32, _vp],
     "rl8_gather_packed": [_vp, _i64, _vp, _i32, _vp, _i32, _vp],
+    "rl8_pack_plan": [_i64, _i64, _i32, C.POINTER(PackPlanStruct)],
     "rl8_lstm_supports": [_i32],
     "rl8_lstm_pack_floats": [],
     "rl8_lstm_pack_f32": [_vp, _vp, _vp, _vp, _i32, _vp, _vp],
@@ -240,7 +256,7 @@ SIGNATURES: dict[str, list[Any]] = {
 
 
 #: RL8_ABI_VERSION of include/rl8_amd.h this binding is written against (checked against the library in ``load``).
-ABI_VERSION = 106
+ABI_VERSION = 107
 
 
 def library_path() -> str:
@@ -849,6 +865,61 @@ def rollout_stats(rewards: torch.Tensor, rdr: None | torch.Tensor) -> torch.Tens
             "rl8_rollout_stats_f32",
         )
     return out
+
+
+#: route names of ``rl8_rollout_stats_plan`` / ``rl8_gather_minibatch_plan``, indexed by their RL8_STATS_* / RL8_GATHER_* codes
+STATS_ROUTES = ("STATS_VEC4", "STATS_VEC1")
+GATHER_ROUTES = ("GATHER_GENERAL", "GATHER_WIDE_ROWS", "GATHER_TILED")
+
+
+class StatsPlan(NamedTuple):
+    """What ``rl8_rollout_stats_f32`` launches (``rl8_stats_plan_t``)."""
+
+    route: str
+    grid: int
+    trips: int
+
+
+def rollout_stats_plan(n: int, h: int, env_stride: int, time_stride: int, aligned16_all: bool = True) -> StatsPlan:
+    """The statistics' launch plan; host arithmetic in the library, no device needed."""
+    p = StatsPlanStruct()
+    _check(load().rl8_rollout_stats_plan(n, h, env_stride, time_stride, int(aligned16_all), C.byref(p)),
+           "rl8_rollout_stats_plan")
+    return StatsPlan(STATS_ROUTES[p.route], p.grid, p.trips)
+
+
+class GatherPlan(NamedTuple):
+    """What ``rl8_gather_minibatch`` launches: per field its route and tiled group (-1: none), and the launch count."""
+
+    routes: tuple[str, ...]
+    groups: tuple[int, ...]
+    launches: int
+
+
+def gather_minibatch_plan(indexed: bool, m: int, h: int, fields: Any, n_fields: int) -> GatherPlan:
+    """``fields``: a ``GatherField`` array as ``rl8_gather_minibatch`` takes it; its pointers are judged for alignment
+    only. Host arithmetic in the library, no device needed."""
+    routes, groups, launches = (C.c_int * MAX_GATHER_FIELDS)(), (C.c_int * MAX_GATHER_FIELDS)(), C.c_int(0)
+    _check(load().rl8_gather_minibatch_plan(int(indexed), m, h, fields, n_fields, routes, groups, C.byref(launches)),
+           "rl8_gather_minibatch_plan")
+    return GatherPlan(tuple(GATHER_ROUTES[routes[f]] for f in range(n_fields)), tuple(groups[f] for f in range(n_fields)),
+                      launches.value)
+
+
+class PackPlan(NamedTuple):
+    """The launch of the tiled transposition (``rl8_pack_plan_t``)."""
+
+    tile_steps: int
+    lds_bytes: int
+    tiles: int
+    grid: int
+
+
+def pack_plan(n: int, h: int, row_words: int) -> PackPlan:
+    """Tile shape and grid of ``rl8_pack_samples`` / ``rl8_gather_minibatch(index=NULL)``; no device needed."""
+    p = PackPlanStruct()
+    _check(load().rl8_pack_plan(n, h, row_words, C.byref(p)), "rl8_pack_plan")
+    return PackPlan(p.tile_steps, p.lds_bytes, p.tiles, p.grid)
 
 
 # --------------------------------------------------------------------------- #

@@ -26,7 +26,7 @@ def test_entries_are_declared_exported_and_bound():
         assert re.search(rf"\bint {name}\(", header), name
         assert hasattr(lib, name) and name in hip.SIGNATURES, name
     assert "} rl8_scatter_leaf;" in header
-    assert hip.abi_version()[0] == hip.ABI_VERSION == 106  # (compatible additions: no bump)
+    assert hip.abi_version()[0] == hip.ABI_VERSION == 107  # (compatible additions: no bump)
 
 
 def test_the_binding_matches_the_header_argument_for_argument():

@@ -34,7 +34,7 @@ def test_library_exports_every_declared_symbol():
     for name in names:
         assert hasattr(lib, name), f"librl8_amd.so lacks {name}"
     assert sorted(hip.SIGNATURES) == names, "rl8_amd/hip.py bindings out of sync with include/rl8_amd.h"
-    assert hip.abi_version() == (hip.ABI_VERSION, "gfx950") and hip.ABI_VERSION == 106
+    assert hip.abi_version() == (hip.ABI_VERSION, "gfx950") and hip.ABI_VERSION == 107
     assert lib.rl8_scratch_bytes() >= 2048 * 16 * 8
 
 
@@ -236,6 +236,80 @@ def test_collect_stats_from_raw_moments():
     assert stats["rewards/std"] == pytest.approx(rewards.std(ddof=1))
     assert stats["rewards/mean"] == pytest.approx(rewards.mean())
     assert scale == pytest.approx(rdr[:, 1:].std(ddof=1))
+
+
+def _raw_moments(rewards, rdr):
+    """The twelve raw numbers of ``rl8_rollout_stats_f32`` from numpy (whose min / max keep a NaN, as the kernel's do)."""
+    with np.errstate(invalid="ignore"):
+        ret = rewards.sum(1)
+        raw = [len(ret), ret.sum(), (ret**2).sum(), ret.min(), ret.max(), rewards.size, rewards.sum(), (rewards**2).sum(),
+               rewards.min(), rewards.max(), rdr[:, 1:].sum(), (rdr[:, 1:] ** 2).sum()]
+    return [float(v) for v in raw]  # (plain floats, as ``combine_rollout_stats`` hands them over)
+
+
+def test_collect_stats_carry_rewards_that_are_not_finite():
+    """A NaN reward must show in every statistic it touches, min / max included (``torch.min`` / ``torch.max``
+    propagate it); infinities are ordinary extrema whose mean is infinite and whose std is inf - inf."""
+    import math
+
+    from rl8_amd.algorithms._feedforward import _collect_stats_from_raw
+
+    rng = np.random.default_rng(1)
+    rewards, rdr = rng.standard_normal((6, 5)), rng.standard_normal((6, 6))
+    bad = rewards.copy()
+    bad[2, 3] = np.nan
+    stats, scale = _collect_stats_from_raw(_raw_moments(bad, rdr))
+    assert all(math.isnan(v) for v in stats.values()) and math.isfinite(scale)
+    bad[2, 3] = np.inf
+    stats, scale = _collect_stats_from_raw(_raw_moments(bad, rdr))
+    assert stats["rewards/max"] == stats["returns/max"] == stats["rewards/mean"] == stats["returns/mean"] == math.inf
+    assert math.isfinite(stats["rewards/min"]) and math.isfinite(stats["returns/min"])
+    assert math.isnan(stats["rewards/std"]) and math.isnan(stats["returns/std"])
+    bad[4, 0] = -np.inf
+    stats, _ = _collect_stats_from_raw(_raw_moments(bad, rdr))
+    assert (stats["rewards/min"], stats["rewards/max"]) == (-math.inf, math.inf)
+    assert math.isnan(stats["rewards/mean"]) and math.isnan(stats["returns/mean"])
+    bad_rdr = rdr.copy()
+    bad_rdr[0, 5] = np.nan
+    stats, scale = _collect_stats_from_raw(_raw_moments(rewards, bad_rdr))
+    assert all(math.isfinite(v) for v in stats.values()) and math.isnan(scale)
+
+
+def test_combine_rollout_stats_carries_a_nan_from_any_shard(monkeypatch):
+    """The shards' twelve numbers meet on the host: a NaN minimum or maximum of ONE shard is the global one, whichever
+    rank holds it, and an infinite extremum wins as any other number would."""
+    import math
+
+    import torch.distributed as dist
+
+    from rl8_amd import parallel
+
+    rng = np.random.default_rng(2)
+    rewards, rdr = rng.standard_normal((8, 5)), rng.standard_normal((8, 6))
+    rewards[5, 1], rewards[1, 2] = np.nan, np.inf
+    shards_raw = [torch.tensor(_raw_moments(rewards[:4], rdr[:4]), dtype=torch.float64),
+                  torch.tensor(_raw_moments(rewards[4:], rdr[4:]), dtype=torch.float64)]
+    single = parallel.EnvShards()
+    assert not single.active
+    for raw in shards_raw:  # one rank: the list as it is
+        got = single.combine_rollout_stats(raw)
+        assert all((math.isnan(a) and math.isnan(b)) or a == b for a, b in zip(got, raw.tolist()))
+    for order in ((0, 1), (1, 0)):
+        def all_gather(flat, src, group=None, order=order):
+            flat.copy_(torch.cat([shards_raw[order[0]], shards_raw[order[1]]]))
+
+        monkeypatch.setattr(dist, "all_gather_into_tensor", all_gather)
+        shards = parallel.EnvShards()
+        shards.world_size = 2
+        got = shards.combine_rollout_stats(shards_raw[order[0]])
+        assert got[0] == 8 and got[5] == 40
+        assert math.isnan(got[3]) and math.isnan(got[4]) and math.isnan(got[8]) and math.isnan(got[9])
+        assert math.isnan(got[1]) and math.isnan(got[6]) and math.isfinite(got[10])
+    rewards[5, 1] = 0.25   # the infinity alone: an ordinary maximum
+    shards_raw = [torch.tensor(_raw_moments(rewards[:4], rdr[:4]), dtype=torch.float64),
+                  torch.tensor(_raw_moments(rewards[4:], rdr[4:]), dtype=torch.float64)]
+    got = shards.combine_rollout_stats(shards_raw[1])
+    assert got[9] == math.inf == got[4] and got[8] == rewards.min() and got[6] == math.inf
 
 
 def test_column_sums_fold_equals_the_plain_sum():

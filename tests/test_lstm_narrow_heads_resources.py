@@ -86,7 +86,7 @@ def test_narrow_heads_entries_are_exported_and_bound():
     for name in ("linear_heads_narrow_forward", "linear_heads_narrow_forward_pair", "linear_heads_narrow_backward",
                  "rollout_step_dummy_heads_narrow"):
         assert callable(getattr(hip, name)), name
-    assert hip.ABI_VERSION == 106 and hip.HEADS_MAX_OUT == 8 and hip.ROWS_BACKWARD_HEADS == 4
+    assert hip.ABI_VERSION == 107 and hip.HEADS_MAX_OUT == 8 and hip.ROWS_BACKWARD_HEADS == 4
 
 
 def test_narrow_heads_entries_refuse_bad_arguments_before_launching():

@@ -36,7 +36,7 @@ def test_entries_are_declared_exported_and_bound():
         assert hasattr(lib, name) and name in hip.SIGNATURES, name
         params = re.sub(r"/\*.*?\*/", "", re.search(rf"\bint {name}\((.*?)\);", header, re.S).group(1))
         assert len(params.split(",")) == len(hip.SIGNATURES[name]), name
-    assert hip.abi_version()[0] == hip.ABI_VERSION == 106  # (compatible additions: no bump)
+    assert hip.abi_version()[0] == hip.ABI_VERSION == 107  # (compatible additions: no bump)
 
 
 def test_input_grad_refuses_bad_arguments_before_launching():
