@@ -36,6 +36,10 @@
  *                observations; RL8_AMD_WINDOW_KERNELS=0 puts both back on torch ops) rl8_window_last (collect(): the
  *                model's input at every timestep and at the bootstrap value), rl8_gather_windows (step(): the
  *                observation views of every minibatch)
+ *     masked     (rl8_amd.nn.functional's masked_avg, masked_max, masked_log_softmax, masked_categorical_sample on dense
+ *                f32 HIP tensors; RL8_AMD_MASKED_KERNELS=0 puts them back on torch ops) rl8_masked_pool[_backward]_f32
+ *                (TransformerTrader pools its attended window with it), rl8_masked_log_softmax[_backward]_f32,
+ *                rl8_masked_categorical_sample_f32 (their route: rl8_masked_rows_route)
  *     towers     rl8_mlp_tower_forward_f16_f32, rl8_mlp_tower_backward_gate_f16_f32, rl8_mlp_tower_backward_f16_f32,
  *                rl8_mlp_wgrad_gate_bits_f32, rl8_mlp_wgrad_fused_split_f32, rl8_mlp_wgrad_fused_pair_f32,
  *                rl8_mlp_pack_w2_f16, rl8_mlp_pack_w2_f16_gate, rl8_mlp_dout_pair_check, the *_supports / *_bytes /
@@ -95,7 +99,9 @@ extern "C" {
  * rl8_algotrading_reset_f32, rl8_algotrading_step_f32, rl8_rollout_step_algotrading_f32, rl8_gather_windows,
  * rl8_window_last.  107 (no signature changed: min / max of rl8_rollout_stats_f32 are NaN when a reward is, where they
  * used to drop it; rl8_gather_minibatch checks every field before its first launch; new queries
- * rl8_rollout_stats_plan, rl8_gather_minibatch_plan, rl8_pack_plan). */
+ * rl8_rollout_stats_plan, rl8_gather_minibatch_plan, rl8_pack_plan).  Added under 107 without a bump (new entries
+ * only): rl8_masked_rows_route, rl8_masked_pool_f32, rl8_masked_pool_backward_f32, rl8_masked_log_softmax_f32,
+ * rl8_masked_log_softmax_backward_f32, rl8_masked_categorical_sample_f32. */
 #define RL8_ABI_VERSION 107
 int rl8_abi_version(char *arch, int arch_len);
 
@@ -474,6 +480,48 @@ typedef struct {
 int rl8_gather_windows(const int64_t *index, int64_t m, int64_t h, const rl8_window_field *fields /*host*/,
                        int n_fields, void *stream);
 int rl8_window_last(int64_t t, int64_t n, const rl8_window_field *fields /*host*/, int n_fields, void *stream);
+
+/* Masked sequence ops                    src/rl8/nn/functional.py:126-257 (masked_avg :147-179, masked_categorical_sample
+ * :182-204, masked_log_softmax :207-228, masked_max :231-256)
+ * They read what the window entries above write: inputs [rows][size][...] and a byte mask [rows][size].  Every array is
+ * dense row-major f32; `mask` is [rows][t] or [rows][k] bytes (torch bool storage), NONZERO = VALID -- the reference's
+ * convention for these functions, the opposite of the windows' padding mask -- and NULL means no mask.
+ * rl8_masked_pool_f32, x [rows][t][e] -> out [rows][e], over t:
+ *   RL8_POOL_AVG  out = (sum_t m x) / sum_t m.  The product m x is formed, so a NaN or inf in a padded cell gives NaN as
+ *     mask * x does; a row without a valid cell gives 0 / 0 = NaN; mask == NULL: the mean over t.  The sum runs over
+ *     t in ascending order.  Backward: dx = m (dout / count), one division and one multiplication by 0 or 1.
+ *   RL8_POOL_MAX  padded cells read as -FLT_MAX; index_out [rows][e] is the first maximal t, the first NaN above
+ *     everything (torch.argmax on the CPU); out the value there.  A row without a valid cell therefore gives -FLT_MAX at
+ *     index 0.  Backward: dout at `index` unless that cell is padded (masked_fill's backward), zero elsewhere; every
+ *     element of dx is written, `index` is only compared with t (no address is formed from it).
+ *   Lanes run over the rows x e outputs with the t loop inside: no LDS, any rows, t, e >= 1.
+ * rl8_masked_log_softmax_f32, x [rows][k] -> out [rows][k], along k: z = x + (m ? 0 : -FLT_MAX), the float addition of
+ *   x + clamp(log(mask), FINFO.min, FINFO.max), then (z - max z) - log(sum exp(z - max z)) in torch's order; a row with
+ *   every class masked comes out uniform for moderate x because the same additions are done, not by a special case.
+ *   Backward, from the saved output: dx = dout - exp(out) sum_k dout.
+ * rl8_masked_categorical_sample_f32: z as above; one draw of Categorical(logits = z): index = argmax_j p_j / q_j with
+ *   p = softmax(z - logsumexp z), the first index on ties, q = noise [rows][k] (Exp(1) draws) or, noise == NULL, the
+ *   build's Philox stream at (seed, row_offset + row, step, word j); value_out [rows] = z[index], the masked logit that
+ *   x.gather(dim, samples) returns.  For k <= RL8_MAX_CLASSES the arithmetic and its order are those of
+ *   rl8_categorical_sample_logp_f32 with a = 1: on the same z and address both pick the same classes.
+ * Routes of the two [rows][k] families (rl8_masked_rows_route, host only; k < 1: RL8_ESIZE): one lane per row for
+ *   k <= RL8_MAX_CLASSES, else one wave per row, strided over k, with xor-butterfly reductions (a fixed order).
+ * RL8_ENULL: a required pointer (index_out / index in MAX mode too).  RL8_ESIZE: rows, t, e or k < 1.  RL8_ECONFIG: an
+ * unknown mode.  RL8_EALIGN: a float pointer off 4 bytes, an index pointer off 8.  All before any launch. */
+#define RL8_POOL_AVG 0
+#define RL8_POOL_MAX 1
+#define RL8_MASKED_ROWS_LANE 0 /* one lane per row, K <= RL8_MAX_CLASSES (64) */
+#define RL8_MASKED_ROWS_WAVE 1 /* one wave per row, strided over K, cross-lane reductions in a fixed order */
+int rl8_masked_rows_route(int k);
+int rl8_masked_pool_f32(const float *x, const uint8_t *mask, int64_t rows, int t, int e, int mode,
+                        float *out /*[rows][e]*/, int64_t *index_out /*[rows][e], MAX only*/, void *stream);
+int rl8_masked_pool_backward_f32(const float *dout, const uint8_t *mask, const int64_t *index, int64_t rows, int t, int e,
+                                 int mode, float *dx /*[rows][t][e]*/, void *stream);
+int rl8_masked_log_softmax_f32(const float *x, const uint8_t *mask, int64_t rows, int k, float *out, void *stream);
+int rl8_masked_log_softmax_backward_f32(const float *dout, const float *out, int64_t rows, int k, float *dx, void *stream);
+int rl8_masked_categorical_sample_f32(const float *x, const uint8_t *mask, const float *noise /*q [rows][k] or NULL*/,
+                                      int64_t rows, int k, uint64_t seed, uint64_t step, int64_t row_offset,
+                                      float *value_out /*[rows]*/, int64_t *index_out /*[rows]*/, void *stream);
 
 /* The same gather for a buffer that is shuffled many times per step()
  * (num_sgd_iters x num_minibatches): rl8_pack_samples lays the fields of every

@@ -5,6 +5,10 @@ view requirement, built by the window kernels), summed over four spans, next to 
 change of the price against the position; two BatchNorm towers give masked logits and a value. The towers run as torch
 modules (BatchNorm towers are outside the fused tower families).
 
+``TransformerTrader`` is the attentive feed-forward one: the same window, embedded cell by cell, goes through a
+parameter-sharing stack of residual self-attention blocks (``rl8_amd.nn``, on torch's ``nn.MultiheadAttention``) under
+the window's padding mask and is averaged over its valid cells by the masked-pool kernel (``nn.functional.masked_avg``).
+
 ``LSTMTrader`` is the recurrent one: an embedding of ``invested`` and the two price log-changes go through an LSTM
 whose latents feed a logits head and a value head. At hidden width 64 / 128 a training pass is one fused autograd
 node (``nn/fused_lstm.py:lstm_heads_forward``) that also returns the gradient of the LSTM's input, which is what
@@ -20,7 +24,8 @@ import torch
 import torch.nn as nn
 
 from ..data import DataKeys, Device
-from ..models import MLP, Model, get_activation
+from ..models import Model
+from ..nn import MLP, SelfAttention, SelfAttentionStack, get_activation, masked_avg
 from ..models_recurrent import RecurrentModel, _lstm_state_spec, _run_lstm_heads, _small_head
 from ..specs import TensorSpec
 from ..tensordict import TensorDict
@@ -96,6 +101,82 @@ class MLPTrader(Model):
         return self._value
 
 
+class TransformerTrader(Model):
+    """The reference's ``AttentiveAlpaca`` (``examples/algotrading/models/transformer.py``; its ``state_dict`` loads as
+    is): ``("obs", "LOG_CHANGE(price)") -> ViewRequirement(shift=seq_len)`` on top of the default view,
+    ``Linear(1, price_embed_dim)`` on every cell of the window, ``num_layers`` passes through ONE residual
+    ``SelfAttention(price_embed_dim, num_heads, hidden_dim=hiddens[0])`` with the padded cells masked as keys, the
+    average over the valid cells, and next to it ``Embedding(2, invested_embed_dim)`` on ``invested`` and
+    ``LOG_CHANGE(price, position)`` -> the two BatchNorm towers and heads of :class:`MLPTrader`."""
+
+    def __init__(
+        self,
+        observation_spec: TensorSpec,
+        action_spec: TensorSpec,
+        /,
+        invested_embed_dim: int = 2,
+        price_embed_dim: int = 8,
+        seq_len: int = 4,
+        num_heads: int = 4,
+        num_layers: int = 2,
+        hiddens: Sequence[int] = (64, 64),
+        activation_fn: str = "relu",
+    ) -> None:
+        super().__init__(observation_spec, action_spec, invested_embed_dim=invested_embed_dim,
+                         price_embed_dim=price_embed_dim, seq_len=seq_len, num_heads=num_heads, num_layers=num_layers,
+                         hiddens=hiddens, activation_fn=activation_fn)
+        self.view_requirements[(DataKeys.OBS, LOG_CHANGE)] = ViewRequirement(shift=seq_len)
+        self.invested_embedding = nn.Embedding(2, invested_embed_dim)
+        self.price_embedding = nn.Linear(1, price_embed_dim)
+        self.price_attention = SelfAttentionStack(
+            SelfAttention(price_embed_dim, num_heads=num_heads, hidden_dim=hiddens[0], activation_fn=activation_fn,
+                          skip_kind="residual"),
+            num_layers,
+            share_parameters=True,
+        )
+
+        def tower() -> list[nn.Module]:
+            return [
+                MLP(invested_embed_dim + 1 + price_embed_dim, hiddens, activation_fn=activation_fn,
+                    norm_layer=nn.BatchNorm1d),
+                get_activation(activation_fn),
+            ]
+
+        # (modules are created in the reference's order, so one seed initialises both alike)
+        self.feature_model = nn.Sequential(*tower())
+        self.feature_model.append(_small_head(hiddens[-1], 3))
+        self.vf_model = nn.Sequential(*tower(), nn.Linear(hiddens[-1], 1))
+        self._value: None | torch.Tensor = None
+
+    def forward(self, batch: TensorDict, /) -> TensorDict:
+        obs = batch[DataKeys.OBS]
+        window = obs[LOG_CHANGE]
+        padding_mask = window[DataKeys.PADDING_MASK]  # [B, seq_len + 1] bool, True = padded; the last cell never is
+        x_price = self.price_embedding(window[DataKeys.INPUTS])  # [B, seq_len + 1, price_embed_dim]
+        x_price = self.price_attention(x_price, key_padding_mask=padding_mask)
+        x = torch.cat(
+            [
+                self.invested_embedding(obs["invested"].flatten()),
+                obs[LOG_CHANGE_POSITION],
+                masked_avg(x_price, mask=~padding_mask, dim=1, keepdim=False),
+            ],
+            dim=-1,
+        )
+        finfo = torch.finfo(torch.float32)
+        mask = torch.clamp(torch.log(obs["action_mask"].to(torch.float32)), min=finfo.min, max=finfo.max)
+        logits = self.feature_model(x).reshape(-1, 1, 3) + mask.reshape(-1, 1, 3)
+        self._value = self.vf_model(x)
+        return TensorDict({"logits": logits}, batch_size=batch.batch_size, device=x.device)
+
+    def to(self, device: Device) -> "TransformerTrader":  # type: ignore[override]
+        self._value = None
+        return super().to(device)  # type: ignore[return-value]
+
+    def value_function(self) -> torch.Tensor:
+        assert self._value is not None
+        return self._value
+
+
 class LSTMTrader(RecurrentModel):
     """``Embedding(2, invested_embed_dim)`` on ``invested``, concatenated with ``LOG_CHANGE(price, position)`` and
     ``LOG_CHANGE(price)`` -> ``LSTM(invested_embed_dim + 2, hidden_size)`` -> a small-initialised ``Linear(hidden, 3)``
@@ -160,4 +241,4 @@ class LSTMTrader(RecurrentModel):
         return self._value
 
 
-__all__ = ["LSTMTrader", "MLPTrader"]
+__all__ = ["LSTMTrader", "MLPTrader", "TransformerTrader"]

@@ -36,6 +36,8 @@ MAX_CLASSES = 64
 MAX_GATHER_FIELDS = 8
 LAYOUT_ENV_MAJOR = 0
 LAYOUT_TIME_MAJOR = 1
+POOL_AVG, POOL_MAX = 0, 1  # RL8_POOL_*
+MASKED_ROWS_LANE, MASKED_ROWS_WAVE = 0, 1  # RL8_MASKED_ROWS_*
 
 
 class HipExtensionError(RuntimeError):
@@ -180,6 +182,12 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_gather_sequences": [_vp, _i64, _i32, _i64, C.POINTER(GatherField), _i32, _vp],
     "rl8_gather_windows": [_vp, _i64, _i64, C.POINTER(WindowField), _i32, _vp],
     "rl8_window_last": [_i64, _i64, C.POINTER(WindowField), _i32, _vp],
+    "rl8_masked_rows_route": [_i32],
+    "rl8_masked_pool_f32": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp],
+    "rl8_masked_pool_backward_f32": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "rl8_masked_log_softmax_f32": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "rl8_masked_log_softmax_backward_f32": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "rl8_masked_categorical_sample_f32": [_vp, _vp, _vp, _i64, _i32, _u64, _u64, _i64, _vp, _vp, _vp],
     "rl8_pack_samples": [_vp, _i32, _i64, _i64, _vp, _i32, _vp],
     "rl8_gather_packed": [_vp, _i64, _vp, _i32, _vp, _i32, _vp],
     "rl8_pack_plan": [_i64, _i64, _i32, C.POINTER(PackPlanStruct)],
@@ -1196,6 +1204,99 @@ def window_last(t: int, leaves: Sequence[torch.Tensor],
     with _timed("window_last", n):
         _check(load().rl8_window_last(t, n, fields, len(outs), _stream()), "rl8_window_last")
     return outs
+
+
+# --------------------------------------------------------------------------- #
+# Masked sequence ops (rl8_amd/csrc/masked_kernels.hip).
+# --------------------------------------------------------------------------- #
+def _byte_mask(mask: None | torch.Tensor, shape: tuple, what: str) -> None | torch.Tensor:
+    """``mask`` (bool or uint8, nonzero = VALID) as the dense byte array the kernels read; ``None`` stays ``None``."""
+    if mask is None:
+        return None
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{what} must be bool or uint8, got {mask.dtype}")
+    if tuple(mask.shape) != shape:
+        raise ValueError(f"{what} must have shape {shape}, got {tuple(mask.shape)}")
+    if not mask.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return mask
+
+
+def masked_rows_route(k: int) -> int:
+    """``MASKED_ROWS_LANE`` or ``MASKED_ROWS_WAVE`` for rows of ``k`` classes (host only)."""
+    route = int(load().rl8_masked_rows_route(k))
+    _check(min(route, 0), "rl8_masked_rows_route")
+    return route
+
+
+def masked_pool(x: torch.Tensor, mask: None | torch.Tensor, mode: int) -> tuple[torch.Tensor, None | torch.Tensor]:
+    """``x [rows, T, E]`` pooled over T under ``mask [rows, T]`` (nonzero = valid, ``None`` = no mask):
+    ``(out [rows, E], index [rows, E] int64 in MAX mode or None)``."""
+    x = _dense(x.detach(), torch.float32, "x")
+    rows, t, e = x.shape
+    mask = _byte_mask(mask, (rows, t), "mask")
+    out = torch.empty(rows, e, dtype=torch.float32, device=x.device)
+    index = torch.empty(rows, e, dtype=torch.int64, device=x.device) if mode == POOL_MAX else None
+    with _timed("masked_pool", rows):
+        _check(load().rl8_masked_pool_f32(_ptr(x), _ptr(mask), rows, t, e, mode, _ptr(out), _ptr(index), _stream()),
+               "rl8_masked_pool_f32")
+    return out, index
+
+
+def masked_pool_backward(dout: torch.Tensor, mask: None | torch.Tensor, index: None | torch.Tensor, t: int,
+                         mode: int) -> torch.Tensor:
+    """Gradient ``[rows, T, E]`` of :func:`masked_pool`'s input from ``dout [rows, E]``; every element is written."""
+    dout = _dense(dout.detach(), torch.float32, "dout")
+    rows, e = dout.shape
+    mask = _byte_mask(mask, (rows, t), "mask")
+    if index is not None:
+        _shaped(index, (rows, e), "index", torch.int64)
+    dx = torch.empty(rows, t, e, dtype=torch.float32, device=dout.device)
+    with _timed("masked_pool_backward", rows):
+        _check(load().rl8_masked_pool_backward_f32(_ptr(dout), _ptr(mask), _ptr(index), rows, t, e, mode, _ptr(dx),
+                                                   _stream()), "rl8_masked_pool_backward_f32")
+    return dx
+
+
+def masked_log_softmax(x: torch.Tensor, mask: None | torch.Tensor) -> torch.Tensor:
+    """Log-softmax of ``x [rows, K]`` along K under ``mask [rows, K]`` (nonzero = valid, ``None`` = no mask)."""
+    x = _dense(x.detach(), torch.float32, "x")
+    rows, k = x.shape
+    mask = _byte_mask(mask, (rows, k), "mask")
+    out = torch.empty_like(x)
+    with _timed("masked_log_softmax", rows):
+        _check(load().rl8_masked_log_softmax_f32(_ptr(x), _ptr(mask), rows, k, _ptr(out), _stream()),
+               "rl8_masked_log_softmax_f32")
+    return out
+
+
+def masked_log_softmax_backward(dout: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    dout = _dense(dout.detach(), torch.float32, "dout")
+    rows, k = dout.shape
+    _shaped(out, (rows, k), "out")
+    dx = torch.empty_like(dout)
+    with _timed("masked_log_softmax_backward", rows):
+        _check(load().rl8_masked_log_softmax_backward_f32(_ptr(dout), _ptr(out), rows, k, _ptr(dx), _stream()),
+               "rl8_masked_log_softmax_backward_f32")
+    return dx
+
+
+def masked_categorical_sample(x: torch.Tensor, mask: None | torch.Tensor, noise: None | torch.Tensor, *, seed: int = 0,
+                              step: int = 0, row_offset: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    """One draw per row of ``x [rows, K]`` under ``mask``: ``(masked logit of the class [rows], class [rows] int64)``.
+    ``noise`` [rows, K] are injected Exp(1) draws; ``None`` takes the Philox stream at ``(seed, row_offset + row, step)``."""
+    x = _dense(x.detach(), torch.float32, "x")
+    rows, k = x.shape
+    mask = _byte_mask(mask, (rows, k), "mask")
+    if noise is not None:
+        _shaped(noise, (rows, k), "noise")
+    value = torch.empty(rows, dtype=torch.float32, device=x.device)
+    index = torch.empty(rows, dtype=torch.int64, device=x.device)
+    with _timed("masked_categorical_sample", rows):
+        _check(load().rl8_masked_categorical_sample_f32(_ptr(x), _ptr(mask), _ptr(noise), rows, k, seed, step, row_offset,
+                                                        _ptr(value), _ptr(index), _stream()),
+               "rl8_masked_categorical_sample_f32")
+    return value, index
 
 
 class PackedSamples:

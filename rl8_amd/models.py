@@ -19,57 +19,10 @@ import torch.nn as nn
 
 from ._utils import assert_1d_spec
 from .data import DataKeys, Device
+from .nn.modules import ACTIVATIONS, MLP, get_activation  # noqa: F401  (they live in rl8_amd.nn; re-exported here)
 from .specs import Categorical, TensorSpec, Unbounded
 from .tensordict import TensorDict
 from .views import ViewKind, ViewRequirement
-
-ACTIVATIONS: dict[str, type[nn.Module]] = {
-    "elu": nn.ELU,
-    "gelu": nn.GELU,
-    "identity": nn.Identity,
-    "leaky_relu": nn.LeakyReLU,
-    "relu": nn.ReLU,
-    "relu6": nn.ReLU6,
-    "selu": nn.SELU,
-    "sigmoid": nn.Sigmoid,
-    "swish": nn.SiLU,
-    "tanh": nn.Tanh,
-}
-
-
-def get_activation(name: str, /, **params: Any) -> nn.Module:
-    """Activation module by name."""
-    return ACTIVATIONS[name](**params)
-
-
-class MLP(nn.Sequential):
-    """``Linear -> act -> ... -> Linear`` (no trailing activation)."""
-
-    def __init__(
-        self,
-        input_dim: int,
-        hiddens: Sequence[int],
-        /,
-        *,
-        activation_fn: str = "relu",
-        norm_layer: None | type[nn.Module] = None,
-        bias: bool = True,
-        dropout: float = 0.0,
-        inplace: bool = False,
-    ) -> None:
-        params = {"inplace": inplace} if inplace else {}
-        layers: list[nn.Module] = []
-        in_dim = input_dim
-        for hidden_dim in hiddens[:-1]:
-            layers.append(nn.Linear(in_dim, hidden_dim, bias=bias))
-            if norm_layer is not None:
-                layers.append(norm_layer(hidden_dim))
-            layers.append(get_activation(activation_fn, **params))
-            if dropout:
-                layers.append(nn.Dropout(p=dropout))
-            in_dim = hidden_dim
-        layers.append(nn.Linear(in_dim, hiddens[-1], bias=bias))
-        super().__init__(*layers)
 
 
 class Model(nn.Module):

@@ -1,4 +1,4 @@
-"""GAE and the PPO loss, backed by the gfx950 kernels.
+"""GAE, the PPO loss and the masked sequence functions, backed by the gfx950 kernels.
 
 Signatures and semantics follow the reference's ``src/rl8/nn/functional.py``:
 ``generalized_advantage_estimate`` :50-123 and ``ppo_losses`` :259-363. Both take
@@ -12,18 +12,24 @@ and return tensordicts exactly as the reference does; what runs underneath is
   w.r.t. the distribution features and the value estimates in one launch, hooked
   into autograd so ``losses["total"].backward()`` keeps working.
 
-Tensors must live on a HIP device: there is no CPU fallback.
+For those two, tensors must live on a HIP device: there is no CPU fallback.
+
+The mask helpers and the masked sequence functions (:13-47, :126-257, :366-400; the second half of this file) are
+general-purpose: user models and host tests call them on any device. ``masked_avg``, ``masked_max``,
+``masked_log_softmax`` and ``masked_categorical_sample`` run ``rl8_masked_*`` (``csrc/masked_kernels.hip``) on dense
+float32 HIP tensors reduced along the dimension the kernels take, and the reference's torch expression everywhere else.
 
 """
 
 from __future__ import annotations
 
+import os
 from typing import Any, Callable
 
 import numpy as np
 import torch
 
-from .. import hip
+from .. import distributions, hip
 from ..data import DataKeys
 from ..distributions import Categorical, Distribution, Normal, SquashedNormal
 from ..tensordict import TensorDict
@@ -407,3 +413,241 @@ def ppo_losses(
         {"entropy": entropy_loss, "policy": policy_loss, "vf": vf_loss, "total": total_loss},
         batch_size=[],
     )
+
+
+# --------------------------------------------------------------------------- #
+# Masks, skip connections and the masked sequence functions.
+# --------------------------------------------------------------------------- #
+FINFO = torch.finfo(torch.float32)
+
+
+def binary_mask_to_float_mask(mask: torch.Tensor, /) -> torch.Tensor:
+    """``0`` / ``1`` -> ``-inf`` / ``0``: a float mask whose ``0`` marks a VALID cell."""
+    out = mask.float()
+    out = out.masked_fill(mask == 0, float("-inf"))
+    return out.masked_fill(mask == 1, 0.0)
+
+
+def float_mask_to_binary_mask(mask: torch.Tensor, /) -> torch.Tensor:
+    """``0`` / ``-inf`` -> ``True`` / ``False``: a boolean mask whose ``True`` marks a VALID cell."""
+    out = mask.float()
+    out = out.masked_fill(mask == float("-inf"), False)
+    return out.masked_fill(mask == 0, True).bool()
+
+
+def mask_from_lengths(x: torch.Tensor, lengths: torch.Tensor, /) -> torch.Tensor:
+    """``[B, T]`` boolean mask of the VALID cells of ``x [B, T, ...]`` whose sequences have ``lengths [B]``."""
+    b, t = x.shape[:2]
+    lengths = lengths.long().view(-1, 1).expand(b, t)
+    steps = torch.arange(t, device=lengths.device, dtype=lengths.dtype).expand(b, t)
+    return steps < lengths
+
+
+def skip_connection(x: torch.Tensor, y: torch.Tensor, /, *, kind: None | str = "cat", dim: int = -1) -> torch.Tensor:
+    """``x + y`` (``"residual"``), ``cat([x, y], dim)`` (``"cat"``) or ``y`` (``None``)."""
+    if kind == "residual":
+        return x + y
+    if kind == "cat":
+        return torch.cat([x, y], dim=dim)
+    if kind is None:
+        return y
+    raise ValueError(f"No skip connection type for {kind}.")
+
+
+def _masked_kernels_on() -> bool:
+    """``RL8_AMD_MASKED_KERNELS=0`` (read on every call) puts the masked functions on their torch expressions."""
+    return os.environ.get("RL8_AMD_MASKED_KERNELS", "1") != "0"
+
+
+def _kernel_input(x: torch.Tensor) -> bool:
+    return x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0 and _masked_kernels_on()
+
+
+def _kernel_mask(mask: None | torch.Tensor, shape: tuple) -> bool:
+    return mask is None or (mask.is_cuda and mask.dtype in (torch.bool, torch.uint8)
+                            and tuple(mask.shape) == tuple(shape))
+
+
+def _expand_mask(mask: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    while mask.dim() < x.dim():
+        mask = mask.unsqueeze(-1)
+    return mask
+
+
+def _add_log_mask(x: torch.Tensor, mask: None | torch.Tensor) -> torch.Tensor:
+    """``x`` with ``clamp(log(mask))`` added: ``-FLT_MAX`` on the padded cells."""
+    if mask is None:
+        return x
+    return x + torch.clamp(torch.log(_expand_mask(mask, x)), FINFO.min, FINFO.max)
+
+
+def _wants_grad(x: torch.Tensor) -> bool:
+    return torch.is_grad_enabled() and x.requires_grad
+
+
+class _MaskedAvg(torch.autograd.Function):
+    """``rl8_masked_pool_f32`` / ``rl8_masked_pool_backward_f32`` in AVG mode on ``[B, T, ...]``: saves the mask only."""
+
+    @staticmethod
+    def forward(ctx: Any, x: torch.Tensor, mask: None | torch.Tensor) -> torch.Tensor:
+        b, t = x.shape[:2]
+        out, _ = hip.masked_pool(x.view(b, t, -1), mask, hip.POOL_AVG)
+        ctx.shape = x.shape
+        ctx.save_for_backward(*([] if mask is None else [mask]))
+        return out.view(b, *x.shape[2:])
+
+    @staticmethod
+    def backward(ctx: Any, dout: torch.Tensor) -> tuple[Any, ...]:
+        mask = ctx.saved_tensors[0] if ctx.saved_tensors else None
+        b, t = ctx.shape[:2]
+        dx = hip.masked_pool_backward(dout.contiguous().view(b, -1), mask, None, t, hip.POOL_AVG)
+        return dx.view(ctx.shape), None
+
+
+class _MaskedMax(torch.autograd.Function):
+    """The same pair in MAX mode: saves the indices (and the mask, an input)."""
+
+    @staticmethod
+    def forward(ctx: Any, x: torch.Tensor, mask: None | torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        b, t = x.shape[:2]
+        out, index = hip.masked_pool(x.view(b, t, -1), mask, hip.POOL_MAX)
+        ctx.shape = x.shape
+        ctx.save_for_backward(index, *([] if mask is None else [mask]))
+        index = index.view(b, 1, *x.shape[2:])
+        ctx.mark_non_differentiable(index)
+        return out.view(b, 1, *x.shape[2:]), index
+
+    @staticmethod
+    def backward(ctx: Any, dout: torch.Tensor, _dindex: Any) -> tuple[Any, ...]:
+        index, *rest = ctx.saved_tensors
+        b, t = ctx.shape[:2]
+        dx = hip.masked_pool_backward(dout.contiguous().view(b, -1), rest[0] if rest else None, index, t, hip.POOL_MAX)
+        return dx.view(ctx.shape), None
+
+
+class _MaskedLogSoftmax(torch.autograd.Function):
+    """``rl8_masked_log_softmax_f32`` / ``..._backward_f32`` along the last dimension: saves its output."""
+
+    @staticmethod
+    def forward(ctx: Any, x: torch.Tensor, mask: None | torch.Tensor) -> torch.Tensor:
+        k = x.shape[-1]
+        out = hip.masked_log_softmax(x.view(-1, k), None if mask is None else mask.view(-1, k)).view(x.shape)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx: Any, dout: torch.Tensor) -> tuple[Any, ...]:
+        (out,) = ctx.saved_tensors
+        k = out.shape[-1]
+        return hip.masked_log_softmax_backward(dout.contiguous().view(-1, k), out.view(-1, k)).view(out.shape), None
+
+
+class _MaskedSample(torch.autograd.Function):
+    """``rl8_masked_categorical_sample_f32`` on ``[B, K]``; the gathered logit's gradient is a one-hot scatter."""
+
+    @staticmethod
+    def forward(ctx: Any, x: torch.Tensor, mask: None | torch.Tensor, noise: None | torch.Tensor, seed: int, step: int,
+                row_offset: int) -> tuple[torch.Tensor, torch.Tensor]:
+        value, index = hip.masked_categorical_sample(x, mask, noise, seed=seed, step=step, row_offset=row_offset)
+        index = index.unsqueeze(-1)
+        ctx.shape = x.shape
+        ctx.save_for_backward(index)
+        ctx.mark_non_differentiable(index)
+        return value.unsqueeze(-1), index
+
+    @staticmethod
+    def backward(ctx: Any, dvalue: torch.Tensor, _dindex: Any) -> tuple[Any, ...]:
+        (index,) = ctx.saved_tensors
+        dx = torch.zeros(ctx.shape, dtype=dvalue.dtype, device=dvalue.device).scatter_(1, index, dvalue)
+        return dx, None, None, None, None, None
+
+
+def masked_avg(x: torch.Tensor, /, *, mask: None | torch.Tensor = None, dim: int = 1, keepdim: bool = False) -> torch.Tensor:
+    """Average of ``x [B, T, ...]`` along ``dim`` over the cells that ``mask [B, T]`` marks VALID (all of them without a
+    mask). A row without a valid cell is ``0 / 0 = NaN``, as in the reference."""
+    if x.dim() >= 2 and dim % x.dim() == 1 and _kernel_input(x) and _kernel_mask(mask, x.shape[:2]):
+        if mask is not None:
+            mask = mask.contiguous()
+        if _wants_grad(x):
+            avg = _MaskedAvg.apply(x, mask)
+        else:
+            b, t = x.shape[:2]
+            avg = hip.masked_pool(x.view(b, t, -1), mask, hip.POOL_AVG)[0].view(b, *x.shape[2:])
+        return avg.unsqueeze(1) if keepdim else avg
+    if mask is not None:
+        mask = _expand_mask(mask, x)
+        count = mask.sum(dim=dim, keepdim=True)
+        avg = (mask * x).sum(dim=dim, keepdim=True) / count
+    else:
+        avg = x.mean(dim=dim, keepdim=True)
+    return avg if keepdim else avg.squeeze(dim)
+
+
+def masked_max(x: torch.Tensor, /, *, mask: None | torch.Tensor = None, dim: int = 1) -> tuple[torch.Tensor, torch.Tensor]:
+    """Maximum of ``x [B, T, ...]`` along ``dim`` over the VALID cells (padded ones read as the lowest finite float)
+    and its index, both with ``dim`` kept."""
+    if x.dim() >= 2 and dim % x.dim() == 1 and _kernel_input(x) and _kernel_mask(mask, x.shape[:2]):
+        if mask is not None:
+            mask = mask.contiguous()
+        if _wants_grad(x):
+            return _MaskedMax.apply(x, mask)
+        b, t = x.shape[:2]
+        out, index = hip.masked_pool(x.view(b, t, -1), mask, hip.POOL_MAX)
+        return out.view(b, 1, *x.shape[2:]), index.view(b, 1, *x.shape[2:])
+    if mask is not None:
+        x = x.masked_fill(~_expand_mask(mask, x).bool(), FINFO.min)
+    index = x.argmax(dim=dim, keepdim=True)
+    return x.gather(dim, index), index
+
+
+def masked_log_softmax(x: torch.Tensor, /, *, mask: None | torch.Tensor = None, dim: int = -1) -> torch.Tensor:
+    """Log-softmax of ``x`` along ``dim`` with ``clamp(log(mask))`` added first: padded cells sit at the lowest finite
+    float, so a row that is padded throughout comes out uniform."""
+    if x.dim() >= 1 and dim % x.dim() == x.dim() - 1 and _kernel_input(x) and _kernel_mask(mask, x.shape):
+        if mask is not None:
+            mask = mask.contiguous()
+        if _wants_grad(x):
+            return _MaskedLogSoftmax.apply(x, mask)
+        k = x.shape[-1]
+        return hip.masked_log_softmax(x.view(-1, k), None if mask is None else mask.view(-1, k)).view(x.shape)
+    return torch.nn.functional.log_softmax(_add_log_mask(x, mask), dim=dim)
+
+
+def masked_categorical_sample(
+    x: torch.Tensor,
+    /,
+    *,
+    mask: None | torch.Tensor = None,
+    dim: int = 1,
+    noise: None | torch.Tensor = None,
+    noise_stream: None | "distributions.NoiseStream" = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """One categorical draw along the last dimension of the logits ``x`` (with ``clamp(log(mask))`` added), and the
+    masked logits gathered along ``dim`` at the drawn classes: ``(logits, classes)``, the classes with a trailing 1.
+
+    ``noise`` (the shape of ``x``) injects the Exp(1) draws ``q`` of ``argmax p / q``; otherwise a HIP ``[B, T]`` input
+    draws from ``noise_stream`` (default: ``distributions.default_noise``, the stream ``Distribution.sample`` uses) and
+    any other input from ``torch.distributions.Categorical``, as the reference does.
+
+    """
+    if (
+        x.dim() == 2 and dim % 2 == 1 and _kernel_input(x) and _kernel_mask(mask, x.shape)
+        and (noise is None or (_kernel_input(noise) and noise.shape == x.shape))
+    ):
+        seed = step = row_offset = 0
+        if noise is None:
+            stream = noise_stream or distributions.default_noise
+            seed, step, row_offset = stream.seed, stream.next_step(), stream.row_offset
+        if mask is not None:
+            mask = mask.contiguous()
+        if _wants_grad(x):
+            return _MaskedSample.apply(x, mask, noise, seed, step, row_offset)
+        value, index = hip.masked_categorical_sample(x, mask, noise, seed=seed, step=step, row_offset=row_offset)
+        return value.unsqueeze(-1), index.unsqueeze(-1)
+    x = _add_log_mask(x, mask)
+    if noise is None:
+        samples = torch.distributions.Categorical(logits=x).sample().unsqueeze(-1)
+    else:
+        probs = torch.distributions.Categorical(logits=x).probs
+        samples = (probs / noise).argmax(dim=-1).unsqueeze(-1)
+    return x.gather(dim, samples), samples
