@@ -488,26 +488,8 @@ class Algorithm:
         H = hp.horizon
         tm = self._tm
         rdr = tm.get(DataKeys.REVERSED_DISCOUNTED_RETURNS)
-        # the observation slabs: one for a tensor spec, one per leaf for a composite one
-        obs_slabs = self._tm_obs if self._tm_obs is not None else {None: tm[DataKeys.OBS]}
         with profile_ms() as collect_timer:
-            env_was_reset = False
-            carry = (self.state.horizons and hp.horizons_per_env_reset < 0) or (
-                self.state.horizons % hp.horizons_per_env_reset
-            )
-            if carry:
-                for storage in obs_slabs.values():
-                    storage[0].copy_(storage[H])
-                if rdr is not None:
-                    rdr[0].copy_(rdr[H])
-            else:
-                first = self.env.reset(config=env_config)
-                for leaf, storage in obs_slabs.items():
-                    storage[0].copy_(first if leaf is None else first[leaf])
-                env_was_reset = True
-                if rdr is not None:
-                    rdr[0].zero_()
-
+            env_was_reset = self._reset_or_carry(env_config)
             fused = self._fusable()
             # windowed views: built by one launch per column instead of torch ops on buffer[:, :t + 1]
             plan = None if self._identity_views() else self._window_plan()
@@ -546,16 +528,45 @@ class Algorithm:
                 self.buffer[DataKeys.REVERSED_DISCOUNTED_RETURNS] if rdr is not None else None,
             )
             collect_stats, reward_scale = _collect_stats_from_raw(self.shards.combine_rollout_stats(raw))
-            self.state.horizons += 1
-            self.state.buffered = True
-            self.state.reward_scale = reward_scale if hp.normalize_rewards else 1.0
-            self.injected_noise = None
             if record is not None:  # (a Python-level write to the observations before step() voids the record)
                 record.seal(tm[DataKeys.OBS])
+        return self._finish_collect(collect_stats, reward_scale, env_was_reset, collect_timer())
 
+    def _reset_or_carry(self, env_config: None | dict[str, Any]) -> bool:
+        """Column 0 of a rollout: the env's reset observation (and ``rdr`` = 0) according to
+        ``horizons_per_env_reset``, else the last column of the previous one.  Returns whether the env was reset."""
+        hp, tm = self.hparams, self._tm
+        H = hp.horizon
+        rdr = tm.get(DataKeys.REVERSED_DISCOUNTED_RETURNS)
+        # the observation slabs: one for a tensor spec, one per leaf for a composite one
+        obs_slabs = self._tm_obs if self._tm_obs is not None else {None: tm[DataKeys.OBS]}
+        carry = (self.state.horizons and hp.horizons_per_env_reset < 0) or (
+            self.state.horizons % hp.horizons_per_env_reset
+        )
+        if carry:
+            for storage in obs_slabs.values():
+                storage[0].copy_(storage[H])
+            if rdr is not None:
+                rdr[0].copy_(rdr[H])
+            return False
+        first = self.env.reset(config=env_config)
+        for leaf, storage in obs_slabs.items():
+            storage[0].copy_(first if leaf is None else first[leaf])
+        if rdr is not None:
+            rdr[0].zero_()
+        return True
+
+    def _finish_collect(self, collect_stats: CollectStats, reward_scale: float, env_was_reset: bool,
+                        collect_ms: float) -> CollectStats:
+        """What every ``collect()`` ends on: the buffer counts as filled, the injected noise as used."""
+        hp = self.hparams
+        self.state.horizons += 1
+        self.state.buffered = True
+        self.state.reward_scale = reward_scale if hp.normalize_rewards else 1.0
+        self.injected_noise = None
         collect_stats["env/resets"] = hp.num_envs * int(env_was_reset)
         collect_stats["env/steps"] = hp.num_envs * hp.horizon
-        collect_stats["profiling/collect_ms"] = collect_timer()
+        collect_stats["profiling/collect_ms"] = collect_ms
         return collect_stats
 
     def _obs_column(self, t: int) -> torch.Tensor | TensorDict:
@@ -620,8 +631,6 @@ class Algorithm:
     ) -> None:
         """Any ``Env`` / ``Distribution``: policy.sample -> env.step -> one
         bookkeeping launch.  ``views``: the model's input at column ``t`` when the window kernels built it."""
-        tm = self._tm
-        rdr = tm.get(DataKeys.REVERSED_DISCOUNTED_RETURNS)
         self.policy.injected_noise = noise
         self.noise.step = step_id  # policy.sample advances it again by one
         sample = self.policy.sample(
@@ -636,40 +645,24 @@ class Algorithm:
             return_values=True,
             return_views=False,
         )
-        out = self.env.step(sample[DataKeys.ACTIONS])
+        self._scatter_step(sample, self.env.step(sample[DataKeys.ACTIONS]), t, gamma)
+
+    def _scatter_step(self, sample: TensorDict, out: TensorDict, t: int, gamma: float) -> None:
+        """The bookkeeping launch of a generic timestep: what the policy sampled at column ``t`` and what ``env.step``
+        returned for it go to the buffer's columns, the observation (each leaf of a dict one) to column ``t + 1``."""
+        tm = self._tm
+        rdr = tm.get(DataKeys.REVERSED_DISCOUNTED_RETURNS)
+        sampled = [sample[key].contiguous() for key in (DataKeys.ACTIONS, DataKeys.LOGP, DataKeys.VALUES)]
+        columns = [tm[key][t] for key in (DataKeys.ACTIONS, DataKeys.LOGP, DataKeys.VALUES, DataKeys.REWARDS)]
+        rdr_pair = (rdr[t], rdr[t + 1]) if rdr is not None else (None, None)
+        obs = out[DataKeys.OBS]
         if self._tm_obs is not None:
-            obs = out[DataKeys.OBS]
-            hip.rollout_scatter_leaves(
-                sample[DataKeys.ACTIONS].contiguous(),
-                sample[DataKeys.LOGP].contiguous(),
-                sample[DataKeys.VALUES].contiguous(),
-                out[DataKeys.REWARDS].contiguous(),
-                [obs[leaf].contiguous() for leaf in self._tm_obs],
-                tm[DataKeys.ACTIONS][t],
-                tm[DataKeys.LOGP][t],
-                tm[DataKeys.VALUES][t],
-                tm[DataKeys.REWARDS][t],
-                [storage[t + 1] for storage in self._tm_obs.values()],
-                rdr[t] if rdr is not None else None,
-                rdr[t + 1] if rdr is not None else None,
-                gamma,
-            )
-            return
-        hip.rollout_scatter(
-            sample[DataKeys.ACTIONS].contiguous(),
-            sample[DataKeys.LOGP].contiguous(),
-            sample[DataKeys.VALUES].contiguous(),
-            out[DataKeys.REWARDS].contiguous(),
-            out[DataKeys.OBS].contiguous(),
-            tm[DataKeys.ACTIONS][t],
-            tm[DataKeys.LOGP][t],
-            tm[DataKeys.VALUES][t],
-            tm[DataKeys.REWARDS][t],
-            tm[DataKeys.OBS][t + 1],
-            rdr[t] if rdr is not None else None,
-            rdr[t + 1] if rdr is not None else None,
-            gamma,
-        )
+            hip.rollout_scatter_leaves(*sampled, out[DataKeys.REWARDS].contiguous(),
+                                       [obs[leaf].contiguous() for leaf in self._tm_obs], *columns,
+                                       [storage[t + 1] for storage in self._tm_obs.values()], *rdr_pair, gamma)
+        else:
+            hip.rollout_scatter(*sampled, out[DataKeys.REWARDS].contiguous(), obs.contiguous(), *columns,
+                                tm[DataKeys.OBS][t + 1], *rdr_pair, gamma)
 
     # ------------------------------------------------------------------ #
     # step()

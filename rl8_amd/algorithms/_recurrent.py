@@ -330,27 +330,10 @@ class RecurrentAlgorithm(Algorithm):
         H, N = hp.horizon, self.local_num_envs
         tm, stm = self._tm, self._tm_states
         rdr = tm.get(DataKeys.REVERSED_DISCOUNTED_RETURNS)
-        # the observation slabs: one for a tensor spec, one per leaf for a composite one
-        obs_slabs = self._tm_obs if self._tm_obs is not None else {None: tm[DataKeys.OBS]}
         self._flat_full = None  # (a sequence-major copy of the buffer this collect() overwrites)
         self._release_step_caches()
         with profile_ms() as collect_timer:
-            env_was_reset = False
-            carry = (self.state.horizons and hp.horizons_per_env_reset < 0) or (
-                self.state.horizons % hp.horizons_per_env_reset
-            )
-            if carry:
-                for storage in obs_slabs.values():
-                    storage[0].copy_(storage[H])
-                if rdr is not None:
-                    rdr[0].copy_(rdr[H])
-            else:
-                first = self.env.reset(config=env_config)
-                for leaf, storage in obs_slabs.items():
-                    storage[0].copy_(first if leaf is None else first[leaf])
-                env_was_reset = True
-                if rdr is not None:
-                    rdr[0].zero_()
+            env_was_reset = self._reset_or_carry(env_config)
             for v in stm.values():  # :380-382
                 v[0].copy_(v[H])
 
@@ -390,25 +373,7 @@ class RecurrentAlgorithm(Algorithm):
                         in_batch, self._state_slabs(t), deterministic=deterministic, inplace=False,
                         requires_grad=False, return_actions=True, return_logp=True, return_values=True,
                     )
-                    out = self.env.step(sample[DataKeys.ACTIONS])
-                    if self._tm_obs is not None:
-                        obs = out[DataKeys.OBS]
-                        hip.rollout_scatter_leaves(
-                            sample[DataKeys.ACTIONS].contiguous(), sample[DataKeys.LOGP].contiguous(),
-                            sample[DataKeys.VALUES].contiguous(), out[DataKeys.REWARDS].contiguous(),
-                            [obs[leaf].contiguous() for leaf in self._tm_obs], tm[DataKeys.ACTIONS][t],
-                            tm[DataKeys.LOGP][t], tm[DataKeys.VALUES][t], tm[DataKeys.REWARDS][t],
-                            [storage[t + 1] for storage in self._tm_obs.values()],
-                            rdr[t] if rdr is not None else None, rdr[t + 1] if rdr is not None else None, gamma,
-                        )
-                    else:
-                        hip.rollout_scatter(
-                            sample[DataKeys.ACTIONS].contiguous(), sample[DataKeys.LOGP].contiguous(),
-                            sample[DataKeys.VALUES].contiguous(), out[DataKeys.REWARDS].contiguous(),
-                            out[DataKeys.OBS].contiguous(), tm[DataKeys.ACTIONS][t], tm[DataKeys.LOGP][t],
-                            tm[DataKeys.VALUES][t], tm[DataKeys.REWARDS][t], tm[DataKeys.OBS][t + 1],
-                            rdr[t] if rdr is not None else None, rdr[t + 1] if rdr is not None else None, gamma,
-                        )
+                    self._scatter_step(sample, self.env.step(sample[DataKeys.ACTIONS]), t, gamma)
                 for k, v in stm.items():  # :428
                     v[t + 1].copy_(new_states[k])
                 if not ((t + 1) % hp.seq_len):
@@ -442,15 +407,7 @@ class RecurrentAlgorithm(Algorithm):
                 )
             else:
                 reward_scale = 1.0
-            self.state.horizons += 1
-            self.state.buffered = True
-            self.state.reward_scale = reward_scale if hp.normalize_rewards else 1.0
-            self.injected_noise = None
-
-        collect_stats["env/resets"] = hp.num_envs * int(env_was_reset)
-        collect_stats["env/steps"] = hp.num_envs * hp.horizon
-        collect_stats["profiling/collect_ms"] = collect_timer()
-        return collect_stats
+        return self._finish_collect(collect_stats, reward_scale, env_was_reset, collect_timer())
 
     # -- step ---------------------------------------------------------------------
     def _release_step_caches(self) -> None:

@@ -12,6 +12,7 @@
 // value 4, reward 4, the leaves 3 + 8 + 4 + 4, state 24, rdr 4 = 123 B, beside one sinf and up to five fp64 logs.
 #include "common.hip.h"
 #include "device_math.hip.h"
+#include "rollout_step.hip.h"
 
 namespace rl8 {
 
@@ -63,36 +64,23 @@ __global__ __launch_bounds__(kBlock) void rollout_step_algotrading_kernel(
     int64_t *__restrict__ invested_next, float *__restrict__ log_change_next,
     float *__restrict__ log_change_position_next, const float *__restrict__ rdr_t, float *__restrict__ rdr_t1,
     float gamma, int64_t n, uint64_t seed, uint64_t step, int64_t env_offset, int deterministic) {
+  const StepColumns cols = {logp_col, value_col, reward_col, rdr_t, rdr_t1, gamma};
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    const float x[3] = {logits[3 * i], logits[3 * i + 1], logits[3 * i + 2]};
-    // (the Exp(1) draws are always handed over in registers -- the injected ones, or the ones categorical_draw would
-    // take from the Philox stream itself: a pointer that may be null would put q in the private segment)
-    float q[3] = {1.0f, 1.0f, 1.0f};
-    if (!deterministic) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        q[j] = noise ? noise[3 * i + j] : rl8_exponential(seed, (uint64_t)(i + env_offset), step, (uint32_t)j);
-    }
     float lp;
-    const int act = categorical_draw<3>(x, q, seed, (uint64_t)(i + env_offset), step, 0u, deterministic != 0, &lp);
+    const int act = draw_categorical<3>(logits, noise, i, seed, (uint64_t)(i + env_offset), step, deterministic != 0, &lp);
     AlgoTradingState s = algotrading_load(state, n, i);
     const float r = algotrading_advance(s, act);
     algotrading_store(state, n, i, s);
     algotrading_write_obs(s, i, mask_next, invested_next, log_change_next, log_change_position_next);
     action_col[i] = act;
-    reward_col[i] = r;
-    logp_col[i] = lp;
-    value_col[i] = value[i];
-    if (rdr_t1) rdr_t1[i] = gamma * rdr_t[i] + r;
+    cols.record(i, lp, value[i], r);
   }
 }
 
 }  // namespace rl8
 
 using namespace rl8;
-
-static bool aligned_to(const void *p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 
 RL8_API int rl8_algotrading_reset_f32(float *state, int64_t n, float f_bounds, float k_cyclic_bounds,
                                       float k_market_bounds, uint64_t seed, uint64_t reset_count, int64_t env_offset,
@@ -132,17 +120,11 @@ RL8_API int rl8_rollout_step_algotrading_f32(const float *logits, const float *v
                                              float *log_change_position_next, const float *rdr_t, float *rdr_t1,
                                              float gamma, int64_t n, uint64_t seed, uint64_t step, int64_t env_offset,
                                              int deterministic, void *stream) {
-  if (!logits || !value || !state || !action_col || !logp_col || !value_col || !reward_col || !mask_next ||
-      !invested_next || !log_change_next || !log_change_position_next)
-    return RL8_ENULL;
-  if ((rdr_t == nullptr) != (rdr_t1 == nullptr)) return RL8_ENULL;
-  if (n <= 0) return RL8_ESIZE;
-  if (!aligned_to(action_col, 8) || !aligned_to(invested_next, 8)) return RL8_EALIGN;
-  for (const void *p : {(const void *)logits, (const void *)value, (const void *)noise, (const void *)state,
-                        (const void *)logp_col, (const void *)value_col, (const void *)reward_col,
-                        (const void *)log_change_next, (const void *)log_change_position_next, (const void *)rdr_t,
-                        (const void *)rdr_t1})
-    if (!aligned_to(p, 4)) return RL8_EALIGN;
+  if (const int bad = check_rollout_step_args(
+          {{logits, 4}, {value, 4}, {noise, 4, false}, {state, 4}, {action_col, 8}, {logp_col, 4}, {value_col, 4},
+           {reward_col, 4}, {mask_next, 1}, {invested_next, 8}, {log_change_next, 4}, {log_change_position_next, 4}},
+          rdr_t, rdr_t1, n))
+    return bad;
   rollout_step_algotrading_kernel<<<grid_for(n, kBlock), kBlock, 0, (hipStream_t)stream>>>(
       logits, value, noise, state, action_col, logp_col, value_col, reward_col, mask_next, invested_next,
       log_change_next, log_change_position_next, rdr_t, rdr_t1, gamma, n, seed, step, env_offset, deterministic);

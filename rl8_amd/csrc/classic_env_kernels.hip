@@ -12,6 +12,7 @@
 // per launch at N = 2^20.
 #include "common.hip.h"
 #include "device_math.hip.h"
+#include "rollout_step.hip.h"
 
 namespace rl8 {
 
@@ -57,26 +58,18 @@ __global__ __launch_bounds__(kBlock) void rollout_step_mountain_car_kernel(
     float *__restrict__ reward_col, float *__restrict__ obs_col_next,
     const float *__restrict__ rdr_t, float *__restrict__ rdr_t1, float gamma, int64_t n,
     uint64_t seed, uint64_t step, int64_t env_offset, int deterministic) {
+  const StepColumns cols = {logp_col, value_col, reward_col, rdr_t, rdr_t1, gamma};
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    const float x[3] = {logits[3 * i], logits[3 * i + 1], logits[3 * i + 2]};
-    float q[3];
-    if (noise) {
-      q[0] = noise[3 * i]; q[1] = noise[3 * i + 1]; q[2] = noise[3 * i + 2];
-    }
     float lp;
-    const int act = categorical_draw<3>(x, noise ? q : nullptr, seed, (uint64_t)(i + env_offset),
-                                        step, 0u, deterministic != 0, &lp);
+    const int act = draw_categorical<3>(logits, noise, i, seed, (uint64_t)(i + env_offset), step, deterministic != 0, &lp);
     float p = state[i], v = state[n + i];
     const float r = mountain_car_advance(p, v, act, cfg);
     state[i] = p;
     state[n + i] = v;
     *reinterpret_cast<float2 *>(obs_col_next + 2 * i) = make_float2(p, v);
     action_col[i] = act;
-    reward_col[i] = r;
-    logp_col[i] = lp;
-    value_col[i] = value[i];
-    if (rdr_t1) rdr_t1[i] = gamma * rdr_t[i] + r;
+    cols.record(i, lp, value[i], r);
   }
 }
 
@@ -122,13 +115,12 @@ __global__ __launch_bounds__(kBlock) void rollout_step_pendulum_kernel(
     float *__restrict__ value_col, float *__restrict__ reward_col,
     float *__restrict__ obs_col_next, const float *__restrict__ rdr_t, float *__restrict__ rdr_t1,
     float gamma, int64_t n, uint64_t seed, uint64_t step, int64_t env_offset, int deterministic) {
+  const StepColumns cols = {logp_col, value_col, reward_col, rdr_t, rdr_t1, gamma};
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    float e = 0.0f;
-    if (!deterministic) e = noise ? noise[i] : rl8_normal(seed, (uint64_t)(i + env_offset), step, 0u);
-    float l, c;
-    const float act = normal_draw(mean[i], log_std[i], e, squashed != 0, deterministic != 0, &l, &c);
-    const float lp = squashed ? l - c : l;
+    float lp;
+    const float act = draw_normal(mean, log_std, noise, i, seed, (uint64_t)(i + env_offset), step, squashed != 0,
+                                  deterministic != 0, &lp);
     float th = state[i], td = state[n + i];
     const float r = pendulum_advance(th, td, act, cfg);
     state[i] = th;
@@ -136,10 +128,7 @@ __global__ __launch_bounds__(kBlock) void rollout_step_pendulum_kernel(
     float *ob = obs_col_next + 3 * i;
     ob[0] = cosf(th); ob[1] = sinf(th); ob[2] = td;
     action_col[i] = act;
-    reward_col[i] = r;
-    logp_col[i] = lp;
-    value_col[i] = value[i];
-    if (rdr_t1) rdr_t1[i] = gamma * rdr_t[i] + r;
+    cols.record(i, lp, value[i], r);
   }
 }
 
@@ -173,12 +162,11 @@ RL8_API int rl8_rollout_step_mountain_car_f32(
     const rl8_mountain_car_cfg *cfg, int64_t *action_col, float *logp_col, float *value_col,
     float *reward_col, float *obs_col_next, const float *rdr_t, float *rdr_t1, float gamma,
     int64_t n, uint64_t seed, uint64_t step, int64_t env_offset, int deterministic, void *stream) {
-  if (!logits || !value || !state || !cfg || !action_col || !logp_col || !value_col ||
-      !reward_col || !obs_col_next)
-    return RL8_ENULL;
-  if ((rdr_t == nullptr) != (rdr_t1 == nullptr)) return RL8_ENULL;
-  if (n <= 0) return RL8_ESIZE;
-  if (reinterpret_cast<uintptr_t>(obs_col_next) & 7u) return RL8_EALIGN;
+  if (const int bad = check_rollout_step_args(
+          {{logits, 4}, {value, 4}, {noise, 4, false}, {state, 4}, {cfg, 4}, {action_col, 8}, {logp_col, 4},
+           {value_col, 4}, {reward_col, 4}, {obs_col_next, 8}},  // (obs[t+1] rows are stored as one float2)
+          rdr_t, rdr_t1, n))
+    return bad;
   rollout_step_mountain_car_kernel<<<grid_for(n, kBlock), kBlock, 0, (hipStream_t)stream>>>(
       logits, value, noise, state, *cfg, action_col, logp_col, value_col, reward_col, obs_col_next,
       rdr_t, rdr_t1, gamma, n, seed, step, env_offset, deterministic);
@@ -212,11 +200,11 @@ RL8_API int rl8_rollout_step_pendulum_f32(int squashed, const float *mean, const
                                           float *obs_col_next, const float *rdr_t, float *rdr_t1,
                                           float gamma, int64_t n, uint64_t seed, uint64_t step,
                                           int64_t env_offset, int deterministic, void *stream) {
-  if (!mean || !log_std || !value || !state || !cfg || !action_col || !logp_col || !value_col ||
-      !reward_col || !obs_col_next)
-    return RL8_ENULL;
-  if ((rdr_t == nullptr) != (rdr_t1 == nullptr)) return RL8_ENULL;
-  if (n <= 0) return RL8_ESIZE;
+  if (const int bad = check_rollout_step_args(
+          {{mean, 4}, {log_std, 4}, {value, 4}, {noise, 4, false}, {state, 4}, {cfg, 4}, {action_col, 4}, {logp_col, 4},
+           {value_col, 4}, {reward_col, 4}, {obs_col_next, 4}},
+          rdr_t, rdr_t1, n))
+    return bad;
   rollout_step_pendulum_kernel<<<grid_for(n, kBlock), kBlock, 0, (hipStream_t)stream>>>(
       squashed, mean, log_std, value, noise, state, *cfg, action_col, logp_col, value_col,
       reward_col, obs_col_next, rdr_t, rdr_t1, gamma, n, seed, step, env_offset, deterministic);

@@ -16,6 +16,7 @@
 #include "common.hip.h"
 #include "device_math.hip.h"
 #include "lstm_narrow_heads.hip.h"
+#include "rollout_step.hip.h"
 
 namespace rl8 {
 
@@ -159,13 +160,8 @@ __global__ __launch_bounds__(kBlock) void rollout_scatter_kernel(
     float *__restrict__ rdr_t1, float gamma, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  for (int64_t i = tid; i < n; i += stride) {
-    const float r = reward[i];
-    logp_col[i] = logp[i];
-    value_col[i] = value[i];
-    reward_col[i] = r;
-    if (rdr_t1) rdr_t1[i] = gamma * rdr_t[i] + r;
-  }
+  const StepColumns cols = {logp_col, value_col, reward_col, rdr_t, rdr_t1, gamma};
+  for (int64_t i = tid; i < n; i += stride) cols.record(i, logp[i], value[i], reward[i]);
   // Rows wider than 4 B are copied as dwords, still lane-contiguous.
   const int64_t a_words = n * action_row_bytes / 4;
   const uint32_t *asrc = reinterpret_cast<const uint32_t *>(action);
@@ -203,13 +199,8 @@ __global__ __launch_bounds__(kBlock) void rollout_scatter_leaves_kernel(
     int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  for (int64_t i = tid; i < n; i += stride) {
-    const float r = reward[i];
-    logp_col[i] = logp[i];
-    value_col[i] = value[i];
-    reward_col[i] = r;
-    if (rdr_t1) rdr_t1[i] = gamma * rdr_t[i] + r;
-  }
+  const StepColumns cols = {logp_col, value_col, reward_col, rdr_t, rdr_t1, gamma};
+  for (int64_t i = tid; i < n; i += stride) cols.record(i, logp[i], value[i], reward[i]);
   copy_units<uint32_t>(action, action_col, n * action_row_bytes / 4, tid, stride);
   for (int f = 0; f < leaves.count; ++f) {
     const char *src = leaves.src[f];
@@ -236,39 +227,24 @@ __global__ __launch_bounds__(kBlock) void rollout_step_dummy_kernel(
     float *__restrict__ reward_col, float *__restrict__ obs_col_next,
     const float *__restrict__ rdr_t, float *__restrict__ rdr_t1, float gamma, int64_t n,
     uint64_t seed, uint64_t step, int64_t env_offset, int deterministic) {
+  const StepColumns cols = {logp_col, value_col, reward_col, rdr_t, rdr_t1, gamma};
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    float s = state[i], lp;
+    const uint64_t row = (uint64_t)(i + env_offset);
     if (DISCRETE) {
-      const float2 xl = *reinterpret_cast<const float2 *>(features + 2 * i);
-      const float x[2] = {xl.x, xl.y};
-      float q[2];
-      if (noise) {
-        const float2 qn = *reinterpret_cast<const float2 *>(noise + 2 * i);
-        q[0] = qn.x; q[1] = qn.y;
-      }
-      const int act = categorical_draw<2>(x, noise ? q : nullptr, seed, (uint64_t)(i + env_offset),
-                                          step, 0u, deterministic != 0, &lp);
-      static_cast<int64_t *>(action_col)[i] = act;
-      s = dummy_step_discrete(s, act);
+      float x[2];
+      load_row<2>(features, i, x);
+      dummy_discrete_timestep(x, value[i], noise, state, static_cast<int64_t *>(action_col), obs_col_next, cols, i,
+                              seed, row, step, deterministic != 0);
     } else {
-      float e = 0.0f;
-      if (!deterministic)
-        e = noise ? noise[i] : rl8_normal(seed, (uint64_t)(i + env_offset), step, 0u);
-      float l, c;
-      const float act = normal_draw(features[i], features2[i], e, squashed != 0,
-                                    deterministic != 0, &l, &c);
-      lp = squashed ? l - c : l;
+      float lp;
+      const float act = draw_normal(features, features2, noise, i, seed, row, step, squashed != 0, deterministic != 0, &lp);
       static_cast<float *>(action_col)[i] = act;
-      s = dummy_step_continuous(s, act);
+      const float s = dummy_step_continuous(state[i], act);
+      state[i] = s;
+      obs_col_next[i] = s;
+      cols.record(i, lp, value[i], -fabsf(s));
     }
-    const float r = -fabsf(s);
-    state[i] = s;
-    obs_col_next[i] = s;
-    reward_col[i] = r;
-    logp_col[i] = lp;
-    value_col[i] = value[i];
-    if (rdr_t1) rdr_t1[i] = gamma * rdr_t[i] + r;
   }
 }
 
@@ -290,6 +266,7 @@ __global__ __launch_bounds__(kBlock) void rollout_step_dummy_heads_kernel(
   for (int i = threadIdx.x; i < kOut * kIn / 4; i += kBlock)
     ws[i] = i < 2 * (kIn / 4) ? reinterpret_cast<const float4 *>(w_pol)[i] : reinterpret_cast<const float4 *>(w_vf)[i - 2 * (kIn / 4)];
   __syncthreads();
+  const StepColumns cols = {logp_col, value_col, reward_col, rdr_t, rdr_t1, gamma};
   const int q4 = threadIdx.x & 3;
   const int64_t stride = (int64_t)gridDim.x * (kBlock / 4);
   for (int64_t i = (int64_t)blockIdx.x * (kBlock / 4) + (threadIdx.x >> 2); i < n; i += stride) {
@@ -314,22 +291,8 @@ __global__ __launch_bounds__(kBlock) void rollout_step_dummy_heads_kernel(
     }
     if (q4 != 0) continue;
     const float x[2] = {o[0] + b_pol[0], o[1] + b_pol[1]};
-    float q[2], lp;
-    if (noise) {
-      const float2 qn = *reinterpret_cast<const float2 *>(noise + 2 * i);
-      q[0] = qn.x; q[1] = qn.y;
-    }
-    const int act = categorical_draw<2>(x, noise ? q : nullptr, seed, (uint64_t)(i + env_offset), step, 0u,
-                                        deterministic != 0, &lp);
-    action_col[i] = act;
-    const float s = dummy_step_discrete(state[i], act);
-    const float r = -fabsf(s);
-    state[i] = s;
-    obs_col_next[i] = s;
-    reward_col[i] = r;
-    logp_col[i] = lp;
-    value_col[i] = o[2] + b_vf[0];
-    if (rdr_t1) rdr_t1[i] = gamma * rdr_t[i] + r;
+    dummy_discrete_timestep(x, o[2] + b_vf[0], noise, state, action_col, obs_col_next, cols, i, seed,
+                            (uint64_t)(i + env_offset), step, deterministic != 0);
   }
 }
 
@@ -347,6 +310,7 @@ __global__ __launch_bounds__(kBlock) void rollout_step_dummy_heads_narrow_kernel
   __shared__ float4 ws[kOut * H / 4];
   narrow_heads::stage_weights<H>(ws, kOut, w_pol, 2, w_vf);
   __syncthreads();
+  const StepColumns cols = {logp_col, value_col, reward_col, rdr_t, rdr_t1, gamma};
   const int q4 = threadIdx.x & 3;
   const int64_t stride = (int64_t)gridDim.x * (kBlock / 4);
   for (int64_t i = (int64_t)blockIdx.x * (kBlock / 4) + (threadIdx.x >> 2); i < n; i += stride) {
@@ -354,22 +318,8 @@ __global__ __launch_bounds__(kBlock) void rollout_step_dummy_heads_narrow_kernel
     narrow_heads::row_dots<H, kOut>(h + i * (H / 4), ws, q4, o);
     if (q4 != 0) continue;
     const float x[2] = {o[0] + b_pol[0], o[1] + b_pol[1]};
-    float q[2], lp;
-    if (noise) {
-      const float2 qn = *reinterpret_cast<const float2 *>(noise + 2 * i);
-      q[0] = qn.x; q[1] = qn.y;
-    }
-    const int act = categorical_draw<2>(x, noise ? q : nullptr, seed, (uint64_t)(i + env_offset), step, 0u,
-                                        deterministic != 0, &lp);
-    action_col[i] = act;
-    const float s = dummy_step_discrete(state[i], act);
-    const float r = -fabsf(s);
-    state[i] = s;
-    obs_col_next[i] = s;
-    reward_col[i] = r;
-    logp_col[i] = lp;
-    value_col[i] = o[2] + b_vf[0];
-    if (rdr_t1) rdr_t1[i] = gamma * rdr_t[i] + r;
+    dummy_discrete_timestep(x, o[2] + b_vf[0], noise, state, action_col, obs_col_next, cols, i, seed,
+                            (uint64_t)(i + env_offset), step, deterministic != 0);
   }
 }
 
@@ -382,26 +332,18 @@ __global__ __launch_bounds__(kBlock) void rollout_step_cartpole_kernel(
     float *__restrict__ reward_col, float *__restrict__ obs_col_next,
     const float *__restrict__ rdr_t, float *__restrict__ rdr_t1, float gamma, int64_t n,
     uint64_t seed, uint64_t step, int64_t env_offset, int deterministic) {
+  const StepColumns cols = {logp_col, value_col, reward_col, rdr_t, rdr_t1, gamma};
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    const float x[3] = {logits[3 * i], logits[3 * i + 1], logits[3 * i + 2]};
-    float q[3];
-    if (noise) {
-      q[0] = noise[3 * i]; q[1] = noise[3 * i + 1]; q[2] = noise[3 * i + 2];
-    }
     float lp;
-    const int act = categorical_draw<3>(x, noise ? q : nullptr, seed, (uint64_t)(i + env_offset),
-                                        step, 0u, deterministic != 0, &lp);
+    const int act = draw_categorical<3>(logits, noise, i, seed, (uint64_t)(i + env_offset), step, deterministic != 0, &lp);
     CartPoleState s = {state[i], state[n + i], state[2 * n + i], state[3 * n + i]};
     const CartPoleOut o = cartpole_advance(s, act, cfg);
     state[i] = s.x; state[n + i] = s.x_dot; state[2 * n + i] = s.theta; state[3 * n + i] = s.theta_dot;
     float *ob = obs_col_next + 5 * i;
     ob[0] = s.x; ob[1] = s.x_dot; ob[2] = o.cos_theta; ob[3] = o.sin_theta; ob[4] = s.theta_dot;
     action_col[i] = act;
-    reward_col[i] = o.reward;
-    logp_col[i] = lp;
-    value_col[i] = value[i];
-    if (rdr_t1) rdr_t1[i] = gamma * rdr_t[i] + o.reward;
+    cols.record(i, lp, value[i], o.reward);
   }
 }
 
@@ -534,15 +476,12 @@ RL8_API int rl8_rollout_step_dummy_f32(int is_discrete, int squashed, const floa
                                        float *obs_col_next, const float *rdr_t, float *rdr_t1,
                                        float gamma, int64_t n, uint64_t seed, uint64_t step,
                                        int64_t env_offset, int deterministic, void *stream) {
-  if (!features || !value || !state || !action_col || !logp_col || !value_col || !reward_col ||
-      !obs_col_next)
-    return RL8_ENULL;
-  if (!is_discrete && !features2) return RL8_ENULL;
-  if ((rdr_t == nullptr) != (rdr_t1 == nullptr)) return RL8_ENULL;
-  if (n <= 0) return RL8_ESIZE;
-  if (is_discrete && ((reinterpret_cast<uintptr_t>(features) & 7u) ||
-                      (noise && (reinterpret_cast<uintptr_t>(noise) & 7u))))
-    return RL8_EALIGN;
+  const unsigned pair = is_discrete ? 8 : 4;  // the two-way kernel loads its logits and draws as float2
+  if (const int bad = check_rollout_step_args(
+          {{features, pair}, {features2, 4, !is_discrete}, {value, 4}, {noise, pair, false}, {state, 4},
+           {action_col, pair}, {logp_col, 4}, {value_col, 4}, {reward_col, 4}, {obs_col_next, 4}},
+          rdr_t, rdr_t1, n))
+    return bad;
   hipStream_t s = (hipStream_t)stream;
   static const int cap = env_int("RL8_STEP_GRID_CAP");
   const int grid = grid_for(n, kBlock, cap > 0 ? cap : kMaxGrid);
@@ -562,13 +501,11 @@ RL8_API int rl8_rollout_step_dummy_heads_f32(const float *h, const float *w_pol,
                                              float *logp_col, float *value_col, float *reward_col, float *obs_col_next,
                                              const float *rdr_t, float *rdr_t1, float gamma, int64_t n, uint64_t seed,
                                              uint64_t step, int64_t env_offset, int deterministic, void *stream) {
-  if (!h || !w_pol || !b_pol || !w_vf || !b_vf || !state || !action_col || !logp_col || !value_col || !reward_col ||
-      !obs_col_next)
-    return RL8_ENULL;
-  if ((rdr_t == nullptr) != (rdr_t1 == nullptr)) return RL8_ENULL;
-  if (n <= 0) return RL8_ESIZE;
-  if (!aligned16(h) || !aligned16(w_pol) || !aligned16(w_vf) || (noise && (reinterpret_cast<uintptr_t>(noise) & 7u)))
-    return RL8_EALIGN;
+  if (const int bad = check_rollout_step_args(
+          {{h, 16}, {w_pol, 16}, {b_pol, 4}, {w_vf, 16}, {b_vf, 4}, {noise, 8, false}, {state, 4}, {action_col, 8},
+           {logp_col, 4}, {value_col, 4}, {reward_col, 4}, {obs_col_next, 4}},
+          rdr_t, rdr_t1, n))
+    return bad;
   rollout_step_dummy_heads_kernel<<<grid_for(n, kBlock / 4), kBlock, 0, (hipStream_t)stream>>>(
       reinterpret_cast<const float4 *>(h), w_pol, b_pol, w_vf, b_vf, noise, state, action_col, logp_col, value_col,
       reward_col, obs_col_next, rdr_t, rdr_t1, gamma, n, seed, step, env_offset, deterministic);
@@ -582,13 +519,11 @@ RL8_API int rl8_rollout_step_dummy_heads_narrow_f32(const float *h, int hidden, 
                                                     const float *rdr_t, float *rdr_t1, float gamma, int64_t n,
                                                     uint64_t seed, uint64_t step, int64_t env_offset, int deterministic,
                                                     void *stream) {
-  if (!h || !w_pol || !b_pol || !w_vf || !b_vf || !state || !action_col || !logp_col || !value_col || !reward_col ||
-      !obs_col_next)
-    return RL8_ENULL;
-  if ((rdr_t == nullptr) != (rdr_t1 == nullptr)) return RL8_ENULL;
-  if (n <= 0 || (hidden != 64 && hidden != 128)) return RL8_ESIZE;
-  if (!aligned16(h) || !aligned16(w_pol) || !aligned16(w_vf) || (noise && (reinterpret_cast<uintptr_t>(noise) & 7u)))
-    return RL8_EALIGN;
+  if (const int bad = check_rollout_step_args(
+          {{h, 16}, {w_pol, 16}, {b_pol, 4}, {w_vf, 16}, {b_vf, 4}, {noise, 8, false}, {state, 4}, {action_col, 8},
+           {logp_col, 4}, {value_col, 4}, {reward_col, 4}, {obs_col_next, 4}},
+          rdr_t, rdr_t1, n, hidden == 64 || hidden == 128))
+    return bad;
   const int grid = grid_for(n, kBlock / 4);
   hipStream_t s = (hipStream_t)stream;
   const float4 *h4 = reinterpret_cast<const float4 *>(h);
@@ -610,11 +545,11 @@ RL8_API int rl8_rollout_step_cartpole_f32(const float *logits, const float *valu
                                           float *obs_col_next, const float *rdr_t, float *rdr_t1,
                                           float gamma, int64_t n, uint64_t seed, uint64_t step,
                                           int64_t env_offset, int deterministic, void *stream) {
-  if (!logits || !value || !state || !cfg || !action_col || !logp_col || !value_col ||
-      !reward_col || !obs_col_next)
-    return RL8_ENULL;
-  if ((rdr_t == nullptr) != (rdr_t1 == nullptr)) return RL8_ENULL;
-  if (n <= 0) return RL8_ESIZE;
+  if (const int bad = check_rollout_step_args(
+          {{logits, 4}, {value, 4}, {noise, 4, false}, {state, 4}, {cfg, 4}, {action_col, 8}, {logp_col, 4},
+           {value_col, 4}, {reward_col, 4}, {obs_col_next, 4}},
+          rdr_t, rdr_t1, n))
+    return bad;
   rollout_step_cartpole_kernel<<<grid_for(n, kBlock), kBlock, 0, (hipStream_t)stream>>>(
       logits, value, noise, state, *cfg, action_col, logp_col, value_col, reward_col, obs_col_next,
       rdr_t, rdr_t1, gamma, n, seed, step, env_offset, deterministic);

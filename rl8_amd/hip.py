@@ -12,6 +12,7 @@ on a HIP device, the call raises.
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Any, NamedTuple, Sequence
@@ -367,6 +368,9 @@ class _timed:
             timer.records.setdefault(self.name, []).append((self.start, end, self.units))
 
 
+_UNTIMED = contextlib.nullcontext()
+
+
 def _ptr(t: None | torch.Tensor) -> None | int:
     if t is None:
         return None
@@ -630,30 +634,78 @@ def normal_sample_logp(
 
 
 # --------------------------------------------------------------------------- #
-# Rollout bookkeeping.
+# Rollout bookkeeping: one timestep's column writes, alone (``rollout_scatter*``, for a generic Env) or fused with
+# the action draw and ``env.step`` (``rollout_step_*``).  One validator and one launcher serve them all.
 # --------------------------------------------------------------------------- #
+_F32 = torch.float32
+
+
+def _check_step_tensors(name: str, specs: Any) -> None:
+    """``specs``: (what, tensor or None, dtype, elements) -- each tensor present must be dense, of that dtype and
+    size.  Nothing here touches the library or a pointer, so a bad call fails before either."""
+    for what, t, dtype, count in specs:
+        if t is None:
+            continue
+        if t.dtype != dtype:
+            raise TypeError(f"{name}: {what} must be {dtype}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous")
+        if t.numel() != count:
+            raise ValueError(f"{name}: {what} must hold {count} elements, got {t.numel()}")
+
+
+def _step_columns(n: int, action_dtype: torch.dtype, action_col: torch.Tensor, logp_col: torch.Tensor,
+                  value_col: torch.Tensor, reward_col: torch.Tensor) -> list:
+    return [("action_col", action_col, action_dtype, n), ("logp_col", logp_col, _F32, n),
+            ("value_col", value_col, _F32, n), ("reward_col", reward_col, _F32, n)]
+
+
+def _rdr_pair(n: int, rdr_t: None | torch.Tensor, rdr_t1: None | torch.Tensor) -> list:
+    return [("rdr_t", rdr_t, _F32, n), ("rdr_t1", rdr_t1, _F32, n)]
+
+
+def _rollout_step(entry: str, n: int, head: Sequence, action_dtype: torch.dtype, obs: Sequence, columns: tuple,
+                  tail: tuple, timed: None | str = None) -> None:
+    """Check and launch one fused timestep.  ``head`` is the entry's leading arguments in ABI order and ``obs`` its
+    ``obs[t+1]`` column(s): a (what, tensor or None, dtype, elements) tuple is checked and passed as its pointer, any
+    other value is passed as it is.  ``columns``: (action_col, logp_col, value_col, reward_col, rdr_t, rdr_t1), one
+    element per env each; ``tail``: (gamma, seed, step, env_offset, deterministic).  Every entry takes them in this order."""
+    gamma, seed, step, env_offset, deterministic = tail
+    args = (*head, *_step_columns(n, action_dtype, *columns[:4]), *obs, *_rdr_pair(n, *columns[4:]))
+    _check_step_tensors(entry, [a for a in args if type(a) is tuple])
+    args = [_ptr(a[1]) if type(a) is tuple else a for a in args]
+    with _timed(timed, n) if timed else _UNTIMED:
+        _check(getattr(load(), entry)(*args, gamma, n, seed, step, env_offset, int(deterministic), _stream()), entry)
+
+
+def _scatter_columns(name: str, n: int, action: torch.Tensor, logp: torch.Tensor, value: torch.Tensor,
+                     reward: torch.Tensor, columns: tuple) -> None:
+    """The checks the two scatter wrappers share: the sampled tensors against the columns they go to."""
+    action_col = columns[0]
+    if action.dtype != action_col.dtype or action.numel() != action_col.numel():
+        raise ValueError(f"{name}: action and action_col must match")
+    _check_step_tensors(name, [("action", action, action.dtype, action.numel()), ("logp", logp, _F32, n),
+                               ("value", value, _F32, n), ("reward", reward, _F32, n),
+                               ("action_col", action_col, action.dtype, action.numel()),
+                               *_step_columns(n, action.dtype, *columns[:4])[1:], *_rdr_pair(n, *columns[4:])])
+
+
 def rollout_scatter(
     action: torch.Tensor, logp: torch.Tensor, value: torch.Tensor, reward: torch.Tensor, obs: torch.Tensor,
     action_col: torch.Tensor, logp_col: torch.Tensor, value_col: torch.Tensor, reward_col: torch.Tensor,
     obs_col_next: torch.Tensor, rdr_t: None | torch.Tensor, rdr_t1: None | torch.Tensor, gamma: float,
 ) -> None:
+    name = "rl8_rollout_scatter_f32"
     n = logp.shape[0]
-    for name, t in (("action", action), ("logp", logp), ("value", value), ("reward", reward), ("obs", obs),
-                    ("action_col", action_col), ("logp_col", logp_col), ("value_col", value_col),
-                    ("reward_col", reward_col), ("obs_col_next", obs_col_next)):
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-    if action.dtype != action_col.dtype or action.numel() != action_col.numel():
-        raise ValueError("action and action_col must match")
-    if obs.numel() != obs_col_next.numel() or obs.dtype != torch.float32:
-        raise ValueError("obs and obs_col_next must match (float32)")
+    _scatter_columns(name, n, action, logp, value, reward, (action_col, logp_col, value_col, reward_col, rdr_t, rdr_t1))
+    _check_step_tensors(name, [("obs", obs, _F32, obs.numel()), ("obs_col_next", obs_col_next, _F32, obs.numel())])
     _check(
         load().rl8_rollout_scatter_f32(
             _ptr(action), action.element_size() * (action.numel() // n), _ptr(logp), _ptr(value), _ptr(reward),
             _ptr(obs), obs.numel() // n, _ptr(action_col), _ptr(logp_col), _ptr(value_col), _ptr(reward_col),
             _ptr(obs_col_next), _ptr(rdr_t), _ptr(rdr_t1), gamma, n, _stream(),
         ),
-        "rl8_rollout_scatter_f32",
+        name,
     )
 
 
@@ -665,26 +717,18 @@ def rollout_scatter_leaves(
 ) -> None:
     """``rollout_scatter`` for dict observations: ``obs[i]`` ``[N, ...]`` (any dtype) goes to ``obs_cols_next[i]`` in
     the same launch as the five other columns."""
+    name = "rl8_rollout_scatter_leaves_f32"
     n = logp.shape[0]
-    for name, t in (("action", action), ("logp", logp), ("value", value), ("reward", reward),
-                    ("action_col", action_col), ("logp_col", logp_col), ("value_col", value_col),
-                    ("reward_col", reward_col), *((f"obs[{i}]", t) for i, t in enumerate(obs)),
-                    *((f"obs_cols_next[{i}]", t) for i, t in enumerate(obs_cols_next))):
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-    if action.dtype != action_col.dtype or action.numel() != action_col.numel():
-        raise ValueError("action and action_col must match")
-    for name, t in (("logp", logp), ("value", value), ("reward", reward), ("logp_col", logp_col),
-                    ("value_col", value_col), ("reward_col", reward_col)):
-        if t.dtype != torch.float32 or t.numel() != n:
-            raise ValueError(f"{name} must hold one float32 per env")
+    _scatter_columns(name, n, action, logp, value, reward, (action_col, logp_col, value_col, reward_col, rdr_t, rdr_t1))
     if not obs or len(obs) != len(obs_cols_next) or len(obs) > MAX_GATHER_FIELDS:
         raise ValueError(f"between 1 and {MAX_GATHER_FIELDS} observation leaves, as many columns")
-    leaves = (ScatterLeaf * len(obs))()
     for i, (src, dst) in enumerate(zip(obs, obs_cols_next)):
         if src.dtype != dst.dtype or src.numel() != dst.numel() or src.shape[0] != n or src.numel() == 0:
             raise ValueError(f"obs[{i}] and obs_cols_next[{i}] must match ([N, ...], one dtype)")
-        leaves[i] = ScatterLeaf(_ptr(src), _ptr(dst), src.element_size() * (src.numel() // n))
+        _check_step_tensors(name, [(f"obs[{i}]", src, src.dtype, src.numel()),
+                                   (f"obs_cols_next[{i}]", dst, src.dtype, src.numel())])
+    leaves = (ScatterLeaf * len(obs))(*(ScatterLeaf(_ptr(src), _ptr(dst), src.element_size() * (src.numel() // n))
+                                        for src, dst in zip(obs, obs_cols_next)))
     with _timed("rollout_scatter_leaves", n):
         _check(
             load().rl8_rollout_scatter_leaves_f32(
@@ -692,7 +736,7 @@ def rollout_scatter_leaves(
                 leaves, len(obs), _ptr(action_col), _ptr(logp_col), _ptr(value_col), _ptr(reward_col), _ptr(rdr_t),
                 _ptr(rdr_t1), gamma, n, _stream(),
             ),
-            "rl8_rollout_scatter_leaves_f32",
+            name,
         )
 
 
@@ -703,31 +747,20 @@ def rollout_step_dummy(
     rdr_t1: None | torch.Tensor, gamma: float, seed: int, step: int, env_offset: int, deterministic: bool,
 ) -> None:
     n = state.numel()
-    tensors = [features, value, state, action_col, logp_col, value_col, reward_col, obs_col_next]
-    tensors += [t for t in (features2, noise, rdr_t, rdr_t1) if t is not None]
-    for t in tensors:
-        if not t.is_contiguous():
-            raise ValueError("rollout_step_dummy: all tensors must be contiguous")
-    want_feat = 2 * n if discrete else n
-    if features.numel() != want_feat or value.numel() != n or action_col.numel() != n:
-        raise ValueError("rollout_step_dummy: shape mismatch")
-    if noise is not None and noise.numel() != want_feat:
-        raise ValueError("rollout_step_dummy: noise shape mismatch")
-    if action_col.dtype != (torch.int64 if discrete else torch.float32):
-        raise TypeError("rollout_step_dummy: action column dtype mismatch")
-    for t in (logp_col, value_col, reward_col, obs_col_next):
-        if t.numel() != n or t.dtype != torch.float32:
-            raise ValueError("rollout_step_dummy: column shape/dtype mismatch")
-    with _timed("rollout_step_dummy", n):
-        _check(
-            load().rl8_rollout_step_dummy_f32(
-                int(discrete), int(squashed), _ptr(features), _ptr(features2), _ptr(value), _ptr(noise),
-                _ptr(state), _ptr(action_col), _ptr(logp_col), _ptr(value_col), _ptr(reward_col),
-                _ptr(obs_col_next), _ptr(rdr_t), _ptr(rdr_t1), gamma, n, seed, step, env_offset,
-                int(deterministic), _stream(),
-            ),
-            "rl8_rollout_step_dummy_f32",
-        )
+    k = 2 if discrete else 1  # two logits per env, or a mean (features) and a log-std (features2)
+    head = (int(discrete), int(squashed), ("features", features, _F32, k * n), ("features2", features2, _F32, n),
+            ("value", value, _F32, n), ("noise", noise, _F32, k * n), ("state", state, _F32, n))
+    _rollout_step("rl8_rollout_step_dummy_f32", n, head, torch.int64 if discrete else _F32,
+                  [("obs_col_next", obs_col_next, _F32, n)],
+                  (action_col, logp_col, value_col, reward_col, rdr_t, rdr_t1),
+                  (gamma, seed, step, env_offset, deterministic), timed="rollout_step_dummy")
+
+
+def _logits_head(n: int, logits: torch.Tensor, value: torch.Tensor, noise: None | torch.Tensor, state: torch.Tensor,
+                 state_rows: int, cfg: Any) -> tuple:
+    """The leading arguments of a three-way categorical env with struct-of-arrays state and a config struct."""
+    return (("logits", logits, _F32, 3 * n), ("value", value, _F32, n), ("noise", noise, _F32, 3 * n),
+            ("state", state, _F32, state_rows * n), C.byref(cfg))
 
 
 def rollout_step_cartpole(
@@ -737,29 +770,10 @@ def rollout_step_cartpole(
     step: int, env_offset: int, deterministic: bool,
 ) -> None:
     n = state.shape[1]
-    tensors = [logits, value, state, action_col, logp_col, value_col, reward_col, obs_col_next]
-    tensors += [t for t in (noise, rdr_t, rdr_t1) if t is not None]
-    for t in tensors:
-        if not t.is_contiguous():
-            raise ValueError("rollout_step_cartpole: all tensors must be contiguous")
-    if logits.numel() != 3 * n or value.numel() != n or obs_col_next.numel() != 5 * n or action_col.numel() != n:
-        raise ValueError("rollout_step_cartpole: shape mismatch")
-    if noise is not None and noise.numel() != 3 * n:
-        raise ValueError("rollout_step_cartpole: noise shape mismatch")
-    _check(
-        load().rl8_rollout_step_cartpole_f32(
-            _ptr(logits), _ptr(value), _ptr(noise), _ptr(state), C.byref(cfg), _ptr(action_col), _ptr(logp_col),
-            _ptr(value_col), _ptr(reward_col), _ptr(obs_col_next), _ptr(rdr_t), _ptr(rdr_t1), gamma, n, seed,
-            step, env_offset, int(deterministic), _stream(),
-        ),
-        "rl8_rollout_step_cartpole_f32",
-    )
-
-
-def _check_step_tensors(name: str, tensors: list[None | torch.Tensor]) -> None:
-    for t in tensors:
-        if t is not None and not t.is_contiguous():
-            raise ValueError(f"{name}: all tensors must be contiguous")
+    _rollout_step("rl8_rollout_step_cartpole_f32", n, _logits_head(n, logits, value, noise, state, 4, cfg), torch.int64,
+                  [("obs_col_next", obs_col_next, _F32, 5 * n)],
+                  (action_col, logp_col, value_col, reward_col, rdr_t, rdr_t1),
+                  (gamma, seed, step, env_offset, deterministic))
 
 
 def rollout_step_mountain_car(
@@ -769,20 +783,10 @@ def rollout_step_mountain_car(
     step: int, env_offset: int, deterministic: bool,
 ) -> None:
     n = state.shape[1]
-    _check_step_tensors("rollout_step_mountain_car", [logits, value, state, action_col, logp_col, value_col,
-                                                      reward_col, obs_col_next, noise, rdr_t, rdr_t1])
-    if logits.numel() != 3 * n or value.numel() != n or obs_col_next.numel() != 2 * n or action_col.numel() != n:
-        raise ValueError("rollout_step_mountain_car: shape mismatch")
-    if noise is not None and noise.numel() != 3 * n:
-        raise ValueError("rollout_step_mountain_car: noise shape mismatch")
-    _check(
-        load().rl8_rollout_step_mountain_car_f32(
-            _ptr(logits), _ptr(value), _ptr(noise), _ptr(state), C.byref(cfg), _ptr(action_col), _ptr(logp_col),
-            _ptr(value_col), _ptr(reward_col), _ptr(obs_col_next), _ptr(rdr_t), _ptr(rdr_t1), gamma, n, seed,
-            step, env_offset, int(deterministic), _stream(),
-        ),
-        "rl8_rollout_step_mountain_car_f32",
-    )
+    _rollout_step("rl8_rollout_step_mountain_car_f32", n, _logits_head(n, logits, value, noise, state, 2, cfg),
+                  torch.int64, [("obs_col_next", obs_col_next, _F32, 2 * n)],
+                  (action_col, logp_col, value_col, reward_col, rdr_t, rdr_t1),
+                  (gamma, seed, step, env_offset, deterministic))
 
 
 def rollout_step_pendulum(
@@ -792,22 +796,11 @@ def rollout_step_pendulum(
     gamma: float, seed: int, step: int, env_offset: int, deterministic: bool,
 ) -> None:
     n = state.shape[1]
-    _check_step_tensors("rollout_step_pendulum", [mean, log_std, value, state, action_col, logp_col, value_col,
-                                                  reward_col, obs_col_next, noise, rdr_t, rdr_t1])
-    if mean.numel() != n or log_std.numel() != n or value.numel() != n or obs_col_next.numel() != 3 * n or action_col.numel() != n:
-        raise ValueError("rollout_step_pendulum: shape mismatch")
-    if action_col.dtype != torch.float32:
-        raise ValueError("rollout_step_pendulum: the action column must be float32")
-    if noise is not None and noise.numel() != n:
-        raise ValueError("rollout_step_pendulum: noise shape mismatch")
-    _check(
-        load().rl8_rollout_step_pendulum_f32(
-            int(squashed), _ptr(mean), _ptr(log_std), _ptr(value), _ptr(noise), _ptr(state), C.byref(cfg),
-            _ptr(action_col), _ptr(logp_col), _ptr(value_col), _ptr(reward_col), _ptr(obs_col_next), _ptr(rdr_t),
-            _ptr(rdr_t1), gamma, n, seed, step, env_offset, int(deterministic), _stream(),
-        ),
-        "rl8_rollout_step_pendulum_f32",
-    )
+    head = (int(squashed), ("mean", mean, _F32, n), ("log_std", log_std, _F32, n), ("value", value, _F32, n),
+            ("noise", noise, _F32, n), ("state", state, _F32, 2 * n), C.byref(cfg))
+    _rollout_step("rl8_rollout_step_pendulum_f32", n, head, _F32, [("obs_col_next", obs_col_next, _F32, 3 * n)],
+                  (action_col, logp_col, value_col, reward_col, rdr_t, rdr_t1),
+                  (gamma, seed, step, env_offset, deterministic))
 
 
 def rollout_step_algotrading(
@@ -817,31 +810,13 @@ def rollout_step_algotrading(
     env_offset: int, deterministic: bool,
 ) -> None:
     """``obs_col_next`` maps the four leaf names to their ``t+1`` columns."""
-    name = "rollout_step_algotrading"
     n = state.shape[1]
-    _check_step_tensors(name, [logits, value, state, action_col, logp_col, value_col, reward_col, noise, rdr_t, rdr_t1])
-    if state.shape[0] != len(ALGOTRADING_STATE_ROWS) or logits.numel() != 3 * n:
-        raise ValueError(f"{name}: state [9,N], logits [N,1,3]")
-    if action_col.dtype != torch.int64 or action_col.numel() != n:
-        raise ValueError(f"{name}: the action column must be [N,1] int64")
-    for t in (logits, value, state, logp_col, value_col, reward_col, noise, rdr_t, rdr_t1):
-        if t is not None and t.dtype != torch.float32:
-            raise TypeError(f"{name}: float32 tensors expected")
-    for t in (value, logp_col, value_col, reward_col, rdr_t, rdr_t1):
-        if t is not None and t.numel() != n:
-            raise ValueError(f"{name}: column shape mismatch")
-    if noise is not None and noise.numel() != 3 * n:
-        raise ValueError(f"{name}: noise shape mismatch")
-    leaves = _algotrading_leaves(name, n, obs_col_next)
-    with _timed(name, n):
-        _check(
-            load().rl8_rollout_step_algotrading_f32(
-                _ptr(logits), _ptr(value), _ptr(noise), _ptr(state), _ptr(action_col), _ptr(logp_col), _ptr(value_col),
-                _ptr(reward_col), *(_ptr(t) for t in leaves), _ptr(rdr_t), _ptr(rdr_t1), gamma, n, seed, step,
-                env_offset, int(deterministic), _stream(),
-            ),
-            "rl8_rollout_step_algotrading_f32",
-        )
+    head = (("logits", logits, _F32, 3 * n), ("value", value, _F32, n), ("noise", noise, _F32, 3 * n),
+            ("state", state, _F32, len(ALGOTRADING_STATE_ROWS) * n))
+    obs = [(f"leaf {key!r}", obs_col_next[key], dtype, d * n) for key, dtype, d in ALGOTRADING_LEAVES]
+    _rollout_step("rl8_rollout_step_algotrading_f32", n, head, torch.int64, obs,
+                  (action_col, logp_col, value_col, reward_col, rdr_t, rdr_t1),
+                  (gamma, seed, step, env_offset, deterministic), timed="rollout_step_algotrading")
 
 
 def buffer_layout(leaf: torch.Tensor) -> tuple[int, int, int]:
@@ -2431,18 +2406,9 @@ def rollout_step_dummy_heads_narrow(
     n, hidden = _heads_narrow_params("rollout_step_dummy_heads_narrow", h, (w_pol, b_pol), (w_vf, b_vf))
     if w_pol.shape[0] != 2 or w_vf.shape[0] != 1:
         raise ValueError("rollout_step_dummy_heads_narrow: w_pol [2, H], w_vf [1, H]")
-    _dense(action_col, torch.int64, "action_col")
-    for name, t in (("state", state), ("logp_col", logp_col), ("value_col", value_col), ("reward_col", reward_col),
-                    ("obs_col_next", obs_col_next), ("noise", noise), ("rdr_t", rdr_t), ("rdr_t1", rdr_t1)):
-        if t is not None:
-            _dense(t, torch.float32, name)
-            if t.numel() != (2 * n if name == "noise" else n):
-                raise ValueError(f"rollout_step_dummy_heads_narrow: {name} has {t.numel()} elements for {n} envs")
-    if action_col.numel() != n:
-        raise ValueError("rollout_step_dummy_heads_narrow: action_col must hold one int64 per env")
-    with _timed("rollout_step_dummy_heads_narrow", n):
-        _check(load().rl8_rollout_step_dummy_heads_narrow_f32(
-            _ptr(h), hidden, _ptr(w_pol), _ptr(b_pol), _ptr(w_vf), _ptr(b_vf), _ptr(noise), _ptr(state), _ptr(action_col),
-            _ptr(logp_col), _ptr(value_col), _ptr(reward_col), _ptr(obs_col_next), _ptr(rdr_t), _ptr(rdr_t1),
-            float(gamma), n, int(seed), int(step), int(env_offset), int(deterministic), _stream()),
-            "rl8_rollout_step_dummy_heads_narrow_f32")
+    head = (("h", h, _F32, n * hidden), hidden, ("w_pol", w_pol, _F32, 2 * hidden), ("b_pol", b_pol, _F32, 2),
+            ("w_vf", w_vf, _F32, hidden), ("b_vf", b_vf, _F32, 1), ("noise", noise, _F32, 2 * n), ("state", state, _F32, n))
+    _rollout_step("rl8_rollout_step_dummy_heads_narrow_f32", n, head, torch.int64, [("obs_col_next", obs_col_next, _F32, n)],
+                  (action_col, logp_col, value_col, reward_col, rdr_t, rdr_t1),
+                  (float(gamma), int(seed), int(step), int(env_offset), deterministic),
+                  timed="rollout_step_dummy_heads_narrow")
