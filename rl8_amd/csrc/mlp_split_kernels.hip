@@ -895,9 +895,11 @@ __global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_gate16_kernel(
   const float k2048 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(0x45000000));
   float gsum = 0.0f;
 
-  const int64_t chunks = (m + kWsChunk - 1) / kWsChunk;
-  const int64_t stride = gridDim.x;
-  const int64_t mine = (chunks - blockIdx.x + stride - 1) / stride;  // >= 1
+  // (a launch covers at most kWgradSegmentRows rows: row numbers and every byte offset below fit 31 bits)
+  const int rows_all = (int)m;
+  const int chunks = (rows_all + kWsChunk - 1) / kWsChunk;
+  const int stride = gridDim.x;
+  const int mine = (chunks - (int)blockIdx.x + stride - 1) / stride;  // >= 1
 
   // what a thread holds of a chunk before it produces it: its column's gate word of its four rows, and (wave-uniform)
   // the rows' observations and dOut
@@ -905,47 +907,46 @@ __global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_gate16_kernel(
     uint32_t g[4];
     f32x8 dv, xv[(4 * kIn + 7) / 8];  // scalar registers: requested by issue(), usable behind land()
   };
-  // (32-bit offsets through buffer descriptors that end at row m: rows past the end read as zero, no branches.  No wait
-  // here: the loads fly under the step's production and products; land() is the wait and the compiler's fence)
+  // ONE buffer descriptor per operand for the whole launch, ending at row m, and a chunk's rows as a 32-bit byte offset
+  // into it: rows past the end read as zero, so the last, ragged step and the all-zero steps behind it are steps like
+  // any other -- no row bound is compared and no pointer rebuilt per step.  The chunks a workgroup asks for are
+  // consecutive ones of its own (numbers 0, 1, 2, ... in issue order), so the first row of the next request is a
+  // running sum.  The gate words' offset rides in the lanes' vector offset, the rows' 32 bytes in the instruction's
+  // immediate: both are what the descriptor's range check looks at.
+  // (No wait here: the loads fly under the step's production and products; land() is the wait and the compiler's fence)
+  const __amdgpu_buffer_rsrc_t g_rsrc = buffer_rsrc(fused.gate2, (uint32_t)rows_all * 32u);
+  const u32x4 x_rsrc = scalar_rsrc(x, rows_all * kIn * 4);
+  const u32x4 d_rsrc = scalar_rsrc(fused.dout, rows_all * (PAIR ? 8 : 4));
+  const int gate_lane = (col >> 5) * 4;
+  const int row_step = stride * kWsChunk;
+  int issue_row = (int)blockIdx.x * kWsChunk + 4 * q;  // first row of this wave's quarter of the next chunk to request
+  [[maybe_unused]] int land_row = issue_row;            // ... and of the next chunk to land (the late scalar loads)
+  auto request_scalars = [&](Raw &r, int row0) {
+    r.dv = scalar_buffer_load_x8_at(d_rsrc, row0 * (PAIR ? 8 : 4));
+    const int xo = row0 * (kIn * 4);
+    r.xv[0] = scalar_buffer_load_x8_at(x_rsrc, xo);
+    if constexpr (4 * kIn > 8) r.xv[1] = scalar_buffer_load_x8_at(x_rsrc, xo + 32);
+    if constexpr (4 * kIn > 16) r.xv[2] = scalar_buffer_load_x8_at(x_rsrc, xo + 64);
+    if constexpr (4 * kIn > 24) r.xv[3] = scalar_buffer_load_x8_at(x_rsrc, xo + 96);
+  };
   // d_in >= 6 (round 6): the scalar loads are made in land(), directly in front of their wait.  Requested a chunk ahead
   // like the narrower widths' -- two sets of up to 40 scalar registers in flight across a whole consume() + produce() --
   // the register allocator ran out and parked destinations of loads still in flight in vector lanes (v_writelane of stale
   // data: tools/check_inflight_regs.py finds it).  One set, alive from its wait to the end of produce(); the wait costs a
   // scalar-cache round trip per chunk, behind which the SIMD's other three waves work.
   constexpr bool kLateScalars = kIn >= 6;
-  auto issue = [&](Raw &r, int64_t n) {
-    const int64_t row0 = (blockIdx.x + n * stride) * kWsChunk + 4 * q;
-    const int64_t left = m - row0;
-    const int rows = left <= 0 ? 0 : left < 4 ? (int)left : 4;
-    const int64_t at = rows > 0 ? row0 : 0;
-    const __amdgpu_buffer_rsrc_t g = buffer_rsrc(fused.gate2 + at * 8, rows * 32);
-    if constexpr (kLateScalars) {
+  auto issue = [&](Raw &r) {  // the next chunk of this workgroup
+    const int row0 = issue_row;
+    issue_row += row_step;
+    const int gv = gate_lane + row0 * 32;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) r.g[e] = __float_as_uint(buffer_load_f32(g, (col >> 5) * 4, e * 32));
-    } else {  // (the narrower widths: text and code as in rounds 4-5)
-      const u32x4 rx = scalar_rsrc(x + at * kIn, rows * kIn * 4);
-      const u32x4 rd = scalar_rsrc(fused.dout + at * (PAIR ? 2 : 1), rows * (PAIR ? 8 : 4));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r.g[e] = __float_as_uint(buffer_load_f32(g, (col >> 5) * 4, e * 32));
-      r.dv = scalar_buffer_load_x8<0>(rd);
-      r.xv[0] = scalar_buffer_load_x8<0>(rx);
-      if constexpr (4 * kIn > 8) r.xv[1] = scalar_buffer_load_x8<32>(rx);
-      if constexpr (4 * kIn > 16) r.xv[2] = scalar_buffer_load_x8<64>(rx);
-    }
+    for (int e = 0; e < 4; ++e) r.g[e] = __float_as_uint(buffer_load_f32(g_rsrc, gv + e * 32, 0));
+    if constexpr (!kLateScalars) request_scalars(r, row0);
   };
-  auto land = [&](Raw &r, [[maybe_unused]] int64_t n) {  // n: the chunk issue(r, n) was called for
+  auto land = [&](Raw &r) {  // the chunk of the oldest issue(r) not yet landed
     if constexpr (kLateScalars) {
-      const int64_t row0 = (blockIdx.x + n * stride) * kWsChunk + 4 * q;
-      const int64_t left = m - row0;
-      const int rows = left <= 0 ? 0 : left < 4 ? (int)left : 4;
-      const int64_t at = rows > 0 ? row0 : 0;
-      const u32x4 rx = scalar_rsrc(x + at * kIn, rows * kIn * 4);
-      const u32x4 rd = scalar_rsrc(fused.dout + at * (PAIR ? 2 : 1), rows * (PAIR ? 8 : 4));
-      r.dv = scalar_buffer_load_x8<0>(rd);
-      r.xv[0] = scalar_buffer_load_x8<0>(rx);
-      r.xv[1] = scalar_buffer_load_x8<32>(rx);
-      r.xv[2] = scalar_buffer_load_x8<64>(rx);
-      if constexpr (4 * kIn > 24) r.xv[3] = scalar_buffer_load_x8<96>(rx);
+      request_scalars(r, land_row);
+      land_row += row_step;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     scalar_tie(r.dv);
@@ -970,8 +971,11 @@ __global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_gate16_kernel(
       const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe((int)r.g[e], (unsigned)(col & 31), 1u);
       const uint32_t m1 = (uint32_t)__builtin_amdgcn_sbfe((int)r.g[e + 1], (unsigned)(col & 31), 1u);
       gw[e >> 1] = (m0 & 0x00003c00u) | (m1 & 0x3c000000u);
-      gsum += __uint_as_float(m0 & __float_as_uint(d_of(r, e)));
-      gsum += __uint_as_float(m1 & __float_as_uint(d_of(r, e + 1)));
+      // gsum += gate * dOut, the gate read as the fp16 1.0 / 0.0 just formed: one instruction per element where a mask
+      // and an add were two, and for finite dOut the same bits (1.0 d + gsum rounds once, as the add did; 0.0 d is a
+      // zero, and gsum, which starts at +0, is never -0)
+      gsum = f16_half_fma<0>(gw[e >> 1], d_of(r, e), gsum);
+      gsum = f16_half_fma<1>(gw[e >> 1], d_of(r, e + 1), gsum);
       f16_pair_product_wide(t[e], t[e + 1], d_of(r, e), d_of(r, e + 1), k2048, hi[e >> 1], lo[e >> 1]);
     }
     *reinterpret_cast<u32x2 *>(base) = u32x2{gw[0], gw[1]};
@@ -1001,6 +1005,10 @@ __global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_gate16_kernel(
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) gl[t][r] = g[t][r] & kF16GateLowMask;
+    // The wave's eight products at raised issue priority: the SIMD's four waves reach this point together (one barrier
+    // per two steps), and whoever holds fragments should feed the matrix pipe before another wave's producer
+    // arithmetic is issued; measured -2.7 % on the one-output call, nothing on the pair (profiles/wgrad_gate_issue.txt).
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -1010,41 +1018,42 @@ __global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_gate16_kernel(
         acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, gl[a]), __builtin_bit_cast(half8, bl[b]),
                                                           acc[a][b], 0, 0, 0);
       }
+    __builtin_amdgcn_s_setprio(0);
   };
 
   // Ring: chunk n lives in stage n % 4.  Step n: load chunk n + 3, produce chunk n + 2 (loaded a step ago), consume chunk n
   // (produced two steps ago), barrier.  Stage (n + 2) % 4 was last read in step n - 2: two barriers back.
   Raw ra, rb;
-  issue(ra, 0);
-  land(ra, 0);
+  issue(ra);  // chunk 0
+  land(ra);
   produce(ra, 0);
-  issue(ra, 1);
-  land(ra, 1);
+  issue(ra);  // chunk 1
+  land(ra);
   produce(ra, 1);
-  issue(ra, 2);
-  land(ra, 2);
+  issue(ra);  // chunk 2
+  land(ra);
   __syncthreads();
-  const int64_t steps = (mine + 3) & ~(int64_t)3;  // (a multiple of four: chunks past the end are all zero)
+  const int steps = (mine + 3) & ~3;  // (a multiple of four: chunks past the end are all zero)
 #pragma unroll 1
-  for (int64_t n = 0; n < steps; n += 4) {
+  for (int n = 0; n < steps; n += 4) {
     // (one barrier per TWO steps: stages 2, 3 are written while 0, 1 are read, and the other way round)
-    issue(rb, n + 3);
+    issue(rb);  // chunk n + 3
     consume(0);
     produce(ra, 2);
-    land(rb, n + 3);
-    issue(ra, n + 4);
+    land(rb);
+    issue(ra);  // chunk n + 4
     consume(1);
     produce(rb, 3);
-    land(ra, n + 4);
+    land(ra);
     __syncthreads();
-    issue(rb, n + 5);
+    issue(rb);  // chunk n + 5
     consume(2);
     produce(ra, 0);
-    land(rb, n + 5);
-    issue(ra, n + 6);
+    land(rb);
+    issue(ra);  // chunk n + 6
     consume(3);
     produce(rb, 1);
-    land(ra, n + 6);
+    land(ra);
     __syncthreads();
   }
 
@@ -1087,6 +1096,7 @@ template <int DIN, bool PAIR>
 static int launch_wgrad_gate16(int grid, hipStream_t s, const float *x, const float *w1, const float *b1, int64_t m,
                                float *slabs, WgradFusedArgs fused) {
   static LdsOptIn opt;
+  if (m > kWgradSegmentRows) return RL8_ESIZE;  // (the kernel's 32-bit byte offsets)
   if (const int e = allow_dynamic_lds(opt, reinterpret_cast<const void *>(&mlp_wgrad_gate16_kernel<DIN, PAIR>), 160 * 1024)) return e;
   mlp_wgrad_gate16_kernel<DIN, PAIR><<<grid, kW16Threads, kW16Stages * kW16StageBytes + kHidden * 4, s>>>(x, w1, b1, m, slabs, fused);
   return launch_status();

@@ -130,6 +130,13 @@ __device__ __forceinline__ f32x8 scalar_buffer_load_x8(u32x4 rsrc) {
   asm volatile("s_buffer_load_dwordx8 %0, %1, %2" : "=&s"(v) : "s"(rsrc), "n"(OFF));
   return v;
 }
+// ... at a byte offset (a multiple of four) held in a scalar register: one descriptor over a whole array serves every
+// request into it, and floats past `bytes` still read as zero.
+__device__ __forceinline__ f32x8 scalar_buffer_load_x8_at(u32x4 rsrc, int offset) {
+  f32x8 v;
+  asm volatile("s_buffer_load_dwordx8 %0, %1, %2" : "=&s"(v) : "s"(rsrc), "s"(offset));
+  return v;
+}
 
 template <bool FIRST>
 __device__ __forceinline__ void split_mma(const u32x4 (&a)[2], const u32x4 (&b)[4], f32x16 (&acc)[2][4]) {
@@ -309,6 +316,14 @@ __device__ __forceinline__ void f16_pair_product_wide(float t0, float t1, float 
       : "v"(t0), "v"(t1), "s"(d0), "s"(d1), "s"(k2048));
 }
 constexpr uint32_t kF16GateLowMask = 0x10001000u;  // fp16 1.0 (0x3c00) -> 2^-11 (0x1000), both halves
+// fma(half H of a packed fp16 pair, d, c) in fp32 (d wave-uniform in a scalar register)
+template <int H>
+__device__ __forceinline__ float f16_half_fma(uint32_t pair, float d, float c) {
+  float r;
+  if constexpr (H == 0) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(pair), "s"(d), "v"(c));
+  else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(pair), "s"(d), "v"(c));
+  return r;
+}
 
 // The same wide low plane for an operand that is a value times a power of two (the general weight gradient's dZ2):
 // hi = fp16(x s), lo = fp16(2^11 (x s - hi)).  Its partner in the hi x lo product must carry the 2^-11: the OTHER
