@@ -40,6 +40,10 @@
  *                f32 HIP tensors; RL8_AMD_MASKED_KERNELS=0 puts them back on torch ops) rl8_masked_pool[_backward]_f32
  *                (TransformerTrader pools its attended window with it), rl8_masked_log_softmax[_backward]_f32,
  *                rl8_masked_categorical_sample_f32 (their route: rl8_masked_rows_route)
+ *     attention  (rl8_amd.nn's SelfAttention / CrossAttention on f32 HIP tensors with sequences of at most 64 cells and
+ *                heads of at most 16 floats, TransformerTrader among them; RL8_AMD_ATTENTION_KERNELS=0, read on every
+ *                call by rl8_amd/nn/fused_attention.py, puts the core back on nn.MultiheadAttention's math backend)
+ *                rl8_attention_f32, rl8_attention_backward_f32 (their envelope: rl8_attention_supports)
  *     towers     rl8_mlp_tower_forward_f16_f32, rl8_mlp_tower_backward_gate_f16_f32, rl8_mlp_tower_backward_f16_f32,
  *                rl8_mlp_wgrad_gate_bits_f32, rl8_mlp_wgrad_fused_split_f32, rl8_mlp_wgrad_fused_pair_f32,
  *                rl8_mlp_pack_w2_f16, rl8_mlp_pack_w2_f16_gate, rl8_mlp_dout_pair_check, the *_supports / *_bytes /
@@ -101,7 +105,8 @@ extern "C" {
  * used to drop it; rl8_gather_minibatch checks every field before its first launch; new queries
  * rl8_rollout_stats_plan, rl8_gather_minibatch_plan, rl8_pack_plan).  Added under 107 without a bump (new entries
  * only): rl8_masked_rows_route, rl8_masked_pool_f32, rl8_masked_pool_backward_f32, rl8_masked_log_softmax_f32,
- * rl8_masked_log_softmax_backward_f32, rl8_masked_categorical_sample_f32. */
+ * rl8_masked_log_softmax_backward_f32, rl8_masked_categorical_sample_f32; rl8_attention_supports, rl8_attention_f32,
+ * rl8_attention_backward_f32. */
 #define RL8_ABI_VERSION 107
 int rl8_abi_version(char *arch, int arch_len);
 
@@ -522,6 +527,42 @@ int rl8_masked_log_softmax_backward_f32(const float *dout, const float *out, int
 int rl8_masked_categorical_sample_f32(const float *x, const uint8_t *mask, const float *noise /*q [rows][k] or NULL*/,
                                       int64_t rows, int k, uint64_t seed, uint64_t step, int64_t row_offset,
                                       float *value_out /*[rows]*/, int64_t *index_out /*[rows]*/, void *stream);
+
+/* Short-sequence attention: the core of nn.MultiheadAttention, softmax(q k^T scale + masks) v with scale = 1 / sqrt(d),
+ * forward and backward (rl8_amd/csrc/attention_kernels.hip).  The projections in front of it and behind it stay the
+ * caller's.
+ * Operands, all f32: q rows [b][tq], k and v rows [b][tk]; each has its own base pointer and a row stride in floats
+ *   (q_stride; kv_stride for both k and v), and head h of a row is the d floats at h d.  A packed [b][t][3 heads d]
+ *   projection is read in place as (p, p + e, p + 2e) with strides 3e, a [b][tk][2e] one as (p, p + e) with 2e.
+ *   key_padding [b][tk] bytes (torch bool storage), NONZERO = PADDED, or NULL -- torch's key_padding_mask and what
+ *   rl8_window_last / rl8_gather_windows write; the OPPOSITE of the rl8_masked_* entries' mask, where nonzero is valid.
+ *   bias [tq][tk] f32 or NULL is added to the scaled scores and may hold -inf.
+ * rl8_attention_f32: out [b][tq][heads d] dense, out[b][q][h d + c] = sum_t P[q, t] v[b][t][h d + c] with
+ *   P = softmax_t(scale q.k + bias), padded keys at -inf; lse [b][heads][tq] = log sum_t exp(s) when a pointer is given.
+ *   A query with no admissible key (every key padded or at -inf) has P = 0: out = 0 and lse = +inf, not NaN -- what
+ *   torch's math backend returns through nn.MultiheadAttention.
+ * rl8_attention_backward_f32, from dout [b][tq][heads d] dense and the forward's out and lse: P = exp(s - lse),
+ *   delta_q = dout[q].out[q], dv[t] = sum_q P[q, t] dout[q], dS[q, t] = P[q, t] (dout[q].v[t] - delta_q),
+ *   dq[q] = scale sum_t dS[q, t] k[t], dk[t] = scale sum_q dS[q, t] q[q].  Two launches in order on `stream`: dq (which
+ *   leaves delta in delta_workspace, [b][heads][tq] floats), then dk and dv.  Every element of dq (rows of dq_stride
+ *   floats), dk and dv (rows of dkv_stride floats; the gaps between rows are left alone) is written; lse = +inf makes
+ *   every gradient of and through a query without an admissible key exactly 0.  No atomics and no reduction across
+ *   lanes: the same bits on every run.
+ * One lane per (b, q, h) resp. (b, t, h), the loop over the other sequence inside it; no LDS.  Envelope
+ *   (rl8_attention_supports, host only: 1 inside, 0 outside, RL8_ESIZE for an argument < 1): tq, tk <= 64, d <= 16,
+ *   any heads and b.
+ * RL8_ENULL: a required pointer (everything but key_padding, bias and the forward's lse).  RL8_ESIZE: b, tq, tk, heads
+ *   or d < 1, a stride below heads d.  RL8_EALIGN: a float pointer off 4 bytes.  RL8_ECONFIG: a shape outside
+ *   rl8_attention_supports.  All before any launch. */
+int rl8_attention_supports(int tq, int tk, int heads, int d);
+int rl8_attention_f32(const float *q, int64_t q_stride, const float *k, const float *v, int64_t kv_stride,
+                      const uint8_t *key_padding, const float *bias, int64_t b, int tq, int tk, int heads, int d,
+                      float *out, float *lse /*may be NULL*/, void *stream);
+int rl8_attention_backward_f32(const float *q, int64_t q_stride, const float *k, const float *v, int64_t kv_stride,
+                               const uint8_t *key_padding, const float *bias, const float *out, const float *lse,
+                               const float *dout, int64_t b, int tq, int tk, int heads, int d, float *dq,
+                               int64_t dq_stride, float *dk, float *dv, int64_t dkv_stride, float *delta_workspace,
+                               void *stream);
 
 /* The same gather for a buffer that is shuffled many times per step()
  * (num_sgd_iters x num_minibatches): rl8_pack_samples lays the fields of every

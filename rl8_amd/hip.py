@@ -189,6 +189,10 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_masked_log_softmax_f32": [_vp, _vp, _i64, _i32, _vp, _vp],
     "rl8_masked_log_softmax_backward_f32": [_vp, _vp, _i64, _i32, _vp, _vp],
     "rl8_masked_categorical_sample_f32": [_vp, _vp, _vp, _i64, _i32, _u64, _u64, _i64, _vp, _vp, _vp],
+    "rl8_attention_supports": [_i32, _i32, _i32, _i32],
+    "rl8_attention_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "rl8_attention_backward_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp,
+                                   _i64, _vp, _vp, _i64, _vp, _vp],
     "rl8_pack_samples": [_vp, _i32, _i64, _i64, _vp, _i32, _vp],
     "rl8_gather_packed": [_vp, _i64, _vp, _i32, _vp, _i32, _vp],
     "rl8_pack_plan": [_i64, _i64, _i32, C.POINTER(PackPlanStruct)],
@@ -1272,6 +1276,92 @@ def masked_categorical_sample(x: torch.Tensor, mask: None | torch.Tensor, noise:
                                                         _ptr(value), _ptr(index), _stream()),
                "rl8_masked_categorical_sample_f32")
     return value, index
+
+
+# --------------------------------------------------------------------------- #
+# Short-sequence attention (rl8_amd/csrc/attention_kernels.hip).
+# --------------------------------------------------------------------------- #
+def attention_supports(tq: int, tk: int, heads: int, d: int) -> bool:
+    """Whether the attention kernels take ``tq`` queries over ``tk`` keys with ``heads`` heads of ``d`` floats (host
+    only)."""
+    status = int(load().rl8_attention_supports(tq, tk, heads, d))
+    _check(min(status, 0), "rl8_attention_supports")
+    return status == 1
+
+
+def _rows(t: torch.Tensor, shape: tuple, what: str) -> int:
+    """Row stride in floats of ``t [B, T, E]`` float32, which may be a slice along the last dimension of a dense
+    ``[B, T, n E]`` tensor: unit stride inside a row, rows evenly spaced over both leading dimensions."""
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} must be {torch.float32}, got {t.dtype}")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{what} must have shape {shape}, got {tuple(t.shape)}")
+    batch_stride, row_stride, unit = t.stride()
+    if shape[1] == 1:  # (the stride of a dimension of one element says nothing)
+        row_stride = batch_stride if shape[0] > 1 else shape[2]
+    if shape[0] == 1:
+        batch_stride = shape[1] * row_stride
+    if (unit != 1 and shape[2] > 1) or row_stride < shape[2] or batch_stride != shape[1] * row_stride:
+        raise ValueError(f"{what} must be dense or a last-dimension slice of a dense tensor, got strides {t.stride()}")
+    return int(row_stride)
+
+
+def _padding_mask(mask: None | torch.Tensor, shape: tuple) -> None | torch.Tensor:
+    """``key_padding`` (bool or uint8, nonzero = PADDED -- the opposite of :func:`_byte_mask`'s masks) as dense bytes."""
+    return _byte_mask(mask, shape, "key_padding")
+
+
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_padding: None | torch.Tensor,
+              bias: None | torch.Tensor, heads: int, *, want_lse: bool = True) -> tuple[torch.Tensor, None | torch.Tensor]:
+    """``softmax(q k^T / sqrt(D) + bias, padded keys at -inf) v`` per head: ``(out [B, Tq, E], lse [B, heads, Tq])``.
+    ``q [B, Tq, E]`` and ``k``, ``v [B, Tk, E]`` may be slices of a packed projection (:func:`_rows`; ``k`` and ``v``
+    with one row stride); ``key_padding [B, Tk]`` nonzero = PADDED, ``bias [Tq, Tk]`` float32, both optional. A query
+    without an admissible key gives 0 and ``lse = +inf``."""
+    q, k, v = q.detach(), k.detach(), v.detach()
+    b, tq, e = q.shape
+    tk = k.shape[1]
+    q_stride, kv_stride = _rows(q, (b, tq, e), "q"), _rows(k, (b, tk, e), "k")
+    if _rows(v, (b, tk, e), "v") != kv_stride:
+        raise ValueError("k and v must have the same row stride")
+    if heads < 1 or e % heads:
+        raise ValueError(f"{heads} heads do not divide rows of {e} floats")
+    key_padding = _padding_mask(key_padding, (b, tk))
+    if bias is not None:
+        _shaped(bias, (tq, tk), "bias")
+    out = torch.empty(b, tq, e, dtype=torch.float32, device=q.device)
+    lse = torch.empty(b, heads, tq, dtype=torch.float32, device=q.device) if want_lse else None
+    with _timed("attention", b):
+        _check(load().rl8_attention_f32(_ptr(q), q_stride, _ptr(k), _ptr(v), kv_stride, _ptr(key_padding), _ptr(bias), b,
+                                        tq, tk, heads, e // heads, _ptr(out), _ptr(lse), _stream()), "rl8_attention_f32")
+    return out, lse
+
+
+def attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_padding: None | torch.Tensor,
+                       bias: None | torch.Tensor, out: torch.Tensor, lse: torch.Tensor, dout: torch.Tensor, heads: int,
+                       dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor) -> None:
+    """Gradients of :func:`attention`'s ``q``, ``k``, ``v`` written into ``dq [B, Tq, E]``, ``dk``, ``dv [B, Tk, E]``,
+    which may be slices of one packed gradient buffer like the operands; every element of the three is written."""
+    q, k, v = q.detach(), k.detach(), v.detach()
+    b, tq, e = q.shape
+    tk = k.shape[1]
+    q_stride, kv_stride = _rows(q, (b, tq, e), "q"), _rows(k, (b, tk, e), "k")
+    dq_stride, dkv_stride = _rows(dq, (b, tq, e), "dq"), _rows(dk, (b, tk, e), "dk")
+    if _rows(v, (b, tk, e), "v") != kv_stride or _rows(dv, (b, tk, e), "dv") != dkv_stride:
+        raise ValueError("k and v, and dk and dv, must have the same row stride")
+    if heads < 1 or e % heads:
+        raise ValueError(f"{heads} heads do not divide rows of {e} floats")
+    key_padding = _padding_mask(key_padding, (b, tk))
+    if bias is not None:
+        _shaped(bias, (tq, tk), "bias")
+    _shaped(out, (b, tq, e), "out")
+    _shaped(lse, (b, heads, tq), "lse")
+    _shaped(dout, (b, tq, e), "dout")
+    delta = torch.empty(b, heads, tq, dtype=torch.float32, device=q.device)
+    with _timed("attention_backward", b):
+        _check(load().rl8_attention_backward_f32(_ptr(q), q_stride, _ptr(k), _ptr(v), kv_stride, _ptr(key_padding),
+                                                 _ptr(bias), _ptr(out), _ptr(lse), _ptr(dout), b, tq, tk, heads,
+                                                 e // heads, _ptr(dq), dq_stride, _ptr(dk), _ptr(dv), dkv_stride,
+                                                 _ptr(delta), _stream()), "rl8_attention_backward_f32")
 
 
 class PackedSamples:

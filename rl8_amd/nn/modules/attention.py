@@ -1,9 +1,13 @@
 """Attention blocks on ``nn.MultiheadAttention`` (``src/rl8/nn/modules/attention.py``).
 
-The attention itself is torch's module, as in the reference; no kernel of this build sits under it. On a HIP device the
-scaled-dot-product call inside it is pinned to torch's math backend: these blocks run at head widths of 2 to 16 on
-sequences of a few cells, outside what the fused backends are written and tested for, and the math backend is the
-composition of matmul, softmax and matmul that the reference's CPU run performs.
+The attention module is torch's, as in the reference, with its parameters and ``state_dict``. On float32 HIP tensors with
+sequences of at most 64 cells and heads of at most 16 features its core -- softmax(Q K^T / sqrt(D) + masks) V, forward
+and backward -- runs on this build's short-sequence attention kernels (``..fused_attention``, ``rl8_attention_f32``),
+between the module's own in- and out-projections. Every other call (CPU tensors, attention dropout in training, other
+dtypes and mask kinds, longer sequences, ``RL8_AMD_ATTENTION_KERNELS=0``) runs the module itself; on a HIP device its
+scaled-dot-product call is then pinned to torch's math backend: these blocks run at head widths of 2 to 16 on sequences
+of a few cells, outside what torch's fused backends are written and tested for, and the math backend is the composition
+of matmul, softmax and matmul that the reference's CPU run performs.
 
 """
 
@@ -16,6 +20,7 @@ import torch
 import torch.nn as nn
 from torch.nn.attention import SDPBackend, sdpa_kernel
 
+from .. import fused_attention
 from .activations import get_activation
 from .module import Module
 from .skip import SequentialSkipConnection
@@ -27,6 +32,9 @@ def _math_attention(x: torch.Tensor):
 
 def _attend(attention: nn.MultiheadAttention, q: torch.Tensor, kv: torch.Tensor, key_padding_mask: None | torch.Tensor,
             attention_mask: None | torch.Tensor) -> torch.Tensor:
+    fused = fused_attention.multihead_attention(attention, q, kv, key_padding_mask, attention_mask)
+    if fused is not None:
+        return fused
     with _math_attention(q):
         out, _ = attention(q, kv, kv, key_padding_mask=key_padding_mask, attn_mask=attention_mask, need_weights=False)
     return out  # type: ignore[no-any-return]
