@@ -44,6 +44,11 @@
  *                heads of at most 16 floats, TransformerTrader among them; RL8_AMD_ATTENTION_KERNELS=0, read on every
  *                call by rl8_amd/nn/fused_attention.py, puts the core back on nn.MultiheadAttention's math backend)
  *                rl8_attention_f32, rl8_attention_backward_f32 (their envelope: rl8_attention_supports)
+ *     feedforward (the LayerNorm -> Linear -> ReLU -> Linear block that ends every SelfAttention / CrossAttention, with
+ *                its skip connection, on f32 HIP tensors of at most 32 features and 256 hidden units;
+ *                opt-in: RL8_AMD_FEEDFORWARD_KERNELS=1, read on every call by rl8_amd/nn/fused_feedforward.py, takes
+ *                it off the torch modules) rl8_feedforward_f32, rl8_feedforward_backward_f32 (their envelope:
+ *                rl8_feedforward_supports; their sizes: rl8_feedforward_limits, rl8_feedforward_workspace_floats)
  *     towers     rl8_mlp_tower_forward_f16_f32, rl8_mlp_tower_backward_gate_f16_f32, rl8_mlp_tower_backward_f16_f32,
  *                rl8_mlp_wgrad_gate_bits_f32, rl8_mlp_wgrad_fused_split_f32, rl8_mlp_wgrad_fused_pair_f32,
  *                rl8_mlp_pack_w2_f16, rl8_mlp_pack_w2_f16_gate, rl8_mlp_dout_pair_check, the *_supports / *_bytes /
@@ -106,7 +111,8 @@ extern "C" {
  * rl8_rollout_stats_plan, rl8_gather_minibatch_plan, rl8_pack_plan).  Added under 107 without a bump (new entries
  * only): rl8_masked_rows_route, rl8_masked_pool_f32, rl8_masked_pool_backward_f32, rl8_masked_log_softmax_f32,
  * rl8_masked_log_softmax_backward_f32, rl8_masked_categorical_sample_f32; rl8_attention_supports, rl8_attention_f32,
- * rl8_attention_backward_f32. */
+ * rl8_attention_backward_f32; rl8_feedforward_supports, rl8_feedforward_limits, rl8_feedforward_workspace_floats,
+ * rl8_feedforward_f32, rl8_feedforward_backward_f32. */
 #define RL8_ABI_VERSION 107
 int rl8_abi_version(char *arch, int arch_len);
 
@@ -563,6 +569,39 @@ int rl8_attention_backward_f32(const float *q, int64_t q_stride, const float *k,
                                const float *dout, int64_t b, int tq, int tk, int heads, int d, float *dq,
                                int64_t dq_stride, float *dk, float *dv, int64_t dkv_stride, float *delta_workspace,
                                void *stream);
+
+/* The fused feedforward block of the attention modules (rl8_amd/csrc/feedforward_kernels.hip), per row of x [rows][f]:
+ *   n   = LayerNorm_f(x; gamma, beta, eps)      biased variance from the centred values, rstd = 1 / sqrt(var + eps)
+ *   out = (residual ? x : 0) + w2 relu(w1 n + b1) + b2
+ * with w1 [hidden][f] and w2 [f][hidden] as nn.Linear holds them, gamma, beta, b2 [f], b1 [hidden]; all f32 and dense.
+ * relu hands a NaN through; its gradient's gate is z > 0 (closed at exactly 0).
+ * rl8_feedforward_f32: one lane per row, the hidden vector in registers only.
+ * rl8_feedforward_backward_f32, from x and dout [rows][f] alone (n and the pre-activations are formed again, by the
+ *   forward's own operations in the forward's order, so the gates agree bit for bit): dx [rows][f] (dout added when
+ *   `residual`), dgamma, dbeta [f], dw1 [hidden][f], db1 [hidden], dw2 [f][hidden], db2 [f].  Every output may be NULL
+ *   and is then not formed; with no output at all nothing is launched.  The parameter gradients are sums of per-workgroup
+ *   and per-wave f32 partial sums over row slices that depend on (rows, f, hidden) only, left in `workspace`
+ *   (rl8_feedforward_workspace_floats(rows, f, hidden) floats, contents undefined before and after; required when a
+ *   parameter gradient is asked for, untouched otherwise) and added up in f64 in a fixed order by the last launch: no
+ *   atomics, the same bits on every run.  Launches in order on `stream`: dx (which also leaves the dgamma / dbeta
+ *   partials), the dw1 / db1 / dw2 / db2 partials, the sum.
+ * Envelope (rl8_feedforward_supports, host only: 1 inside, 0 outside, RL8_ESIZE for an argument < 1): f <= 32,
+ *   hidden <= 256, any rows.  rl8_feedforward_limits writes {grid cap, lanes per workgroup} of the row-per-lane kernels
+ *   and {grid cap, rows staged per workgroup} of the dw kernel -- beyond cap x rows a workgroup strides -- into
+ *   limits[0..3].  rl8_feedforward_workspace_floats: RL8_ESIZE / RL8_ECONFIG as below.
+ * RL8_ENULL: a required pointer (every input; the workspace when a parameter gradient is wanted).  RL8_ESIZE: rows, f or
+ *   hidden < 1.  RL8_EALIGN: a pointer off 4 bytes.  RL8_ECONFIG: a shape outside rl8_feedforward_supports.  All before
+ *   any launch. */
+int rl8_feedforward_supports(int f, int hidden);
+int rl8_feedforward_limits(int *limits /*host, [4]*/);
+int64_t rl8_feedforward_workspace_floats(int64_t rows, int f, int hidden);
+int rl8_feedforward_f32(const float *x, const float *gamma, const float *beta, float eps, const float *w1,
+                        const float *b1, const float *w2, const float *b2, int64_t rows, int f, int hidden, int residual,
+                        float *out, void *stream);
+int rl8_feedforward_backward_f32(const float *x, const float *dout, const float *gamma, const float *beta, float eps,
+                                 const float *w1, const float *b1, const float *w2, int64_t rows, int f, int hidden,
+                                 int residual, float *dx, float *dgamma, float *dbeta, float *dw1, float *db1, float *dw2,
+                                 float *db2, float *workspace, void *stream);
 
 /* The same gather for a buffer that is shuffled many times per step()
  * (num_sgd_iters x num_minibatches): rl8_pack_samples lays the fields of every

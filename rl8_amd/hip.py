@@ -193,6 +193,12 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_attention_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "rl8_attention_backward_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp,
                                    _i64, _vp, _vp, _i64, _vp, _vp],
+    "rl8_feedforward_supports": [_i32, _i32],
+    "rl8_feedforward_limits": [C.POINTER(C.c_int)],
+    "rl8_feedforward_workspace_floats": [_i64, _i32, _i32],
+    "rl8_feedforward_f32": [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "rl8_feedforward_backward_f32": [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp],
     "rl8_pack_samples": [_vp, _i32, _i64, _i64, _vp, _i32, _vp],
     "rl8_gather_packed": [_vp, _i64, _vp, _i32, _vp, _i32, _vp],
     "rl8_pack_plan": [_i64, _i64, _i32, C.POINTER(PackPlanStruct)],
@@ -298,7 +304,8 @@ def load() -> C.CDLL:
                             "rl8_lstm_split_packed_bytes", "rl8_lstm_split_wb_floats", "rl8_lstm_split_state_bytes",
                             "rl8_mlp_f16_packed_bytes", "rl8_lstm_rows_backward_pack_bytes", "rl8_pw_workspace_bytes",
                             "rl8_mlp_narrow_workspace_bytes", "rl8_lstm_narrow_workspace_bytes",
-                            "rl8_lstm_stack_workspace_bytes", "rl8_linear_heads_narrow_workspace_bytes")
+                            "rl8_lstm_stack_workspace_bytes", "rl8_linear_heads_narrow_workspace_bytes",
+                            "rl8_feedforward_workspace_floats")
                 else C.c_int
             )
         built = int(lib.rl8_abi_version(None, 0))
@@ -1362,6 +1369,106 @@ def attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pa
                                                  _ptr(bias), _ptr(out), _ptr(lse), _ptr(dout), b, tq, tk, heads,
                                                  e // heads, _ptr(dq), dq_stride, _ptr(dk), _ptr(dv), dkv_stride,
                                                  _ptr(delta), _stream()), "rl8_attention_backward_f32")
+
+
+# --------------------------------------------------------------------------- #
+# The fused LayerNorm feedforward block (rl8_amd/csrc/feedforward_kernels.hip).
+# --------------------------------------------------------------------------- #
+def feedforward_supports(f: int, hidden: int) -> bool:
+    """Whether the feedforward kernels take rows of ``f`` features through ``hidden`` hidden units (host only)."""
+    status = int(load().rl8_feedforward_supports(f, hidden))
+    _check(min(status, 0), "rl8_feedforward_supports")
+    return status == 1
+
+
+class FeedforwardLimits(NamedTuple):
+    """``rl8_feedforward_limits``: the row-per-lane kernels' grid cap and lanes per workgroup, the weight-gradient
+    kernel's grid cap and rows staged per workgroup. Beyond ``cap x rows`` a workgroup strides."""
+
+    grid_cap: int
+    block: int
+    wgrad_grid_cap: int
+    wgrad_rows: int
+
+
+def feedforward_limits() -> FeedforwardLimits:
+    limits = (C.c_int * 4)()
+    _check(load().rl8_feedforward_limits(limits), "rl8_feedforward_limits")
+    return FeedforwardLimits(*(int(v) for v in limits))
+
+
+def feedforward_workspace_floats(rows: int, f: int, hidden: int) -> int:
+    """Floats of workspace ``rl8_feedforward_backward_f32`` needs for its parameter gradients (host only)."""
+    floats = int(load().rl8_feedforward_workspace_floats(rows, f, hidden))
+    _check(min(floats, 0), "rl8_feedforward_workspace_floats")
+    return floats
+
+
+def _feedforward_operands(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
+                          w2: torch.Tensor, b2: None | torch.Tensor, dout: None | torch.Tensor) -> tuple[int, int, int]:
+    """``(rows, f, hidden)`` of a dense float32 ``x [..., f]``, the block's parameters and ``dout`` like ``x``: every
+    layout checked, then every device."""
+    _dense(x, torch.float32, "x")
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"x must be [..., f] with at least one element, got {tuple(x.shape)}")
+    f = int(x.shape[-1])
+    if w1.dim() != 2:
+        raise ValueError(f"w1 must be [hidden, {f}], got {tuple(w1.shape)}")
+    hidden = int(w1.shape[0])
+    for t, shape, what in ((gamma, (f,), "gamma"), (beta, (f,), "beta"), (w1, (hidden, f), "w1"), (b1, (hidden,), "b1"),
+                           (w2, (f, hidden), "w2"), (b2, (f,), "b2"), (dout, tuple(x.shape), "dout")):
+        if t is not None:
+            _shaped(t, shape, what)
+    for t in (x, gamma, beta, w1, b1, w2, b2, dout):
+        _ptr(t)
+    return x.numel() // f, f, hidden
+
+
+def feedforward(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, w1: torch.Tensor, b1: torch.Tensor,
+                w2: torch.Tensor, b2: torch.Tensor, residual: bool) -> torch.Tensor:
+    """``(x if residual else 0) + linear(relu(linear(layer_norm(x), w1, b1)), w2, b2)`` per row of a dense
+    ``x [..., f]``: ``w1 [hidden, f]``, ``w2 [f, hidden]``, ``gamma``, ``beta``, ``b2 [f]``, ``b1 [hidden]``."""
+    x, gamma, beta, w1, b1, w2, b2 = (t.detach() for t in (x, gamma, beta, w1, b1, w2, b2))
+    rows, f, hidden = _feedforward_operands(x, gamma, beta, w1, b1, w2, b2, None)
+    out = torch.empty_like(x)
+    with _timed("feedforward", rows):
+        _check(load().rl8_feedforward_f32(_ptr(x), _ptr(gamma), _ptr(beta), eps, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
+                                          rows, f, hidden, int(residual), _ptr(out), _stream()), "rl8_feedforward_f32")
+    return out
+
+
+class FeedforwardGrads(NamedTuple):
+    """What :func:`feedforward_backward` returns; a piece that was not asked for is ``None``."""
+
+    dx: None | torch.Tensor
+    dgamma: None | torch.Tensor
+    dbeta: None | torch.Tensor
+    dw1: None | torch.Tensor
+    db1: None | torch.Tensor
+    dw2: None | torch.Tensor
+    db2: None | torch.Tensor
+
+
+def feedforward_backward(x: torch.Tensor, dout: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                         w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, residual: bool, *, want_dx: bool = True,
+                         want_params: bool = True) -> FeedforwardGrads:
+    """Gradients of :func:`feedforward` from ``x`` and ``dout`` alone: ``dx`` like ``x`` and / or the six parameter
+    gradients (the same bits on every run)."""
+    x, dout, gamma, beta, w1, b1, w2 = (t.detach() for t in (x, dout, gamma, beta, w1, b1, w2))
+    rows, f, hidden = _feedforward_operands(x, gamma, beta, w1, b1, w2, None, dout)
+
+    def new(*shape: int) -> torch.Tensor:
+        return torch.empty(shape, dtype=torch.float32, device=x.device)
+
+    dx = torch.empty_like(x) if want_dx else None
+    params = (new(f), new(f), new(hidden, f), new(hidden), new(f, hidden), new(f)) if want_params else (None,) * 6
+    workspace = new(feedforward_workspace_floats(rows, f, hidden)) if want_params else None
+    with _timed("feedforward_backward", rows):
+        _check(load().rl8_feedforward_backward_f32(_ptr(x), _ptr(dout), _ptr(gamma), _ptr(beta), eps, _ptr(w1), _ptr(b1),
+                                                   _ptr(w2), rows, f, hidden, int(residual), _ptr(dx),
+                                                   *(_ptr(p) for p in params), _ptr(workspace), _stream()),
+               "rl8_feedforward_backward_f32")
+    return FeedforwardGrads(dx, *params)
 
 
 class PackedSamples:

@@ -9,6 +9,11 @@ scaled-dot-product call is then pinned to torch's math backend: these blocks run
 of a few cells, outside what torch's fused backends are written and tested for, and the math backend is the composition
 of matmul, softmax and matmul that the reference's CPU run performs.
 
+The feedforward block behind the attention (``_feedforward``) is the reference's ``nn.Sequential`` of torch modules; where
+its activation is ReLU and its dropout is off, ``RL8_AMD_FEEDFORWARD_KERNELS=1`` makes ``SequentialSkipConnection`` run
+it with its skip connection on this build's fused feedforward kernels (``..fused_feedforward``,
+``rl8_feedforward_f32``); without that setting it runs on the modules.
+
 """
 
 from __future__ import annotations

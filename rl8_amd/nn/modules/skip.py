@@ -5,6 +5,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from .. import fused_feedforward
 from ..functional import skip_connection
 from .module import Module
 
@@ -61,10 +62,15 @@ class SequentialSkipConnection(Module[[torch.Tensor, torch.Tensor], torch.Tensor
 
     def forward(self, x: torch.Tensor, y: torch.Tensor, /) -> torch.Tensor:
         """``x`` and ``y`` ``[B, T, ...]`` of one shape: skip-connect them, then run the layers, each appended module
-        inside a skip connection of its own."""
+        inside a skip connection of its own -- the attention modules' feedforward block with its skip connection in one
+        kernel launch where ``fused_feedforward.skip_feedforward`` takes the call."""
         y = skip_connection(x, y, kind=self.kind)
         for i, layer in enumerate(self._layers):
-            y = skip_connection(y, layer(y), kind=self.kind) if i % 2 else layer(y)
+            if i % 2:
+                fused = fused_feedforward.skip_feedforward(layer, y, self.kind)
+                y = fused if fused is not None else skip_connection(y, layer(y), kind=self.kind)
+            else:
+                y = layer(y)
         return y
 
     @property
