@@ -1013,6 +1013,9 @@ int rl8_linear_heads_backward_f32(const float *h, const float *dout, int64_t m, 
  *   into `workspace` (rl8_mlp_narrow_workspace_bytes(m, ...) bytes, no initialisation); rl8_mlp_narrow_reduce_f32
  *   then sums the slabs in a fixed order (fp64) into grads_out = [dW1 (H d_in) | db1 (H) | dW2 (H H) | db2 (H) |
  *   dW3 (n_out H) | db3 (n_out)] floats: bitwise reproducible.  No gradient is produced for x.
+ * rl8_mlp_narrow_backward_dx_f32: the same, and dx [m][d_in] = dz1 W1 (the gradient of x) from the same launch;
+ *   workspace layout and the reduce call are unchanged and the workspace holds the same bits.  dx == NULL: exactly
+ *   rl8_mlp_narrow_backward_f32.
  * All pointers 4-byte aligned; m >= 1; RL8_ESIZE for widths outside the compiled set. */
 int rl8_mlp_narrow_supports(int hidden, int d_in, int n_out);
 int64_t rl8_mlp_narrow_workspace_bytes(int64_t m, int hidden, int d_in, int n_out);
@@ -1024,6 +1027,37 @@ int rl8_mlp_narrow_backward_f32(const float *x, const float *dout, int64_t m, in
                                 int hidden, float *workspace, void *stream);
 int rl8_mlp_narrow_reduce_f32(const float *workspace, int64_t m, int hidden, int d_in, int n_out, float *grads_out,
                               void *stream);
+int rl8_mlp_narrow_backward_dx_f32(const float *x, const float *dout, int64_t m, int d_in, const float *w1,
+                                   const float *b1, const float *w2, const float *b2, const float *w3, int n_out,
+                                   int hidden, float *workspace, float *dx, void *stream);
+
+/* ---- BatchNorm1d behind the first layer of a narrow tower, folded into that layer (batchnorm_tower_kernels.hip).  In
+ * training mode the norm of z1 = x W1^T + b1 over the batch is an affine map of x: with mu = mean_i x_i and the biased
+ * covariance C = (1/m) sum_i (x_i - mu)(x_i - mu)^T, unit j has batch mean m_z_j = W1_j . mu + b1_j, batch variance
+ * v_j = W1_j C W1_j^T, r_j = 1 / sqrt(v_j + eps), and y_j = a_j . x + c_j with a_j = gamma_j r_j W1_j and
+ * c_j = beta_j - gamma_j r_j (W1_j . mu).  The tower then runs rl8_mlp_narrow_* with w1 = a, b1 = c.
+ * rl8_tower_moments_f64: x [m][d_in] fp32 -> mu [d_in], cov [d_in][d_in] in fp64.  One pass: sums of x - p and of
+ *   (x - p)(x - p)^T about the pivot p = x[0] in fp64, one partial slab per workgroup in `workspace`
+ *   (rl8_tower_moments_workspace_bytes(m, d_in) bytes, no initialisation), summed in slab order by a second launch
+ *   into mu = p + S1 / m, cov = S2 / m - (S1 / m)(S1 / m)^T.  No atomics: the same bits on every run; a constant column
+ *   has a row and a column of cov that are exactly 0.
+ * rl8_batchnorm_fold_f32: one launch.  training != 0: from (mu, cov, m >= 2) and w1 [H][d_in], b1, gamma, beta [H], eps
+ *   -> a [H][d_in], c [H] (fp32) and r, m_z, v [H] (fp64), all formed in fp64 and rounded once; running_mean /
+ *   running_var [H] (both or neither) move in place by `factor` -- by 1 / *tracked where `tracked` (device int64, the
+ *   count of batches INCLUDING this one) is given -- towards m_z and the unbiased v m / (m - 1).  training == 0:
+ *   a_j = gamma_j W1_j / sqrt(running_var_j + eps), c_j = beta_j + gamma_j (b1_j - running_mean_j) / sqrt(running_var_j
+ *   + eps); nothing else is read or written.
+ * rl8_tower_limits (host only): limits[0..4] = the moments kernel's workgroup cap and rows per step, the narrow tower
+ *   kernels' workgroup caps at H = 64 and 128 and their rows per step.
+ * RL8_ENULL: a required pointer.  RL8_ESIZE: m < 1 (fold in training mode: m < 2), d_in outside 1 .. 16, hidden not 64
+ *   or 128.  RL8_EALIGN: a float pointer off 4 bytes, a double / int64 pointer off 8.  All before any launch. */
+int rl8_tower_limits(int *limits /*host*/);
+int64_t rl8_tower_moments_workspace_bytes(int64_t m, int d_in);
+int rl8_tower_moments_f64(const float *x, int64_t m, int d_in, double *mu, double *cov, double *workspace, void *stream);
+int rl8_batchnorm_fold_f32(const double *mu, const double *cov, int64_t m, int d_in, int hidden, const float *w1,
+                           const float *b1, const float *gamma, const float *beta, double eps, float *running_mean,
+                           float *running_var, double factor, const int64_t *tracked, int training, float *a, float *c,
+                           double *r, double *m_z, double *v, void *stream);
 
 /* ---- Narrow LSTMs: one layer, biased, batch_first, hidden width H = 64 or 128, d_in <= 16 (lstm_narrow_kernels.hip).
  * Weights in torch layout, unpacked: w_ih [4H][d_in], w_hh [4H][H], b_ih / b_hh [4H], gate order i, f, g, o.  The

@@ -3,7 +3,9 @@
 ``MLPTrader`` is the feed-forward one: a padded rolling window of the last ``seq_len + 1`` price changes (a tuple-key
 view requirement, built by the window kernels), summed over four spans, next to an embedding of ``invested`` and the
 change of the price against the position; two BatchNorm towers give masked logits and a value. The towers run as torch
-modules (BatchNorm towers are outside the fused tower families).
+modules by default; with ``RL8_AMD_BATCHNORM_TOWERS=1`` (opt-in, read per call) they run on the narrow tower kernels,
+the BatchNorm folded into the first layer from the batch's moments (``nn/fused_mlp.py``, family ``"narrow_bn"``), and
+the gradient of the towers' input, which trains ``invested_embedding``, comes from the same backward launch.
 
 ``TransformerTrader`` is the attentive feed-forward one: the same window, embedded cell by cell, goes through a
 parameter-sharing stack of residual self-attention blocks (``rl8_amd.nn``, on torch's ``nn.MultiheadAttention``) under
@@ -32,6 +34,18 @@ from ..tensordict import TensorDict
 from ..views import ViewRequirement
 
 LOG_CHANGE, LOG_CHANGE_POSITION = "LOG_CHANGE(price)", "LOG_CHANGE(price, position)"
+
+
+def _tower(tower: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
+    """``tower(x)`` for ``Sequential(MLP(..., norm_layer=BatchNorm1d), ReLU, head)``: on the BatchNorm tower kernels
+    where ``fused_mlp.tower_forward`` takes the call (``RL8_AMD_BATCHNORM_TOWERS=1``, width 64 / 128, float32 on the
+    device), else the modules."""
+    from ..nn import fused_mlp
+
+    if not fused_mlp.batchnorm_towers_on():  # (the default route pays for no slicing of the Sequential)
+        return tower(x)
+    out = fused_mlp.tower_forward(tower[:2], [tower[2]], x)
+    return tower(x) if out is None else out
 
 
 class MLPTrader(Model):
@@ -88,8 +102,8 @@ class MLPTrader(Model):
         )
         finfo = torch.finfo(torch.float32)
         mask = torch.clamp(torch.log(obs["action_mask"].to(torch.float32)), min=finfo.min, max=finfo.max)
-        logits = self.feature_model(x).reshape(-1, 1, 3) + mask.reshape(-1, 1, 3)
-        self._value = self.vf_model(x)
+        logits = _tower(self.feature_model, x).reshape(-1, 1, 3) + mask.reshape(-1, 1, 3)
+        self._value = _tower(self.vf_model, x)
         return TensorDict({"logits": logits}, batch_size=batch.batch_size, device=x.device)
 
     def to(self, device: Device) -> "MLPTrader":  # type: ignore[override]
@@ -164,8 +178,8 @@ class TransformerTrader(Model):
         )
         finfo = torch.finfo(torch.float32)
         mask = torch.clamp(torch.log(obs["action_mask"].to(torch.float32)), min=finfo.min, max=finfo.max)
-        logits = self.feature_model(x).reshape(-1, 1, 3) + mask.reshape(-1, 1, 3)
-        self._value = self.vf_model(x)
+        logits = _tower(self.feature_model, x).reshape(-1, 1, 3) + mask.reshape(-1, 1, 3)
+        self._value = _tower(self.vf_model, x)
         return TensorDict({"logits": logits}, batch_size=batch.batch_size, device=x.device)
 
     def to(self, device: Device) -> "TransformerTrader":  # type: ignore[override]

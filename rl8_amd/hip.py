@@ -254,6 +254,12 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_mlp_narrow_forward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "rl8_mlp_narrow_backward_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "rl8_mlp_narrow_reduce_f32": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "rl8_mlp_narrow_backward_dx_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "rl8_tower_limits": [C.POINTER(C.c_int)],
+    "rl8_tower_moments_workspace_bytes": [_i64, _i32],
+    "rl8_tower_moments_f64": [_vp, _i64, _i32, _vp, _vp, _vp, _vp],
+    "rl8_batchnorm_fold_f32": [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, C.c_double, _vp,
+                               _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_lstm_narrow_supports": [_i32, _i32],
     "rl8_lstm_narrow_workspace_bytes": [_i64, _i32, _i32, _i32],
     "rl8_lstm_narrow_forward_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
@@ -305,7 +311,7 @@ def load() -> C.CDLL:
                             "rl8_mlp_f16_packed_bytes", "rl8_lstm_rows_backward_pack_bytes", "rl8_pw_workspace_bytes",
                             "rl8_mlp_narrow_workspace_bytes", "rl8_lstm_narrow_workspace_bytes",
                             "rl8_lstm_stack_workspace_bytes", "rl8_linear_heads_narrow_workspace_bytes",
-                            "rl8_feedforward_workspace_floats")
+                            "rl8_feedforward_workspace_floats", "rl8_tower_moments_workspace_bytes")
                 else C.c_int
             )
         built = int(lib.rl8_abi_version(None, 0))
@@ -1905,9 +1911,11 @@ def mlp_narrow_forward(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: 
 
 
 def mlp_narrow_backward(x: torch.Tensor, dout: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
-                        b2: torch.Tensor, w3: torch.Tensor) -> dict[str, torch.Tensor]:
+                        b2: torch.Tensor, w3: torch.Tensor, *, want_dx: bool = False) -> dict[str, torch.Tensor]:
     """Gradients of the six tower parameters ("w1", "b1", "w2", "b2", "w3", "b3") for the output gradient ``dout``
-    [M, n_out]: the forward recomputed from x, partial slabs per workgroup summed in a fixed order (deterministic)."""
+    [M, n_out]: the forward recomputed from x, partial slabs per workgroup summed in a fixed order (deterministic).
+    ``want_dx``: the gradient of x too ("x", [M, d_in]) from the same launch (``rl8_mlp_narrow_backward_dx_f32``, timed
+    as "mlp_narrow_backward_dx"); the parameter gradients hold the same bits either way."""
     x, dout, w1, b1, w2, b2, w3 = (t.detach() for t in (x, dout, w1, b1, w2, b2, w3))
     m, d_in, hidden, n_out = _narrow_params(x, w1, b1, w2, b2, w3, None)
     _shaped(dout, (m, n_out), "dout")
@@ -1916,16 +1924,103 @@ def mlp_narrow_backward(x: torch.Tensor, dout: torch.Tensor, w1: torch.Tensor, b
                      device=x.device)
     sizes = (hidden * d_in, hidden, hidden * hidden, hidden, n_out * hidden, n_out)
     grads = torch.empty(sum(sizes), dtype=torch.float32, device=x.device)
-    with _timed("mlp_narrow_backward", m):
-        _check(lib.rl8_mlp_narrow_backward_f32(_ptr(x), _ptr(dout), m, d_in, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
-                                               _ptr(w3), n_out, hidden, _ptr(ws), _stream()),
-               "rl8_mlp_narrow_backward_f32")
+    dx = torch.empty_like(x) if want_dx else None
+    if want_dx:
+        with _timed("mlp_narrow_backward_dx", m):
+            _check(lib.rl8_mlp_narrow_backward_dx_f32(_ptr(x), _ptr(dout), m, d_in, _ptr(w1), _ptr(b1), _ptr(w2),
+                                                      _ptr(b2), _ptr(w3), n_out, hidden, _ptr(ws), _ptr(dx), _stream()),
+                   "rl8_mlp_narrow_backward_dx_f32")
+    else:
+        with _timed("mlp_narrow_backward", m):
+            _check(lib.rl8_mlp_narrow_backward_f32(_ptr(x), _ptr(dout), m, d_in, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
+                                                   _ptr(w3), n_out, hidden, _ptr(ws), _stream()),
+                   "rl8_mlp_narrow_backward_f32")
     with _timed("mlp_narrow_reduce", m):
         _check(lib.rl8_mlp_narrow_reduce_f32(_ptr(ws), m, hidden, d_in, n_out, _ptr(grads), _stream()),
                "rl8_mlp_narrow_reduce_f32")
     parts = torch.split(grads, sizes)
     shapes = ((hidden, d_in), (hidden,), (hidden, hidden), (hidden,), (n_out, hidden), (n_out,))
-    return {k: p.view(s) for k, p, s in zip(("w1", "b1", "w2", "b2", "w3", "b3"), parts, shapes)}
+    got = {k: p.view(s) for k, p, s in zip(("w1", "b1", "w2", "b2", "w3", "b3"), parts, shapes)}
+    if dx is not None:
+        got["x"] = dx
+    return got
+
+
+# --------------------------------------------------------------------------- #
+# A BatchNorm1d behind the first layer of a narrow tower, folded into that layer (batchnorm_tower_kernels.hip).
+# --------------------------------------------------------------------------- #
+class TowerLimits(NamedTuple):
+    """``rl8_tower_limits``: the moments kernel's workgroup cap and rows per step, the narrow tower kernels' workgroup
+    caps at width 64 and 128 and their rows per step. Beyond ``cap x rows`` a workgroup strides."""
+
+    moments_grid_cap: int
+    moments_rows: int
+    narrow_grid_cap_64: int
+    narrow_grid_cap_128: int
+    narrow_rows: int
+
+
+def tower_limits() -> TowerLimits:
+    limits = (C.c_int * 5)()
+    _check(load().rl8_tower_limits(limits), "rl8_tower_limits")
+    return TowerLimits(*(int(v) for v in limits))
+
+
+def tower_moments(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(mu [d_in], C [d_in, d_in])`` of ``x`` [M, d_in <= 16] in float64: the batch mean and the biased covariance, one
+    pass over x, bitwise reproducible."""
+    x = x.detach()
+    _dense(x, torch.float32, "x")
+    if x.ndim != 2:
+        raise ValueError("x must be [M, d_in]")
+    m, d_in = x.shape
+    lib = load()
+    nbytes = int(lib.rl8_tower_moments_workspace_bytes(m, d_in))
+    _check(min(nbytes, 0), "rl8_tower_moments_workspace_bytes")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+    stats = torch.empty(d_in + d_in * d_in, dtype=torch.float64, device=x.device)
+    mu, cov = stats[:d_in], stats[d_in:].view(d_in, d_in)
+    with _timed("tower_moments", m):
+        _check(lib.rl8_tower_moments_f64(_ptr(x), m, d_in, _ptr(mu), _ptr(cov), _ptr(ws), _stream()),
+               "rl8_tower_moments_f64")
+    return mu, cov
+
+
+def batchnorm_fold(w1: torch.Tensor, b1: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, *,
+                   moments: None | tuple[torch.Tensor, torch.Tensor, int] = None,
+                   running_mean: None | torch.Tensor = None, running_var: None | torch.Tensor = None,
+                   factor: float = 0.0, tracked: None | torch.Tensor = None) -> tuple[torch.Tensor, ...]:
+    """The layer ``BatchNorm1d(Linear(x))`` is on this batch. ``moments`` = ``(mu, C, m)`` (training): returns ``(A, c,
+    r, m_z, v)`` -- ``A`` [H, d_in] and ``c`` [H] float32, the statistics float64 -- and moves ``running_mean`` /
+    ``running_var`` in place by ``factor`` (by ``1 / tracked`` with the device counter ``tracked`` given). ``moments``
+    ``None`` (eval): ``(A, c)`` from the running statistics."""
+    w1, b1, gamma, beta = (t.detach() for t in (w1, b1, gamma, beta))
+    _dense(w1, torch.float32, "w1")
+    if w1.ndim != 2:
+        raise ValueError("w1 must be [H, d_in]")
+    hidden, d_in = w1.shape
+    for name, t in (("b1", b1), ("gamma", gamma), ("beta", beta), ("running_mean", running_mean),
+                    ("running_var", running_var)):
+        if t is not None:
+            _shaped(t, (hidden,), name)
+    if tracked is not None:
+        _shaped(tracked, (), "tracked", torch.int64)
+    a = torch.empty(hidden, d_in, dtype=torch.float32, device=w1.device)
+    c = torch.empty(hidden, dtype=torch.float32, device=w1.device)
+    if moments is None:
+        mu = cov = r = m_z = v = None
+        m = 0
+    else:
+        mu, cov, m = moments
+        _shaped(mu, (d_in,), "mu", torch.float64)
+        _shaped(cov, (d_in, d_in), "C", torch.float64)
+        r, m_z, v = torch.empty(3, hidden, dtype=torch.float64, device=w1.device).unbind(0)
+    with _timed("batchnorm_fold", hidden):
+        _check(load().rl8_batchnorm_fold_f32(_ptr(mu), _ptr(cov), m, d_in, hidden, _ptr(w1), _ptr(b1), _ptr(gamma),
+                                             _ptr(beta), float(eps), _ptr(running_mean), _ptr(running_var),
+                                             float(factor), _ptr(tracked), int(moments is not None), _ptr(a), _ptr(c),
+                                             _ptr(r), _ptr(m_z), _ptr(v), _stream()), "rl8_batchnorm_fold_f32")
+    return (a, c) if moments is None else (a, c, r, m_z, v)
 
 
 # --------------------------------------------------------------------------- #

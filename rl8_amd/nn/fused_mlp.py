@@ -11,10 +11,18 @@ weights; this module only changes how the tower is evaluated.
 Towers of hidden width 64 or 128 (same structure, ``d_in <= 16``, ``n_out <= 8``) run
 their own kernel family (``mlp_narrow_kernels.hip``, ``_NarrowTower``): fp32 MFMA for
 layer 2, nothing saved by the forward, activations recomputed by the one backward
-kernel.  They are never recorded for rollout replay.
+kernel.  They are never recorded for rollout replay.  An input that asks for its
+gradient (a tower behind a learned encoder) gets it from the same backward launch
+(``rl8_mlp_narrow_backward_dx_f32``).
+
+The same towers with an affine ``BatchNorm1d`` behind layer 1 (family ``"narrow_bn"``: the
+two towers of ``MLPTrader`` and ``TransformerTrader``) run on those kernels too, opt-in with
+``RL8_AMD_BATCHNORM_TOWERS=1``: the norm is folded into layer 1 from the batch's first and
+second moments of x (``_NarrowBatchNormTower``; the algebra stands above it, and
+``batchnorm_tower_reference`` is its torch expression).
 
 ``tower_forward`` falls back to the module's own eager path whenever the tower
-is none of these shapes (other widths, activations, norm layers, non-HIP or
+is none of these shapes (other widths, activations, other norm layers, non-HIP or
 non-fp32 inputs), so custom models are unaffected.
 
 Under ``enable_amp`` (torch autocast) the fused towers still run, at fp32 accuracy: that is
@@ -524,17 +532,25 @@ def _tower_params(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear]) -> l
 def _family(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[str, nn.Linear, nn.Linear]:
     """The one place the module structure is inspected: (family, layer1, layer2) if ``trunk`` is
     ``Sequential(MLP(Linear, ReLU, Linear), ReLU)`` with biased layers of one width and biased heads (one at least) that
-    read it -- "wide": 256, "narrow": a width in ``hip.MLP_NARROW_HIDDEN`` (``mlp_narrow_kernels.hip``) -- else ``None``."""
+    read it -- "wide": 256, "narrow": a width in ``hip.MLP_NARROW_HIDDEN`` (``mlp_narrow_kernels.hip``) -- else ``None``.
+    "narrow_bn": a narrow tower with an affine ``BatchNorm1d`` that tracks running statistics behind layer 1,
+    ``Sequential(MLP(Linear, BatchNorm1d, ReLU, Linear), ReLU)`` (the norm is ``trunk[0][1]``)."""
     if not isinstance(trunk, nn.Sequential) or len(trunk) < 2:
         return None
     mlp, act = trunk[0], trunk[1]
-    if not isinstance(mlp, nn.Sequential) or len(mlp) != 3 or not isinstance(act, nn.ReLU):
+    if not isinstance(mlp, nn.Sequential) or len(mlp) not in (3, 4) or not isinstance(act, nn.ReLU):
         return None
-    l1, a1, l2 = mlp[0], mlp[1], mlp[2]
+    norm = mlp[1] if len(mlp) == 4 else None
+    l1, a1, l2 = mlp[0], mlp[-2], mlp[-1]
     if not (isinstance(l1, nn.Linear) and isinstance(a1, nn.ReLU) and isinstance(l2, nn.Linear)):
         return None
     width = l1.out_features
     family = "narrow" if width in hip.MLP_NARROW_HIDDEN else "wide" if width == hip.MLP_HIDDEN else None
+    if norm is not None:
+        if not (type(norm) is nn.BatchNorm1d and family == "narrow" and norm.num_features == width and norm.affine
+                and norm.track_running_stats and norm.running_mean is not None):
+            return None
+        family = "narrow_bn"
     if family is None or l2.in_features != width or l2.out_features != width:
         return None
     if l1.in_features > hip.MLP_MAX_IN or l1.bias is None or l2.bias is None:
@@ -558,8 +574,181 @@ class _NarrowTower(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):  # type: ignore[override]
         x, w1, b1, w2, b2, w3, _ = ctx.saved_tensors
-        g = hip.mlp_narrow_backward(x, dout.contiguous().float(), w1, b1, w2, b2, w3)
-        return None, g["w1"], g["b1"], g["w2"], g["b2"], g["w3"], g["b3"]
+        # (an input that asks for its gradient -- a tower behind a learned encoder -- takes the entry that forms dx)
+        g = hip.mlp_narrow_backward(x, dout.contiguous().float(), w1, b1, w2, b2, w3, want_dx=ctx.needs_input_grad[0])
+        return g.get("x"), g["w1"], g["b1"], g["w2"], g["b2"], g["w3"], g["b3"]
+
+
+# --------------------------------------------------------------------------- #
+# BatchNorm towers ("narrow_bn"): Linear -> BatchNorm1d -> ReLU -> Linear -> ReLU -> heads at width 64 / 128.
+#
+# A BatchNorm1d directly behind a Linear is an affine map of x.  In training mode, with mu = mean_i x_i and the biased
+# covariance C = (1/B) sum_i (x_i - mu)(x_i - mu)^T of the batch, unit j of z1 = x W1^T + b1 has
+#     batch mean  m_j = W1_j . mu + b1_j          batch variance  v_j = W1_j C W1_j^T
+#     r_j = 1 / sqrt(v_j + eps),  s_j = gamma_j r_j
+#     y_j = a_j . x + c_j,   a_j = s_j W1_j,   c_j = beta_j - s_j (W1_j . mu)                     (b1 cancels)
+# so the tower is a plain narrow tower with W1' = A, b1' = c.  With GA = dL/dA and gc = dL/dc of that tower:
+#     dbeta = gc                          ds_j = GA_j . W1_j - gc_j (W1_j . mu)
+#     dgamma_j = r_j ds_j                 dv_j = -1/2 r_j^3 gamma_j ds_j
+#     dW1_j = s_j GA_j - gc_j s_j mu + 2 dv_j (C W1_j)                     db1 = 0
+#     dmu = - sum_j gc_j s_j W1_j         dC = sum_j dv_j W1_j W1_j^T
+#     dx_i = dx_i(tower) + dmu / B + (2 / B) dC (x_i - mu)
+# In eval mode a_j = gamma_j W1_j / sqrt(rv_j + eps) and c_j = beta_j + gamma_j (b1_j - rm_j) / sqrt(rv_j + eps).
+# --------------------------------------------------------------------------- #
+def _fold_training(mu, cov, w1, b1, gamma, beta, eps):
+    """``(A, c, r, m_z, v)`` from the batch moments of x, in the dtype of the operands."""
+    wm = w1 @ mu
+    v = ((w1 @ cov) * w1).sum(-1).clamp_min(0.0)
+    r = torch.rsqrt(v + eps)
+    s = gamma * r
+    return s[:, None] * w1, beta - s * wm, r, wm + b1, v
+
+
+def _fold_training_backward(ga, gc, w1, gamma, mu, cov, r):
+    """``(dW1, dgamma, dbeta, dmu, dC)`` from the gradients ``ga`` / ``gc`` of the folded layer."""
+    s = gamma * r
+    ds = (ga * w1).sum(-1) - gc * (w1 @ mu)
+    dv = -0.5 * r ** 3 * gamma * ds
+    dw1 = s[:, None] * ga - (gc * s)[:, None] * mu[None, :] + 2.0 * dv[:, None] * (w1 @ cov)
+    return dw1, r * ds, gc, -(gc * s) @ w1, (w1 * dv[:, None]).t() @ w1
+
+
+def _fold_eval(w1, b1, gamma, beta, running_mean, running_var, eps):
+    """``(A, c, r)`` from the running statistics."""
+    r = torch.rsqrt(running_var + eps)
+    s = gamma * r
+    return s[:, None] * w1, beta + s * (b1 - running_mean), r
+
+
+def _fold_eval_backward(ga, gc, w1, shift, gamma, r):
+    """``(dW1, db1, dgamma, dbeta)``; ``shift`` = b1 - running_mean."""
+    s = gamma * r
+    return s[:, None] * ga, s * gc, r * ((ga * w1).sum(-1) + gc * shift), gc
+
+
+def _dx_statistics_term(dx: torch.Tensor, x: torch.Tensor, mu: torch.Tensor, dmu: torch.Tensor, dcov: torch.Tensor) -> None:
+    """``dx += dmu / B + (2 / B) (x - mu) dC`` in place: one elementwise pass and one ``addmm_`` over ``[B, d_in]``.  The
+    centring uses ``mu`` rounded to the dtype of x; what the rounding leaves goes into the constant row."""
+    rows = x.shape[0]
+    scaled = dcov * (2.0 / rows)
+    mu_x = mu.to(x.dtype)
+    const = dmu / rows - (mu - mu_x.to(mu.dtype)) @ scaled
+    dx.addmm_(x - mu_x, scaled.to(x.dtype))
+    dx.add_(const.to(x.dtype))
+
+
+def _running_update(running: torch.Tensor, new: torch.Tensor, factor) -> torch.Tensor:
+    return (1.0 - factor) * running + factor * new
+
+
+def batchnorm_tower_reference(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                              eps: float, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, *,
+                              training: bool, running_mean: None | torch.Tensor = None,
+                              running_var: None | torch.Tensor = None, momentum: None | float = 0.1,
+                              num_batches_tracked: int = 0, dout: None | torch.Tensor = None) -> dict:
+    """The torch expression of what the BatchNorm tower route computes, in any dtype on any device, without autograd:
+    the yardstick of the tests. ``out`` [B, n_out]; in training mode ``num_batches_tracked`` plus one and the moved
+    ``running_mean`` / ``running_var`` (new tensors; ``momentum`` ``None`` is the cumulative average, as in
+    ``nn.BatchNorm1d``); with ``dout`` the hand-written gradients ``dx, dw1, db1, dgamma, dbeta, dw2, db2, dw3, db3``."""
+    rows = x.shape[0]
+    got: dict[str, torch.Tensor] = {}
+    if training:
+        mu = x.mean(0)
+        xc = x - mu
+        cov = xc.t() @ xc / rows
+        a, c, r, m_z, v = _fold_training(mu, cov, w1, b1, gamma, beta, eps)
+        if running_mean is not None and running_var is not None:
+            got["num_batches_tracked"] = num_batches_tracked + 1
+            factor = 1.0 / (num_batches_tracked + 1) if momentum is None else momentum
+            got["running_mean"] = _running_update(running_mean, m_z, factor)
+            got["running_var"] = _running_update(running_var, v * (rows / (rows - 1)), factor)
+    else:
+        a, c, r = _fold_eval(w1, b1, gamma, beta, running_mean, running_var, eps)
+    z1 = x @ a.t() + c
+    h1 = torch.relu(z1)
+    z2 = h1 @ w2.t() + b2
+    h2 = torch.relu(z2)
+    got["out"] = h2 @ w3.t() + b3
+    if dout is None:
+        return got
+    dz2 = (dout @ w3) * (z2 > 0)
+    dz1 = (dz2 @ w2) * (z1 > 0)
+    got.update(dw3=dout.t() @ h2, db3=dout.sum(0), dw2=dz2.t() @ h1, db2=dz2.sum(0))
+    ga, gc, dx = dz1.t() @ x, dz1.sum(0), dz1 @ a
+    if training:
+        dw1, dgamma, dbeta, dmu, dcov = _fold_training_backward(ga, gc, w1, gamma, mu, cov, r)
+        db1 = torch.zeros_like(b1)
+        _dx_statistics_term(dx, x, mu, dmu, dcov)
+    else:
+        dw1, db1, dgamma, dbeta = _fold_eval_backward(ga, gc, w1, b1 - running_mean, gamma, r)
+    got.update(dx=dx, dw1=dw1, db1=db1, dgamma=dgamma, dbeta=dbeta)
+    return got
+
+
+def batchnorm_towers_on() -> bool:
+    """``RL8_AMD_BATCHNORM_TOWERS=1`` (read on every call) turns the BatchNorm tower route on; unset or anything else
+    keeps every BatchNorm tower on the torch modules (DESIGN.md section 8 says why it is not the default)."""
+    return os.environ.get("RL8_AMD_BATCHNORM_TOWERS", "0") == "1"
+
+
+class _NarrowBatchNormTower(torch.autograd.Function):
+    """A narrow tower with a BatchNorm1d behind layer 1. Training: the moments of x (``rl8_tower_moments_f64``), the
+    fold (``rl8_batchnorm_fold_f32``, which also moves the running statistics), then the plain narrow forward on the
+    folded layer. The backward runs the narrow backward on the SAVED folded layer -- never folded again, so forward and
+    backward agree on every gate bit -- and takes the fold's own backward in float64 on the ``[H, d_in]`` / ``[d_in,
+    d_in]`` tensors with torch ops (no host synchronisation). Eval: the fold from the running statistics."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, gamma, beta, w2, b2, w3, b3, norm):  # type: ignore[override]
+        training = norm.training
+        if training:
+            mu, cov = hip.tower_moments(x)
+            norm.num_batches_tracked.add_(1)
+            cumulative = norm.momentum is None
+            a, c, r, _, _ = hip.batchnorm_fold(w1, b1, gamma, beta, norm.eps, moments=(mu, cov, x.shape[0]),
+                                               running_mean=norm.running_mean, running_var=norm.running_var,
+                                               factor=0.0 if cumulative else norm.momentum,
+                                               tracked=norm.num_batches_tracked if cumulative else None)
+            ctx.save_for_backward(x, a, c, w2, b2, w3, w1, gamma, mu, cov, r)
+        else:
+            a, c = hip.batchnorm_fold(w1, b1, gamma, beta, norm.eps, running_mean=norm.running_mean,
+                                      running_var=norm.running_var)
+            r = torch.rsqrt(norm.running_var.double() + norm.eps)
+            ctx.save_for_backward(x, a, c, w2, b2, w3, w1, gamma, b1.detach().double() - norm.running_mean.double(), r)
+        ctx.training = training
+        return hip.mlp_narrow_forward(x, a, c, w2, b2, w3, b3)
+
+    @staticmethod
+    def backward(ctx, dout):  # type: ignore[override]
+        x, a, c, w2, b2, w3, w1, gamma, *stats = ctx.saved_tensors
+        g = hip.mlp_narrow_backward(x, dout.contiguous().float(), a, c, w2, b2, w3, want_dx=ctx.needs_input_grad[0])
+        ga, gc, w1d, gammad = (t.double() for t in (g["w1"], g["b1"], w1, gamma))
+        dx = g.get("x")
+        if ctx.training:
+            mu, cov, r = stats
+            dw1, dgamma, dbeta, dmu, dcov = _fold_training_backward(ga, gc, w1d, gammad, mu, cov, r)
+            db1 = torch.zeros_like(c)
+            if dx is not None:
+                _dx_statistics_term(dx, x, mu, dmu, dcov)
+        else:
+            shift, r = stats
+            dw1, db1, dgamma, dbeta = _fold_eval_backward(ga, gc, w1d, shift, gammad, r)
+        return (dx, dw1.float(), db1.float(), dgamma.float(), dbeta.float(), g["w2"], g["b2"], g["w3"], g["b3"], None)
+
+
+def _batchnorm_tower_forward(l1: nn.Linear, norm: nn.BatchNorm1d, l2: nn.Linear, w3: torch.Tensor, b3: torch.Tensor,
+                             x: torch.Tensor) -> None | torch.Tensor:
+    """The "narrow_bn" route, or ``None`` when this call is not its: the switch off, autocast, an ``x`` that is not
+    dense or is empty, parameters that are not float32 on the device, one row in training mode (the module then raises
+    torch's own ``ValueError``)."""
+    if not batchnorm_towers_on() or torch.is_autocast_enabled() or not x.is_contiguous() or x.numel() == 0:
+        return None
+    if norm.training and x.shape[0] == 1:
+        return None
+    params = (l1.weight, l1.bias, norm.weight, norm.bias, l2.weight, l2.bias, w3, b3)
+    if not all(p.is_cuda and p.dtype == torch.float32 for p in (*params, norm.running_mean, norm.running_var)):
+        return None
+    return _NarrowBatchNormTower.apply(x, *params, norm)
 
 
 def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Tensor, *,
@@ -578,6 +767,8 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
     if found is None or x.shape[1] != found[1].in_features:
         return None
     family, l1, l2 = found
+    if family == "narrow_bn" and not batchnorm_towers_on():  # (opt-in: nothing else is done for it while it is off)
+        return None
     # opt-in prototype: scalar observations from an exact piecewise-linear table
     if family == "wide" and piecewise_mlp.ENABLED and x.shape[1] == 1:
         out = piecewise_mlp.tower_forward(l1, l2, heads, x)
@@ -585,6 +776,8 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
             return out
     w3 = heads[0].weight if len(heads) == 1 else torch.cat([h.weight for h in heads], 0)
     b3 = heads[0].bias if len(heads) == 1 else torch.cat([h.bias for h in heads], 0)
+    if family == "narrow_bn":
+        return _batchnorm_tower_forward(l1, trunk[0][1], l2, w3, b3, x)
     if family == "narrow":  # (never recorded or replayed: everything below assumes width 256)
         return _NarrowTower.apply(x.contiguous(), l1.weight, l1.bias, l2.weight, l2.bias, w3, b3)
     if pair_gradients is None:
