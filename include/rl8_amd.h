@@ -112,7 +112,12 @@ extern "C" {
  * only): rl8_masked_rows_route, rl8_masked_pool_f32, rl8_masked_pool_backward_f32, rl8_masked_log_softmax_f32,
  * rl8_masked_log_softmax_backward_f32, rl8_masked_categorical_sample_f32; rl8_attention_supports, rl8_attention_f32,
  * rl8_attention_backward_f32; rl8_feedforward_supports, rl8_feedforward_limits, rl8_feedforward_workspace_floats,
- * rl8_feedforward_f32, rl8_feedforward_backward_f32. */
+ * rl8_feedforward_f32, rl8_feedforward_backward_f32.  Widened under 107 without a bump (no entry added, none changed
+ * in signature, and a binding of either age works with a library of either age): rl8_lstm_split_state[_bound] take an
+ * h of any finite size -- they scale the call's planes by a power of two from max |h| and leave it in sixteen bytes
+ * behind the planes, which rl8_lstm_step_split_f32 reads behind h_planes and writes behind planes_out.  The planes'
+ * size has always been rl8_lstm_split_state_bytes(b), asked of the library at run time: it grew by those sixteen
+ * bytes, and inputs that were inside the old envelope (max |h| < 2) give the bits they gave. */
 #define RL8_ABI_VERSION 107
 int rl8_abi_version(char *arch, int arch_len);
 
@@ -877,12 +882,29 @@ int rl8_mlp_wgrad_split_strided_f32(const float *dz, int64_t dz_pitch, const flo
  * rl8_lstm_split_state: h [B][pitch] fp32 -> `planes` (rl8_lstm_split_state_bytes(B) bytes),
  *   the step kernel's A operand.  rl8_lstm_split_state_bound: the same, and max |h| over the rows as a float's bit
  *   pattern in *bound_out (what rl8_lstm_wgrad_f16_f32 takes as h_bound for the first timestep).
+ *   Envelope.  h may be a caller's own (torch.nn.LSTM takes any h_0), so both entries take max |h| over the FINITE
+ *   entries of the call while they make the planes of h * 2^14, and a second launch keeps those while that maximum is
+ *   below 2 (an LSTM's own outputs: the bits are those of ABI 107, and h is read once) or makes them again as those of
+ *   h * 2^(14 - e), max < 2^e, from 2 up to FLT_MAX.  The
+ *   factor, its inverse and the two maxima are the last sixteen bytes of `planes` (counted in
+ *   rl8_lstm_split_state_bytes).  One factor per call: an entry far below the call's maximum keeps the two
+ *   planes' 22 bits while it is above 2^(e - 17) and an absolute step of 2^(e - 38) below that (fp16's subnormal step
+ *   in the low plane; e = 0 under 2), so rows of 0.3 beside a row of 2^10 lose nothing, and entries under 2^(e - 39)
+ *   read as zero: 256 of them are less than 2^(e - 31) * max |W_hh| of a pre-activation.
+ *   A row holding an infinity or a NaN gives non-finite planes for that row only, and NaN h_t, c_t in that row
+ *   (torch does the same for a NaN; one infinity it lets saturate the row's gates instead); *bound_out then holds that entry's bit pattern.
  * rl8_lstm_step_split_f32: x row r at x + r * x_pitch (d_in floats); h_planes of h_{t-1};
  *   c_prev row r at c_prev + r * c_prev_pitch; writes h_t, c_t rows at the given pitches
  *   (floats) and, when `gates` is not NULL, the post-activation gates i, f, g, o as
  *   [4][256] per row at gates + r * gates_pitch (what rl8_lstm_backward_f32 reads); when
  *   `planes_out` is not NULL, h_t also as fp16 planes (rl8_lstm_split_state's layout) for the
  *   next timestep's call, so that only the first step of a sequence needs rl8_lstm_split_state.
+ *   `h_planes` must come from rl8_lstm_split_state[_bound] or from an earlier step's `planes_out`: the kernel takes
+ *   the inverse of the planes' factor from the sixteen bytes behind them, and writes 2^14, 2^-14 behind `planes_out`
+ *   (|h_t| < 1).  With that any finite h_0 is inside the envelope while max |h_0| * max |W_hh| < 2^126 (the two
+ *   inverses meet in one fp32 factor; past that pre-activations of 2^126 and more are formed, which torch saturates
+ *   and this kernel may turn into NaN); W_hh's own power of two holds down to a largest weight of 2^-96.  The factor
+ *   sits at the offset of b's planes: planes made for one b are not the planes of another b.
  *   d_in in {1, 2, 3, 5} (rl8_lstm_split_supports); other widths keep rl8_lstm_forward_f32.
  * ---------------------------------------------------------------------- */
 int rl8_lstm_split_supports(int d_in);
@@ -965,7 +987,17 @@ int rl8_lstm_rows_backward_f32(int64_t b, int l, const float *c0, const float *g
                                uint32_t *dg_bound_out, void *stream);
 /* The same with dL/dh_t of the output heads formed inside from heads_dout [b][l][4] (the gradient of the heads' outputs,
  * zero-padded to four per row-step) and heads_w [4][256] (their nn.Linear weights stacked, zero rows past their number):
- * the [b][l][256] array is neither written by rl8_linear_heads_backward_f32 (dh_out NULL) nor read here. */
+ * the [b][l][256] array is neither written by rl8_linear_heads_backward_f32 (dh_out NULL) nor read here.
+ * Limit.  This form runs the recurrent product on two fp16 planes of dG, scaled per sequence and step by a power of two
+ * that places a bound on that step's |dh| + |dc| at 2^6.  The forget gate's gradient dc * c_{t-1} * f (1 - f) carries
+ * the cell state, so it stays below fp16's top while |c_{t-1}| < 4 094 (2^6 * |c| / 4 < 65 504); cell states are
+ * carried across horizons and never clamped, so a caller has to know this.  Past the limit the plane overflows to
+ * infinity and every gate gradient of THAT sequence's earlier timesteps is NaN -- other sequences are untouched -- and
+ * *dg_bound_out is then not finite either (a NaN's bit pattern), so that rl8_lstm_wgrad_f16_f32 /
+ * rl8_mlp_wgrad_f16_strided_f32 cannot scale such gradients by a finite bound: the weight gradients come out
+ * non-finite, never finite and wrong.  The way out is the switch RL8_AMD_LSTM_BACKWARD_PLANES=bf16 (read here, on
+ * every call; see the list of LSTM switches at the head of this file): three exact bf16 planes, six plane products, the
+ * whole of fp32's range, at about the cost of rl8_lstm_rows_backward_f32. */
 int rl8_lstm_rows_backward_heads_f32(int64_t b, int l, const float *c0, const float *gates, const float *cs,
                                      const float *heads_dout, const float *heads_w, const void *packed, float *dgates,
                                      float *dc_scratch, uint32_t *dg_bound_out, void *stream);

@@ -389,10 +389,12 @@ __device__ __forceinline__ void lstm_rows_backward_body(const LrArgs &a, const v
   // accumulator register between the three places per chunk that fold into it: the vector registers are all taken
   float dg_max;
   asm volatile("v_accvgpr_write_b32 %0, 0" : "=a"(dg_max));
+  // (as bit patterns of non-negative floats: a NaN parked here, whose pattern is above every number's, stays -- fmaxf
+  // would return the other operand and the weight gradient would scale NaN gradients by a finite bound)
   auto fold_max = [&](float m) {
     float t;
     asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(t) : "a"(dg_max));
-    t = __builtin_fmaxf(t, m);
+    t = __uint_as_float(max(__float_as_uint(t), __float_as_uint(m)));  // (both are non-negative, or a positive NaN)
     asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(dg_max) : "v"(t));
   };
 
@@ -774,6 +776,11 @@ __device__ __forceinline__ void lstm_rows_backward_body(const LrArgs &a, const v
         if constexpr (F16) {
           // the accumulators carry this step's power of two times W_hh's; what the carries bound in the step that follows:
           // max |dh| over the sequence's 256 units (the other 128 sit in lane ^ 32), max |dc| of this step's chunks
+          // A dG past the planes' range has the planes (inf, NaN), and inf x w + NaN x w is NaN for EVERY w, zero included:
+          // all 256 dh of that sequence are NaN then, so one of them tells.  Every dG formed from such a carry is NaN,
+          // which the fmaxf of the three places that fold |dG| drops: the NaN enters the bound here (0 x dh is zero or
+          // NaN), so that max |dG| is not finite once a plane has overflowed.  (A NaN that comes in with the caller's
+          // gates, cell states or dOut is still dropped by those fmaxf: the weight gradient is NaN from the NaN dG itself.)
           float m = 0.0f;
 #pragma unroll
           for (int cc = 0; cc < kLrChunks; ++cc)
@@ -783,6 +790,7 @@ __device__ __forceinline__ void lstm_rows_backward_body(const LrArgs &a, const v
               dhe[e][cc] = v;
               m = __builtin_fmaxf(m, __builtin_fabsf(v));
             }
+          fold_max(__builtin_fabsf(dhe[0][0] * 0.0f));
           const auto sm = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
           cmax = __builtin_fmaxf(__uint_as_float(sm[0]), __uint_as_float(sm[1]));
           const auto se = __builtin_amdgcn_permlane32_swap(__float_as_uint(emax), __float_as_uint(emax), false, false);
@@ -809,7 +817,8 @@ __device__ __forceinline__ void lstm_rows_backward_body(const LrArgs &a, const v
     float t;
     asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(t) : "a"(dg_max));
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t = __builtin_fmaxf(t, __shfl_down(t, off, 64));
+    for (int off = 32; off > 0; off >>= 1)
+      t = __uint_as_float(max(__float_as_uint(t), __float_as_uint(__shfl_down(t, off, 64))));  // (a NaN's pattern is the largest)
     if (lane == 0) atomicMax(a.dg_bound, __float_as_uint(t));
   }
 #ifdef RL8_LR_STAMP

@@ -6,7 +6,11 @@
 // products: mlp_f16_kernels.hip), which costs nothing here: |h| < 1 by construction
 // (h = o * tanh(c)), so the state's planes are those of h * 2^14 with no per-row factor, and
 // W_hh gets one power of two for the matrix (behind the planes, like the towers' W2); the
-// inverse of both meets the accumulators in the epilogue's first fma.
+// inverse of both meets the accumulators in the epilogue's first fma.  A caller's h_0 is not
+// the LSTM's own output and may be of any size: rl8_lstm_split_state takes max |h_0| over the
+// finite entries while it splits and, from 2 up, makes the call's planes again, scaled by 2^(14 - e), max < 2^e; the
+// factor and its inverse sit in sixteen bytes behind the planes, where the step kernel reads
+// the inverse (and leaves 2^14, 2^-14 behind the planes of the h_t it writes).
 // lstm_kernels.hip runs the same step on fp32 MFMAs (64 cycles per 32x32x2 block; 108-129
 // TFLOP/s); this one runs 5.3x fewer matrix-pipe cycles per product.
 //
@@ -59,7 +63,16 @@ __device__ __forceinline__ void ls_planes(const float (&v)[8], float scale, u32x
     planes[1][e >> 1] = lo;
   }
 }
-constexpr float kLsStateScale = 16384.0f;  // 2^14: |h| < 1
+constexpr float kLsStateScale = 16384.0f;  // 2^14: |h| < 1 (the LSTM's own outputs; a caller's h_0: ls_state_exponent)
+// The tail behind a buffer of state planes: {factor the planes were scaled by, its inverse, bit pattern of the largest
+// finite |h|, bit pattern of the largest |h| (a NaN's is above every number's)}.
+constexpr int kLsStateTail = 16;
+// max |h| < 2^e.  0 while the maximum is below 2: such states keep 2^14 (the bits they always had; 2 x 2^14 is far from
+// fp16's top), larger ones get 2^(14 - e) >= 2^-114.
+__device__ __forceinline__ int ls_state_exponent(uint32_t finite_max_bits) {
+  const int e = __builtin_amdgcn_frexp_expf(__uint_as_float(finite_max_bits));
+  return e < 2 ? 0 : e;
+}
 
 // max |W_hh| -> {2^k, 2^-k} with max * 2^k < 2^14, behind the planes (one workgroup).
 __global__ __launch_bounds__(1024) void lstm_whh_scale_kernel(const float *__restrict__ w_hh, float *__restrict__ tail) {
@@ -81,7 +94,10 @@ __global__ __launch_bounds__(1024) void lstm_whh_scale_kernel(const float *__res
     __syncthreads();
   }
   if (tid == 0) {
-    const int e = f16_bound_exponent(red[0]);
+    // (down to 2^-96, not f16_bound_exponent's 2^-80: beside an h_0 of 1e30 the weights that keep the gates open are
+    // of 1e-32, and their planes want the whole of fp16's range too; 2^-110 x the state's 2^-14 is still normal)
+    int e = __builtin_amdgcn_frexp_expf(red[0]);
+    e = e < -96 ? -96 : e;
     tail[0] = __builtin_amdgcn_ldexpf(1.0f, kF16Top - e);
     tail[1] = __builtin_amdgcn_ldexpf(1.0f, e - kF16Top);
     tail[2] = tail[3] = 0.0f;
@@ -120,18 +136,38 @@ __global__ __launch_bounds__(kBlock) void lstm_pack_split_kernel(const float *__
 
 // h [B][pitch] fp32 -> planes [tile][k-step][plane][k-half][row] x 16 B (rows past B are
 // zero): the A operand of rl8_lstm_step_split_f32, one contiguous 8 KiB per tile and
-// k-step.  Thread = (row, k-half); sixteen fragments each.  `bound_out` (or null): max |h| over the rows, as the bit
-// pattern of the float (atomicMax of non-negative floats as integers), for the fp16-plane weight gradient that reads
-// the same h_0 in the backward -- a separate abs + amax over 2^19 rows cost 0.33 ms per pass.
+// k-step.  Thread = (row, k-half); sixteen fragments each.  Two launches of this kernel make a split:
+//   RESCALE = false  the planes of h * 2^14, and max |h| over the rows as bit patterns (atomicMax of non-negative floats
+//                    as integers) into the tail, zero on entry: the largest FINITE entry (what decides the factor: an
+//                    infinity or a NaN in one row must not cost the others their bits) and the largest of all;
+//   RESCALE = true   workgroup 0 leaves the factor and its inverse in the tail and the largest of all in `bound_out`
+//                    (or null: the fp16-plane weight gradient reads the same h_0 in the backward); below 2 that is all
+//                    -- an LSTM's own outputs cost this launch and no traffic -- else the planes are made again, of
+//                    h * 2^(14 - e).  (A pass for the maximum in front of ONE split read h twice on every call: 0.1 ms
+//                    per 2^17 rows of the recurrent bench's training passes.)
+template <bool RESCALE>
 __global__ __launch_bounds__(kBlock) void lstm_split_state_kernel(const float *__restrict__ h, int64_t pitch,
                                                                   int64_t b, uint32_t *__restrict__ planes_out,
                                                                   uint32_t *__restrict__ bound_out) {
-  __shared__ uint32_t block_max;
-  if (threadIdx.x == 0) block_max = 0;
-  __syncthreads();
-  uint32_t mx = 0;
+  __shared__ uint32_t block_max[2];
   const int rr = threadIdx.x & 127, kh = threadIdx.x >> 7;
   const int64_t tiles = (b + kSplitRows - 1) / kSplitRows;
+  uint32_t *tail = planes_out + tiles * (kLsATileBytes / 4);
+  float scale = kLsStateScale;
+  if constexpr (RESCALE) {
+    const int e = ls_state_exponent(tail[2]);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      reinterpret_cast<float *>(tail)[0] = __builtin_amdgcn_ldexpf(1.0f, kF16Top - e);
+      reinterpret_cast<float *>(tail)[1] = __builtin_amdgcn_ldexpf(1.0f, e - kF16Top);
+      if (bound_out) *bound_out = tail[3];
+    }
+    if (e == 0) return;  // (uniform)
+    scale = __builtin_amdgcn_ldexpf(1.0f, kF16Top - e);
+  } else {
+    if (threadIdx.x < 2) block_max[threadIdx.x] = 0;
+    __syncthreads();
+  }
+  uint32_t finite = 0, all = 0;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t row = tile * kSplitRows + rr;
     const float *src = h + row * pitch + 8 * kh;
@@ -146,18 +182,28 @@ __global__ __launch_bounds__(kBlock) void lstm_split_state_kernel(const float *_
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = 0.0f;
       }
+      if constexpr (!RESCALE) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) mx = max(mx, __float_as_uint(v[e]) & 0x7fffffffu);
+        for (int e = 0; e < 8; ++e) {
+          const uint32_t bits = __float_as_uint(v[e]) & 0x7fffffffu;
+          all = max(all, bits);
+          finite = max(finite, bits < 0x7f800000u ? bits : 0u);
+        }
+      }
       u32x4 planes[2];
-      ls_planes(v, kLsStateScale, planes);
+      ls_planes(v, scale, planes);
 #pragma unroll
       for (int p = 0; p < 2; ++p) dst[s * (kLsAChunkBytes / 16) + p * 256] = planes[p];
     }
   }
-  if (bound_out) {  // (uniform)
-    atomicMax(&block_max, mx);
+  if constexpr (!RESCALE) {
+    atomicMax(&block_max[0], finite);
+    atomicMax(&block_max[1], all);
     __syncthreads();
-    if (threadIdx.x == 0) atomicMax(bound_out, block_max);
+    if (threadIdx.x == 0) {
+      atomicMax(tail + 2, block_max[0]);
+      atomicMax(tail + 3, block_max[1]);
+    }
   }
 }
 
@@ -196,10 +242,14 @@ __global__ __launch_bounds__(kBlock, 2) void lstm_step_split_kernel(
   const unsigned b_read = lds0 + kLsABytes + (4 * wc * 2) * 1024 + lane * 16;
   const __amdgpu_buffer_rsrc_t wrsrc =
       buffer_rsrc(static_cast<const unsigned char *>(w_planes) + ub * kLsWBlockBytes, kLsWBlockBytes);
-  // undoes the operand scaling: 2^-14 of the state planes times W_hh's inverse power of two
-  const float unscale = reinterpret_cast<const float *>(static_cast<const unsigned char *>(w_planes) + kLsPackedBytes)[1] *
-                        (1.0f / kLsStateScale);
   const int64_t tiles = (b + kSplitRows - 1) / kSplitRows;
+  // undoes the operand scaling: the inverse behind the state planes (2^-14 for an LSTM's own outputs) times W_hh's
+  const float unscale = reinterpret_cast<const float *>(static_cast<const unsigned char *>(w_planes) + kLsPackedBytes)[1] *
+                        reinterpret_cast<const float *>(static_cast<const unsigned char *>(a_planes) + tiles * kLsATileBytes)[1];
+  if (args.planes_out != nullptr && blockIdx.x == 0 && tid == 0) {  // h_t is this LSTM's own: |h| < 1
+    const u32x4 own = {__float_as_uint(kLsStateScale), __float_as_uint(1.0f / kLsStateScale), 0x3f800000u, 0x3f800000u};
+    *reinterpret_cast<u32x4 *>(static_cast<unsigned char *>(args.planes_out) + tiles * kLsATileBytes) = own;
+  }
   const int64_t tile_stride = gridDim.x / kLsBlocks;
 
   // this lane's unit: gate rows of [w_ih | bias]
@@ -440,7 +490,10 @@ RL8_API int rl8_lstm_split_supports(int d_in) { return d_in >= 1 && d_in <= kLsI
 RL8_API int64_t rl8_lstm_split_packed_bytes(void) { return kLsPackedBytes + 16; }
 RL8_API int64_t rl8_lstm_split_wb_floats(void) { return 4 * kHidden * kLsInCols; }
 // bytes of the state planes for b rows (whole 128-row tiles)
-RL8_API int64_t rl8_lstm_split_state_bytes(int64_t b) { return ((b + kSplitRows - 1) / kSplitRows) * (int64_t)kLsATileBytes; }
+// (+ the tail: the planes' power of two, its inverse and the two maxima it came from)
+RL8_API int64_t rl8_lstm_split_state_bytes(int64_t b) {
+  return ((b + kSplitRows - 1) / kSplitRows) * (int64_t)kLsATileBytes + kLsStateTail;
+}
 
 RL8_API int rl8_lstm_pack_split(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, int d_in,
                                 void *packed, float *wb, void *stream) {
@@ -461,8 +514,10 @@ static int split_state(const float *h, int64_t pitch, int64_t b, void *planes, u
   if (!aligned16(h) || !aligned16(planes) || (pitch & 3)) return RL8_EALIGN;
   const int64_t tiles = (b + kSplitRows - 1) / kSplitRows;
   const int grid = (int)(tiles < kMaxGrid ? tiles : kMaxGrid);
-  if (bound_out && hipMemsetAsync(bound_out, 0, 4, (hipStream_t)stream) != hipSuccess) return launch_status();
-  lstm_split_state_kernel<<<grid, kBlock, 0, (hipStream_t)stream>>>(h, pitch, b, static_cast<uint32_t *>(planes), bound_out);
+  uint32_t *tail = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(planes) + tiles * kLsATileBytes);
+  if (hipMemsetAsync(tail, 0, kLsStateTail, (hipStream_t)stream) != hipSuccess) return launch_status();
+  lstm_split_state_kernel<false><<<grid, kBlock, 0, (hipStream_t)stream>>>(h, pitch, b, static_cast<uint32_t *>(planes), nullptr);
+  lstm_split_state_kernel<true><<<grid, kBlock, 0, (hipStream_t)stream>>>(h, pitch, b, static_cast<uint32_t *>(planes), bound_out);
   return launch_status();
 }
 

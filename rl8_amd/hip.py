@@ -2334,7 +2334,9 @@ def lstm_state_planes(rows: int, device: torch.device | str, copies: int = 1) ->
 def lstm_split_state(h: torch.Tensor, *, out: None | torch.Tensor = None,
                      bound_out: None | torch.Tensor = None) -> torch.Tensor:
     """``h`` [B, 256] -> its fp16 planes in the step kernel's operand order (``out`` or a fresh buffer);
-    ``bound_out`` (one float32 element) receives max |h|."""
+    ``bound_out`` (one float32 element) receives max |h|. ``h`` may be of any finite size (a caller's ``h0``): from
+    max |h| = 2 up the planes carry a power of two of their own, kept in the buffer's last sixteen bytes, where the
+    step kernel reads it (include/rl8_amd.h has the envelope)."""
     h = _dense(h, torch.float32, "h")
     b, dev, lib = h.shape[0], h.device, load()
     if h.ndim != 2 or h.shape[1] != LSTM_HIDDEN:
