@@ -766,7 +766,9 @@ int rl8_mlp_wgrad_fused_pair_f32(const float *h2, const float *dout, const float
  * (two plane products per 16 rows; the column bounds come from one pass over dout and x in front of the first
  * segment and live in the 256 bytes behind the slabs of `workspace`); RL8_WGRAD_GATE_PLANES=bf16 in the environment
  * selects the three exact bf16 planes of round 2.  dW2 stays within the fp32 kernels' error against the tensor's
- * largest entry; an entry made only of rows 2^17 below its column's bound keeps ~1e-5 of its own size. */
+ * largest entry; an entry made only of rows 2^17 below its column's bound keeps ~1e-5 of its own size.
+ * RL8_WGRAD_PHASES=inphase (read once per process) gives every wave of the fp16-plane kernel the one phase order it
+ * had before half of them were set to produce first (d_in <= 2): same bits, for A/B timing and the equality test. */
 int rl8_mlp_wgrad_gate_bits_f32(const uint32_t *gate2, const float *dout, const float *x, const float *w1,
                                 const float *b1, const float *w2, const float *b2, const float *w3,
                                 int64_t m, int d_in, int n_out, float *workspace, float *dw2_out,

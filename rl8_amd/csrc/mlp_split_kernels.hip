@@ -78,6 +78,8 @@ struct WgradFusedArgs {
   // equals `guard_want` -- both generations are launched, one of them runs, no host round trip.
   const uint32_t *guard = nullptr;
   int guard_want = 0;
+  // mlp_wgrad_gate16_kernel: the bit of the wave number whose waves run the late phase order (wgrad_late_bit(); 0: none)
+  int late_bit = 0;
 };
 
 // Words of the 64 behind the slabs of the weight-gradient workspace: [0 .. 3] max |dOut column|, [4 .. 11] max |x column|
@@ -864,11 +866,46 @@ constexpr int kW16Threads = 1024;
 constexpr int kW16StageBytes = 3 * 2 * kHidden * 16;  // gate plane | hi plane | lo plane, each [sample half][column] x 16 B
 constexpr int kW16Stages = 4;
 
-template <int DIN, bool PAIR>
-__global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_gate16_kernel(
+// Phase order of mlp_wgrad_gate16_kernel's waves.  Between two barriers a wave consumes two stages of the ring and
+// produces the two others: disjoint stages, so either may come first.  With one order for all, the four waves of a SIMD
+// (w, w + 4, w + 8, w + 12) queue their products on the one matrix pipe together and then do their producer arithmetic
+// together while the pipe stands empty.  So two of the four run "late": produce, then consume.  Each wave's products into
+// an accumulator, its running sums, the LDS bytes and the barriers are what they were: the same bits.
+// The late waves are those with bit 2 of the wave number set (4..7, 12..15): -6.2 % per call against -4.9 % for waves
+// 8..15 (one output, 2^23 rows), both with the products' raised priority kept for the late waves too (without it:
+// -3.2 %); profiles/wgrad_phases_ab.txt.  The general and the LSTM kernel keep one order: see DESIGN section 9.
+//   RL8_WGRAD_PHASES=inphase (read once per process): no wave late, the kernel of before -- for A/B runs, one process
+//   per value, and for tests/test_wgrad_phases_gpu.py.
+static int wgrad_late_bit() {
+  static const int bit = [] {
+    const char *v = getenv("RL8_WGRAD_PHASES");
+    return v && v[0] == 'i' ? 0 : 4;
+  }();
+  return bit;
+}
+
+// The running kernel's argument block, read again where it is called: T lists the kernel's parameters in their order
+// (the block is laid out as that struct is).  The empty asm hides where the pointer came from, so the loads stay behind
+// it instead of joining the ones at the kernel's entry; they are scalar loads from constant memory like those.
+struct WgradGate16Args {  // mlp_wgrad_gate16_kernel's parameter list
+  const float *x, *w1, *b1;
+  int64_t m;
+  float *slabs;
+  WgradFusedArgs fused;
+};
+template <class T>
+__device__ __forceinline__ const __attribute__((address_space(4))) T *reread_kernel_args() {
+  auto *p = (const __attribute__((address_space(4))) T *)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
+// (LATE: this wave's phase order.  The kernel below calls one of the two instantiations per wave, whole: prologue, loop
+// and epilogue -- the two loops alone, joined in front of one epilogue, cost registers the budget does not have.)
+template <int DIN, bool PAIR, bool LATE>
+__device__ __forceinline__ void mlp_wgrad_gate16_waves(
     const float *__restrict__ x, const float *__restrict__ w1, const float *__restrict__ b1, int64_t m,
-    float *__restrict__ slabs, WgradFusedArgs fused) {
-  if (guard_says_leave(fused)) return;
+    float *__restrict__ slabs, const WgradFusedArgs &fused) {
   constexpr int kIn = DIN;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float *inv_scales = reinterpret_cast<float *>(smem + kW16Stages * kW16StageBytes);  // [256]
@@ -1034,30 +1071,43 @@ __global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_gate16_kernel(
   land(ra);
   __syncthreads();
   const int steps = (mine + 3) & ~3;  // (a multiple of four: chunks past the end are all zero)
+  // A half-step in this wave's phase order (see RL8_WGRAD_PHASES above).  The late order is the same calls on the same
+  // stages and sets: issue(r) stays behind produce(r, ...), which reads what it overwrites, and land() of the other set
+  // stays behind that produce() -- and comes behind consume(), whose reads are waited for: it waits for scalar loads only.
+  auto step = [&](int read, const Raw &r, int write) {
+    if constexpr (LATE) {
+      produce(r, write);
+      asm volatile("" ::: "memory");  // (consume's reads are not moved up into produce(): registers)
+      consume(read);
+    } else {
+      consume(read);
+      produce(r, write);
+    }
+  };
 #pragma unroll 1
   for (int n = 0; n < steps; n += 4) {
     // (one barrier per TWO steps: stages 2, 3 are written while 0, 1 are read, and the other way round)
     issue(rb);  // chunk n + 3
-    consume(0);
-    produce(ra, 2);
+    step(0, ra, 2);
     land(rb);
     issue(ra);  // chunk n + 4
-    consume(1);
-    produce(rb, 3);
+    step(1, rb, 3);
     land(ra);
     __syncthreads();
     issue(rb);  // chunk n + 5
-    consume(2);
-    produce(ra, 0);
+    step(2, ra, 0);
     land(rb);
     issue(ra);  // chunk n + 6
-    consume(3);
-    produce(rb, 1);
+    step(3, rb, 1);
     land(ra);
     __syncthreads();
   }
 
-  float *slab = slabs + (int64_t)blockIdx.x * kHidden * kHidden;
+  // What only the epilogue reads -- slabs, the partial rows, w3, b2 -- it reads from the kernel's argument block again,
+  // here, through a pointer the compiler cannot trace back: with two copies of the body it otherwise loads them once in
+  // front of both and holds eleven scalar registers across the loops, which the budget does not have.
+  const auto *args = reread_kernel_args<WgradGate16Args>();
+  float *slab = args->slabs + (int64_t)blockIdx.x * kHidden * kHidden;
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -1075,21 +1125,36 @@ __global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_gate16_kernel(
   __syncthreads();
   red[q * kHidden + col] = gsum;
   __syncthreads();
-  float *row = fused.partials + (int64_t)blockIdx.x * fused.partial_stride;
+  float *row = args->fused.partials + (int64_t)blockIdx.x * args->fused.partial_stride;
   constexpr int kOut = PAIR ? 2 : 1;
   constexpr int off_db2 = kHidden * kIn + kHidden, off_dw3 = off_db2 + kHidden, off_db3 = off_dw3 + kOut * kHidden;
-  const bool more = fused.accumulate != 0;
+  const bool more = args->fused.accumulate != 0;
   if (q == 0) {
     const float total = ((red[col] + red[kHidden + col]) + red[2 * kHidden + col]) + red[3 * kHidden + col];
-    const float w3e = PAIR ? fused.w3[col] - fused.w3[kHidden + col] : fused.w3[col];
-    const float sum_b2 = total * w3e, sum_w3 = total * fused.b2[col];
+    const float w3e = PAIR ? args->fused.w3[col] - args->fused.w3[kHidden + col] : args->fused.w3[col];
+    const float sum_b2 = total * w3e, sum_w3 = total * args->fused.b2[col];
     row[off_db2 + col] = more ? row[off_db2 + col] + sum_b2 : sum_b2;
     row[off_dw3 + col] = more ? row[off_dw3 + col] + sum_w3 : sum_w3;
     if constexpr (PAIR) row[off_dw3 + kHidden + col] = more ? row[off_dw3 + kHidden + col] - sum_w3 : -sum_w3;
     if (col < kOut && !more) row[off_db3 + col] = 0.0f;
   }
-  if (!more && (int)blockIdx.x >= fused.other_rows)
+  if (!more && (int)blockIdx.x >= args->fused.other_rows)
     for (int idx = tid; idx < kHidden * kIn + kHidden; idx += kW16Threads) row[idx] = 0.0f;
+}
+
+template <int DIN, bool PAIR>
+__global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_gate16_kernel(
+    const float *__restrict__ x, const float *__restrict__ w1, const float *__restrict__ b1, int64_t m,
+    float *__restrict__ slabs, WgradFusedArgs fused) {
+  if (guard_says_leave(fused)) return;
+  // (wave-uniform, a scalar branch; both sides hold the same barriers.  d_in >= 3 keeps the one order: these widths sit
+  // at the 128 vector and ~100 scalar registers of four waves per SIMD already, and the second copy of the body tips one
+  // or the other of them into scratch -- d_in 3 and 5 to 7 as built; 4 fits by a register, which is no margin)
+  if constexpr (DIN <= 2) {
+    if ((__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) & fused.late_bit) != 0)
+      return mlp_wgrad_gate16_waves<DIN, PAIR, true>(x, w1, b1, m, slabs, fused);
+  }
+  mlp_wgrad_gate16_waves<DIN, PAIR, false>(x, w1, b1, m, slabs, fused);
 }
 
 template <int DIN, bool PAIR>
@@ -1098,6 +1163,7 @@ static int launch_wgrad_gate16(int grid, hipStream_t s, const float *x, const fl
   static LdsOptIn opt;
   if (m > kWgradSegmentRows) return RL8_ESIZE;  // (the kernel's 32-bit byte offsets)
   if (const int e = allow_dynamic_lds(opt, reinterpret_cast<const void *>(&mlp_wgrad_gate16_kernel<DIN, PAIR>), 160 * 1024)) return e;
+  fused.late_bit = wgrad_late_bit();
   mlp_wgrad_gate16_kernel<DIN, PAIR><<<grid, kW16Threads, kW16Stages * kW16StageBytes + kHidden * 4, s>>>(x, w1, b1, m, slabs, fused);
   return launch_status();
 }
