@@ -26,7 +26,7 @@ static_assert(kMaxGrid <= RL8_MAX_PARTIALS, "partials must fit the scratch");
 // Dynamic-LDS opt-in of a kernel on the device that is current NOW: once per device and kernel (the attribute belongs to
 // the device's copy of the function), safe to race from several host threads, and the error comes back instead of
 // being dropped (a process-wide `static bool` set the attribute on the first device only and launched on
-// the others without it).  One `static LdsOptIn` per call site and kernel.
+// the others without it).  One `static LdsOptIn` per kernel: allow_dynamic_lds<&kernel>() below keeps it.
 struct LdsOptIn {
   std::atomic<unsigned long long> devices{0};
 };
@@ -51,6 +51,13 @@ inline int allow_dynamic_lds(LdsOptIn &state, const void *kernel, int bytes) {
   }
   state.devices.fetch_or(bit, std::memory_order_release);
   return 0;
+}
+// The form to use in front of a launch: `if (const int e = allow_dynamic_lds<&kernel<...>>()) return e;`.  Keyed on the
+// kernel, so every kernel -- every instantiation of a kernel template -- has its own state.
+template <auto Kernel>
+inline int allow_dynamic_lds(int bytes = 160 * 1024) {
+  static LdsOptIn state;
+  return allow_dynamic_lds(state, reinterpret_cast<const void *>(Kernel), bytes);
 }
 
 struct SumOp {

@@ -501,10 +501,8 @@ RL8_API int rl8_gae_scan_f32(float *rewards, const float *values, float *adv_out
   hipStream_t s = (hipStream_t)stream;
   double *partials = (double *)scratch;
   if (layout == 0) {
-    static LdsOptIn lds_attr_set_0;
-    if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&gae_scan_env_major_kernel<true>), 160 * 1024)) return e_lds_attr_set_0;
-    static LdsOptIn lds_attr_set_1;
-    if (const int e_lds_attr_set_1 = allow_dynamic_lds(lds_attr_set_1, reinterpret_cast<const void *>(&gae_scan_env_major_kernel<false>), 160 * 1024)) return e_lds_attr_set_1;
+    if (const int e = allow_dynamic_lds<&gae_scan_env_major_kernel<true>>()) return e;
+    if (const int e = allow_dynamic_lds<&gae_scan_env_major_kernel<false>>()) return e;
   }
   switch (p.route) {
     case RL8_GAE_TIME_VEC4:
@@ -518,8 +516,7 @@ RL8_API int rl8_gae_scan_f32(float *rewards, const float *values, float *adv_out
           write_scaled_rewards, partials, moments_out);
       break;
     case RL8_GAE_ENV_PIPELINED: {
-      static LdsOptIn lds_attr9_0;
-      if (const int e_lds_attr9_0 = allow_dynamic_lds(lds_attr9_0, reinterpret_cast<const void *>(&gae_scan_env_major_pipelined_kernel<9>), 160 * 1024)) return e_lds_attr9_0;
+      if (const int e = allow_dynamic_lds<&gae_scan_env_major_pipelined_kernel<9>>()) return e;
       gae_scan_env_major_pipelined_kernel<9><<<p.grid, p.envs_per_block, (size_t)p.lds_bytes, s>>>(
           rewards, values, adv_out, ret_out, n, h, gamma, gamma_lambda, reward_denominator, write_scaled_rewards, partials,
           moments_out);

@@ -399,9 +399,8 @@ int launch_backward(hipStream_t s, int64_t b, int l, const float *c0, const floa
                     const float *cs, const float *dhs, float *dz) {
   constexpr size_t bytes = sizeof(float) * Geo<H>::RB * Geo<H>::LD;
   static_assert(bytes * Geo<H>::kWgPerCU <= 160 * 1024, "backward LDS");
-  static LdsOptIn opt_in;
-  auto *kernel = &lstm_narrow_backward_kernel<H>;
-  if (const int e = allow_dynamic_lds(opt_in, reinterpret_cast<const void *>(kernel), (int)bytes)) return e;
+  constexpr auto *kernel = &lstm_narrow_backward_kernel<H>;
+  if (const int e = allow_dynamic_lds<kernel>((int)bytes)) return e;
   kernel<<<tile_grid<H>(b, Geo<H>::RB), Geo<H>::kThreads, bytes, s>>>(b, l, c0, w_hh, gates, cs, dhs, dz);
   return launch_status();
 }
@@ -410,9 +409,8 @@ template <int H>
 int launch_backward_heads(hipStream_t s, int64_t b, int l, const float *c0, const float *w_hh, const float *gates,
                           const float *cs, const float *heads_dout, const float *heads_w, float *dz) {
   constexpr size_t bytes = sizeof(float) * Geo<H>::RB * Geo<H>::LD;
-  static LdsOptIn opt_in;
-  auto *kernel = &lstm_narrow_backward_heads_kernel<H>;
-  if (const int e = allow_dynamic_lds(opt_in, reinterpret_cast<const void *>(kernel), (int)bytes)) return e;
+  constexpr auto *kernel = &lstm_narrow_backward_heads_kernel<H>;
+  if (const int e = allow_dynamic_lds<kernel>((int)bytes)) return e;
   kernel<<<tile_grid<H>(b, Geo<H>::RB), Geo<H>::kThreads, bytes, s>>>(b, l, c0, w_hh, gates, cs, heads_dout, heads_w,
                                                                       dz);
   return launch_status();
@@ -844,9 +842,8 @@ int launch_stack_backward(hipStream_t s, const float *x, int64_t b, int l, const
   if (const int st = launch_backward<H>(s, b, l, c0, w_hh, gates, cs, dhs, dz)) return st;
   constexpr size_t bytes = sizeof(float) * kStackRows * Geo<H>::LD;
   static_assert(bytes * Geo<H>::kWgPerCU <= 160 * 1024, "dx LDS");
-  static LdsOptIn opt_in;
-  auto *kernel = &lstm_narrow_stack_dx_kernel<H>;
-  if (const int e = allow_dynamic_lds(opt_in, reinterpret_cast<const void *>(kernel), (int)bytes)) return e;
+  constexpr auto *kernel = &lstm_narrow_stack_dx_kernel<H>;
+  if (const int e = allow_dynamic_lds<kernel>((int)bytes)) return e;
   kernel<<<stack_grid<H>(b * l), Geo<H>::kThreads, bytes, s>>>(b * l, w_ih, dz, dx);
   if (const int st = launch_status()) return st;
   int64_t per = 0;

@@ -918,10 +918,8 @@ static int rows_backward(int64_t b, int l, const float *c0, const float *gates, 
   if (!aligned16(packed) || !aligned16(c0) || !aligned16(gates) || !aligned16(cs) || !aligned16(dhs) || !aligned16(dgates) ||
       !aligned16(dc_scratch) || !aligned16(heads_w))
     return RL8_EALIGN;
-  static LdsOptIn lds_attr_set_0;
-  if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&lstm_rows_backward_kernel), kLrLdsBytes)) return e_lds_attr_set_0;
-  static LdsOptIn lds_attr_set_1;
-  if (const int e_lds_attr_set_1 = allow_dynamic_lds(lds_attr_set_1, reinterpret_cast<const void *>(&lstm_rows_backward_heads_kernel), kLrLdsBytes)) return e_lds_attr_set_1;
+  if (const int e = allow_dynamic_lds<&lstm_rows_backward_kernel>(kLrLdsBytes)) return e;
+  if (const int e = allow_dynamic_lds<&lstm_rows_backward_heads_kernel>(kLrLdsBytes)) return e;
   const int64_t tiles = (b + kLrRows - 1) / kLrRows;
   const int grid = (int)(tiles < kCUs ? tiles : kCUs);
   unsigned long long *stamps = nullptr;
@@ -934,8 +932,7 @@ static int rows_backward(int64_t b, int l, const float *c0, const float *gates, 
   const char *planes = getenv("RL8_AMD_LSTM_BACKWARD_PLANES");
   const bool f16 = heads_w != nullptr && !(planes && planes[0] == 'b');
   if (f16) {
-    static LdsOptIn lds_attr_set_2;
-    if (const int e = allow_dynamic_lds(lds_attr_set_2, reinterpret_cast<const void *>(&lstm_rows_backward_heads16_kernel), lr_lds_bytes(true))) return e;
+    if (const int e = allow_dynamic_lds<&lstm_rows_backward_heads16_kernel>(lr_lds_bytes(true))) return e;
     lstm_rows_backward_heads16_kernel<<<grid, kBlock, lr_lds_bytes(true), (hipStream_t)stream>>>(args, packed);
   } else if (heads_w) lstm_rows_backward_heads_kernel<<<grid, kBlock, kLrLdsBytes, (hipStream_t)stream>>>(args, packed);
   else lstm_rows_backward_kernel<<<grid, kBlock, kLrLdsBytes, (hipStream_t)stream>>>(args, packed);

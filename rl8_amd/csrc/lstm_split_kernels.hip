@@ -534,14 +534,13 @@ RL8_API int rl8_lstm_split_state_bound(const float *h, int64_t pitch, int64_t b,
 template <int DIN>
 static int launch_lstm_step(int grid, hipStream_t s, const void *a_planes, const void *w_planes, const float *wb, int64_t b,
                             const LstmStepArgs &args) {
-  static LdsOptIn lds_attr_set_0;
-  if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&lstm_step_split_kernel<DIN, true>), 160 * 1024)) return e_lds_attr_set_0;
-  static LdsOptIn lds_attr_set_1;
-  if (const int e_lds_attr_set_1 = allow_dynamic_lds(lds_attr_set_1, reinterpret_cast<const void *>(&lstm_step_split_kernel<DIN, false>), 160 * 1024)) return e_lds_attr_set_1;
-  if (args.gates)
+  if (args.gates) {
+    if (const int e = allow_dynamic_lds<&lstm_step_split_kernel<DIN, true>>()) return e;
     lstm_step_split_kernel<DIN, true><<<grid, kBlock, lstm_step_lds_bytes(), s>>>(a_planes, w_planes, wb, b, args);
-  else
+  } else {
+    if (const int e = allow_dynamic_lds<&lstm_step_split_kernel<DIN, false>>()) return e;
     lstm_step_split_kernel<DIN, false><<<grid, kBlock, lstm_step_lds_bytes(), s>>>(a_planes, w_planes, wb, b, args);
+  }
   return launch_status();
 }
 

@@ -18,6 +18,7 @@
 // What fp16 costs is RANGE (5 exponent bits): hence the power-of-two scaling per activation
 // row and per weight matrix described at set_row_scale().
 #include "split_tile.hip.h"
+#include "tower_launch.hip.h"
 
 namespace rl8 {
 
@@ -454,8 +455,7 @@ template <int DIN, int NOUT>
 static int launch_backward_f16(int grid, hipStream_t s, const float *x, const float *w1, const float *b1, const float *dout,
                                int64_t m, const void *w2ts, const float *w3, float *partials, int stride, int head_rows,
                                const uint32_t *gate2) {
-  static LdsOptIn lds_attr_set_0;
-  if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&mlp_tower_backward_f16_kernel<DIN, NOUT>), 160 * 1024)) return e_lds_attr_set_0;
+  if (const int e = allow_dynamic_lds<&mlp_tower_backward_f16_kernel<DIN, NOUT>>()) return e;
   mlp_tower_backward_f16_kernel<DIN, NOUT><<<grid, kBlock, f16_backward_lds_bytes(DIN), s>>>(
       x, w1, b1, dout, m, w2ts, w3, partials, stride, head_rows, gate2);
   return launch_status();
@@ -476,22 +476,6 @@ RL8_API int rl8_mlp_pack_w2_f16(const float *w2, int transposed, void *packed, v
   return launch_status();
 }
 
-namespace rl8 {
-int mlp_rows_backward_gate_dispatch(int grid, hipStream_t s, const float *x, const float *w1, const float *b1, const float *dout,
-                                    int64_t m, int d_in, const void *w2ts, int n_out, float *partials, int stride, int head_rows,
-                                    const uint32_t *gate2);
-int mlp_rows_backward_general_dispatch(int grid, hipStream_t s, const float *x, const float *w1, const float *b1, const float *dout,
-                                       int64_t m, int d_in, const void *w2ts, const float *w3, int n_out, float *partials, int stride,
-                                       int head_rows, const uint32_t *gate2);
-int mlp_rows_forward_dispatch(hipStream_t s, const float *x, int64_t m, int d_in, const float *w1, const float *b1,
-                              const void *w2s, const float *b2, const float *w3, const float *b3, int n_out, float *out,
-                              float *h1, float *h2, uint32_t *gate);
-}
-
-namespace rl8 {
-int rows_in_class(int d_in);
-int rows_out_class(int n_out);
-}
 RL8_API int rl8_mlp_forward_f16_supports(int d_in, int n_out) {
   // (class 16 x output class 8 has no variant: its constants and the h2 scratch do not fit beside three chunks of W2)
   return d_in >= 1 && rows_in_class(d_in) != 0 && rows_out_class(n_out) != 0 && !(rows_in_class(d_in) == 16 && rows_out_class(n_out) == 8);
@@ -522,17 +506,6 @@ RL8_API int rl8_mlp_backward_f16_supports(int d_in, int n_out) {
   return d_in >= 1 && d_in <= 7 && n_out >= 1 && n_out <= 4 && !(d_in == 7 && n_out == 4);
 }
 
-// Grids of the two halves of the fused backward (as in mlp_split_kernels.hip: both derive
-// them from m alone, so that each can zero the partial-row segments the other does not cover).
-static void f16_backward_grids(int64_t m, int *g1, int *g2) {
-  const int64_t tiles = (m + kSplitRows - 1) / kSplitRows;
-  const int64_t chunks = (m + 16 - 1) / 16;  // (16-sample chunks of the weight-gradient kernel)
-  static const int cap = env_int("RL8_MLP_GRID_CAP");
-  const int max_grid = cap > 0 ? cap : 2 * kCUs;
-  *g1 = (int)(tiles < max_grid ? tiles : max_grid);
-  *g2 = (int)(chunks < kCUs ? chunks : kCUs);
-}
-
 RL8_API int rl8_mlp_tower_backward_f16_f32(const float *x, const float *w1, const float *b1, const float *dout,
                                            int64_t m, int d_in, const void *w2t_f16, const float *w3, int n_out,
                                            float *partials, int *partial_rows_out, const uint32_t *gate2,
@@ -540,26 +513,22 @@ RL8_API int rl8_mlp_tower_backward_f16_f32(const float *x, const float *w1, cons
   if (!x || !w1 || !b1 || !dout || !w2t_f16 || !w3 || !partials || !partial_rows_out || !gate2) return RL8_ENULL;
   if (m <= 0 || !rl8_mlp_backward_f16_supports(d_in, n_out)) return RL8_ESIZE;
   if (((uintptr_t)w2t_f16 & 15) != 0 || !aligned16(gate2) || !aligned16(w3)) return RL8_EALIGN;
-  int grid, g2;
-  f16_backward_grids(m, &grid, &g2);
-  *partial_rows_out = grid > g2 ? grid : g2;
+  const BackwardGrids grids = backward_grids(m);
+  *partial_rows_out = grids.partial_rows();
   const int stride = (int)rl8_mlp_backward_partial_floats(d_in, n_out);
   hipStream_t s = (hipStream_t)stream;
   if (!env_int("RL8_MLP_DGRAD_TILE")) {  // (diagnostics: 1 = the tile kernel for every width; read per call)
     // d_in <= 3, n_out 2..4: the rows-per-wave kernel (mlp_rows_kernels.hip, round 5)
-    const int st = mlp_rows_backward_general_dispatch(grid, s, x, w1, b1, dout, m, d_in, w2t_f16, w3, n_out, partials, stride, g2, gate2);
-    if (st != -1) return st;
+    const int st = mlp_rows_backward_general_dispatch(grids.g1, s, x, w1, b1, dout, m, d_in, w2t_f16, w3, n_out, partials, stride,
+                                                      grids.g2, gate2);
+    if (st != kNoVariant) return st;
   }
-  int status = RL8_ESIZE;
-#define RL8_BACKWARD_F16(D, N) \
-  if (d_in == D && n_out == N) status = launch_backward_f16<D, N>(grid, s, x, w1, b1, dout, m, w2t_f16, w3, partials, stride, g2, gate2);
-  RL8_BACKWARD_F16(1, 1) RL8_BACKWARD_F16(1, 2) RL8_BACKWARD_F16(1, 3) RL8_BACKWARD_F16(1, 4)
-  RL8_BACKWARD_F16(2, 1) RL8_BACKWARD_F16(2, 2) RL8_BACKWARD_F16(2, 3) RL8_BACKWARD_F16(2, 4)
-  RL8_BACKWARD_F16(3, 1) RL8_BACKWARD_F16(3, 2) RL8_BACKWARD_F16(3, 3) RL8_BACKWARD_F16(3, 4)
-  RL8_BACKWARD_F16(4, 1) RL8_BACKWARD_F16(4, 2) RL8_BACKWARD_F16(4, 3) RL8_BACKWARD_F16(4, 4)
-  RL8_BACKWARD_F16(5, 1) RL8_BACKWARD_F16(5, 2) RL8_BACKWARD_F16(5, 3) RL8_BACKWARD_F16(5, 4)
-#undef RL8_BACKWARD_F16
-  return status;
+  // the tile kernel: d_in 1..5 (the widths it served before the rows-per-wave kernels took 6 and 7 on)
+  return variant_status(dispatch_width(d_in, Widths<1, 2, 3, 4, 5>{}, [&](auto d) {
+    return dispatch_width(n_out, Widths<1, 2, 3, 4>{}, [&](auto n) {
+      return launch_backward_f16<d(), n()>(grids.g1, s, x, w1, b1, dout, m, w2t_f16, w3, partials, stride, grids.g2, gate2);
+    });
+  }));
 }
 
 /* The B operand of rl8_mlp_tower_backward_gate_f16_f32: planes of W2[k][i] * w3e[k] (w3e = W3[0] for one output,
@@ -583,12 +552,11 @@ RL8_API int rl8_mlp_tower_backward_gate_f16_f32(const float *x, const float *w1,
   if (!x || !w1 || !b1 || !dout || !w2t_gate || !partials || !partial_rows_out || !gate2) return RL8_ENULL;
   if (m <= 0 || (n_out != 1 && n_out != 2) || !rl8_mlp_backward_f16_supports(d_in, n_out)) return RL8_ESIZE;
   if (((uintptr_t)w2t_gate & 15) != 0 || !aligned16(gate2)) return RL8_EALIGN;
-  int grid, g2;
-  f16_backward_grids(m, &grid, &g2);
-  *partial_rows_out = grid > g2 ? grid : g2;
+  const BackwardGrids grids = backward_grids(m);
+  *partial_rows_out = grids.partial_rows();
   const int stride = (int)rl8_mlp_backward_partial_floats(d_in, n_out);
   hipStream_t s = (hipStream_t)stream;
   // the rows-per-wave kernels (mlp_rows_kernels.hip): d_in <= 3 with the layer-1 fma chain, 4 and 5 in class 8
-  const int st = mlp_rows_backward_gate_dispatch(grid, s, x, w1, b1, dout, m, d_in, w2t_gate, n_out, partials, stride, g2, gate2);
-  return st == -1 ? RL8_ESIZE : st;
+  return variant_status(mlp_rows_backward_gate_dispatch(grids.g1, s, x, w1, b1, dout, m, d_in, w2t_gate, n_out, partials, stride,
+                                                        grids.g2, gate2));
 }

@@ -24,6 +24,7 @@
 // both the row walks of the MFMA A operand and the column walks of the VALU
 // phases bank-conflict-free.
 #include "mfma_tile.hip.h"
+#include "tower_launch.hip.h"
 
 namespace rl8 {
 
@@ -591,38 +592,19 @@ RL8_API int rl8_mlp_pack_w2_f32(const float *w2, float *w2_packed, int transpose
 }
 
 template <int DIN, int NOUT, bool SAVE>
-static int launch_forward_save(int grid, hipStream_t s, const float *x, int64_t m, int d_in,
-                               const float *w1, const float *b1, const float4 *w2p,
-                               const float *b2, const float *w3, const float *b3, int n_out,
-                               float *out, float *save_h1, float *save_h2) {
-  static LdsOptIn lds_attr_set_0;
-  if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&mlp_tower_forward_kernel<DIN, NOUT, SAVE>), 160 * 1024)) return e_lds_attr_set_0;
+static int launch_forward(int grid, hipStream_t s, const float *x, int64_t m, int d_in,
+                          const float *w1, const float *b1, const float4 *w2p,
+                          const float *b2, const float *w3, const float *b3, int n_out,
+                          float *out, float *save_h1, float *save_h2) {
+  if (const int e = allow_dynamic_lds<&mlp_tower_forward_kernel<DIN, NOUT, SAVE>>()) return e;
   mlp_tower_forward_kernel<DIN, NOUT, SAVE><<<grid, kBlock, mlp_forward_lds_bytes(), s>>>(
       x, m, d_in, w1, b1, w2p, b2, w3, b3, n_out, out, save_h1, save_h2);
   return launch_status();
 }
 
-template <int DIN, int NOUT>
-static int launch_forward(int grid, hipStream_t s, const float *x, int64_t m, int d_in,
-                          const float *w1, const float *b1, const float4 *w2p, const float *b2,
-                          const float *w3, const float *b3, int n_out, float *out, float *h1,
-                          float *h2) {
-  return h1 ? launch_forward_save<DIN, NOUT, true>(grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, n_out, out, h1, h2)
-            : launch_forward_save<DIN, NOUT, false>(grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, n_out, out, h1, h2);
-}
-
-template <int DIN>
-static int dispatch_forward_nout(int n_out, int grid, hipStream_t s, const float *x, int64_t m,
-                                 int d_in, const float *w1, const float *b1, const float4 *w2p,
-                                 const float *b2, const float *w3, const float *b3, float *out,
-                                 float *h1, float *h2) {
-  switch (n_out) {
-    case 1: return launch_forward<DIN, 1>(grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, n_out, out, h1, h2);
-    case 2: return launch_forward<DIN, 2>(grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, n_out, out, h1, h2);
-    case 3: return launch_forward<DIN, 3>(grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, n_out, out, h1, h2);
-    default: return launch_forward<DIN, 0>(grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, n_out, out, h1, h2);
-  }
-}
+// The built-in environments' widths compiled in; anything else runs the run-time-width variant <0>.
+using TowerInWidths = Widths<1, 2, 3, 5>;
+using TowerOutWidths = Widths<1, 2, 3>;
 
 RL8_API int rl8_mlp_tower_forward_f32(const float *x, int64_t m, int d_in, const float *w1,
                                       const float *b1, const float *w2_packed, const float *b2,
@@ -632,19 +614,15 @@ RL8_API int rl8_mlp_tower_forward_f32(const float *x, int64_t m, int d_in, const
   if ((save_h1 == nullptr) != (save_h2 == nullptr)) return RL8_ENULL;
   if (m <= 0 || d_in <= 0 || d_in > kMaxIn || n_out <= 0 || n_out > kMaxOut) return RL8_ESIZE;
   if (!aligned16(w2_packed)) return RL8_EALIGN;
-  const int64_t tiles = (m + kTileRows - 1) / kTileRows;
-  static const int cap = env_int("RL8_MLP_GRID_CAP");
-  const int max_grid = cap > 0 ? cap : 2 * kCUs;  // two resident workgroups per CU
-  const int grid = (int)(tiles < max_grid ? tiles : max_grid);
+  const int grid = tower_grid(m, kTileRows);
   const float4 *w2p = reinterpret_cast<const float4 *>(w2_packed);
   hipStream_t s = (hipStream_t)stream;
-  switch (d_in) {  // the built-in environments' observation widths compiled in; anything else run-time
-    case 1: return dispatch_forward_nout<1>(n_out, grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, out, save_h1, save_h2);
-    case 2: return dispatch_forward_nout<2>(n_out, grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, out, save_h1, save_h2);
-    case 3: return dispatch_forward_nout<3>(n_out, grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, out, save_h1, save_h2);
-    case 5: return dispatch_forward_nout<5>(n_out, grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, out, save_h1, save_h2);
-    default: return dispatch_forward_nout<0>(n_out, grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, out, save_h1, save_h2);
-  }
+  return dispatch_width_or_runtime(d_in, TowerInWidths{}, [&](auto d) {
+    return dispatch_width_or_runtime(n_out, TowerOutWidths{}, [&](auto n) {
+      return save_h1 ? launch_forward<d(), n(), true>(grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, n_out, out, save_h1, save_h2)
+                     : launch_forward<d(), n(), false>(grid, s, x, m, d_in, w1, b1, w2p, b2, w3, b3, n_out, out, save_h1, save_h2);
+    });
+  });
 }
 
 RL8_API int64_t rl8_mlp_backward_partial_floats(int d_in, int n_out) {
@@ -864,24 +842,10 @@ static int launch_backward(int grid, hipStream_t s, const float *x, const float 
                            const float *h2, const float *dout, int64_t m, int d_in,
                            const float4 *w2tp, const float *w3, int n_out, float *dz2_out,
                            float *partials, int stride) {
-  static LdsOptIn lds_attr_set_0;
-  if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&mlp_tower_backward_kernel<DIN, NOUT>), 160 * 1024)) return e_lds_attr_set_0;
+  if (const int e = allow_dynamic_lds<&mlp_tower_backward_kernel<DIN, NOUT>>()) return e;
   mlp_tower_backward_kernel<DIN, NOUT><<<grid, kBlock, mlp_backward_lds_bytes(), s>>>(
       x, h1, h2, dout, m, d_in, w2tp, w3, n_out, dz2_out, partials, stride);
   return launch_status();
-}
-
-template <int DIN>
-static int dispatch_backward_nout(int n_out, int grid, hipStream_t s, const float *x,
-                                  const float *h1, const float *h2, const float *dout,
-                                  int64_t m, int d_in, const float4 *w2tp, const float *w3,
-                                  float *dz2_out, float *partials, int stride) {
-  switch (n_out) {
-    case 1: return launch_backward<DIN, 1>(grid, s, x, h1, h2, dout, m, d_in, w2tp, w3, n_out, dz2_out, partials, stride);
-    case 2: return launch_backward<DIN, 2>(grid, s, x, h1, h2, dout, m, d_in, w2tp, w3, n_out, dz2_out, partials, stride);
-    case 3: return launch_backward<DIN, 3>(grid, s, x, h1, h2, dout, m, d_in, w2tp, w3, n_out, dz2_out, partials, stride);
-    default: return launch_backward<DIN, 0>(grid, s, x, h1, h2, dout, m, d_in, w2tp, w3, n_out, dz2_out, partials, stride);
-  }
 }
 
 RL8_API int rl8_mlp_tower_backward_f32(const float *x, const float *h1, const float *h2,
@@ -895,19 +859,16 @@ RL8_API int rl8_mlp_tower_backward_f32(const float *x, const float *h1, const fl
   if (!aligned16(h2) || !aligned16(h1) || !aligned16(dz2_out)) return RL8_EALIGN;
   if (m <= 0 || d_in <= 0 || d_in > kMaxIn || n_out <= 0 || n_out > kMaxOut) return RL8_ESIZE;
   if (!aligned16(w2t_packed)) return RL8_EALIGN;
-  const int64_t tiles = (m + kTileRows - 1) / kTileRows;
-  const int grid = (int)(tiles < 2 * kCUs ? tiles : 2 * kCUs);
+  const int grid = grid_for(m, kTileRows, 2 * kCUs);  // (rl8_mlp_backward_max_rows() partial rows: no RL8_MLP_GRID_CAP here)
   *partial_rows_out = grid;
   const float4 *w2tp = reinterpret_cast<const float4 *>(w2t_packed);
   const int stride = (int)rl8_mlp_backward_partial_floats(d_in, n_out);
   hipStream_t s = (hipStream_t)stream;
-  switch (d_in) {
-    case 1: return dispatch_backward_nout<1>(n_out, grid, s, x, h1, h2, dout, m, d_in, w2tp, w3, dz2_out, partials, stride);
-    case 2: return dispatch_backward_nout<2>(n_out, grid, s, x, h1, h2, dout, m, d_in, w2tp, w3, dz2_out, partials, stride);
-    case 3: return dispatch_backward_nout<3>(n_out, grid, s, x, h1, h2, dout, m, d_in, w2tp, w3, dz2_out, partials, stride);
-    case 5: return dispatch_backward_nout<5>(n_out, grid, s, x, h1, h2, dout, m, d_in, w2tp, w3, dz2_out, partials, stride);
-    default: return dispatch_backward_nout<0>(n_out, grid, s, x, h1, h2, dout, m, d_in, w2tp, w3, dz2_out, partials, stride);
-  }
+  return dispatch_width_or_runtime(d_in, TowerInWidths{}, [&](auto d) {
+    return dispatch_width_or_runtime(n_out, TowerOutWidths{}, [&](auto n) {
+      return launch_backward<d(), n()>(grid, s, x, h1, h2, dout, m, d_in, w2tp, w3, n_out, dz2_out, partials, stride);
+    });
+  });
 }
 
 RL8_API int64_t rl8_mlp_wgrad_workspace_bytes(void) {
@@ -924,10 +885,8 @@ RL8_API int rl8_mlp_wgrad_strided_f32(const float *dz2, int64_t dz2_pitch, const
     return RL8_ESIZE;
   if (!aligned16(dz2) || !aligned16(h1) || !aligned16(workspace) || !aligned16(dw2_out))
     return RL8_EALIGN;
-  static LdsOptIn lds_attr_set_0;
-  if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&mlp_wgrad_kernel), 160 * 1024)) return e_lds_attr_set_0;
-  const int64_t tiles = (m + kWgradRows - 1) / kWgradRows;
-  const int grid = (int)(tiles < kCUs ? tiles : kCUs);
+  if (const int e = allow_dynamic_lds<&mlp_wgrad_kernel>()) return e;
+  const int grid = grid_for(m, kWgradRows, kCUs);
   hipStream_t s = (hipStream_t)stream;
   const size_t lds_bytes = sizeof(float) * 4 * kWgradTile;
   mlp_wgrad_kernel<<<grid, kWgradThreads, lds_bytes, s>>>(dz2, dz2_pitch, h1, h1_pitch, m, workspace);

@@ -12,9 +12,8 @@ int launch_backward_dx(hipStream_t s, const float *x, const float *dout, int64_t
                        float *dx) {
   constexpr size_t bytes = (backward_lds_floats<H, KIN, KOUT>() + (size_t)H * (KIN + 4)) * sizeof(float);
   static_assert(bytes * Geo<H>::kWgPerCU <= 160 * 1024, "backward LDS with the W1 tile");
-  static LdsOptIn opt_in;
-  auto *kernel = &mlp_narrow_backward_kernel<H, KIN, KOUT, true>;
-  if (const int e = allow_dynamic_lds(opt_in, reinterpret_cast<const void *>(kernel), (int)bytes)) return e;
+  constexpr auto *kernel = &mlp_narrow_backward_kernel<H, KIN, KOUT, true>;
+  if (const int e = allow_dynamic_lds<kernel>((int)bytes)) return e;
   kernel<<<grid_for<H>(m), kThreads, bytes, s>>>(x, dout, m, d_in, w1, b1, w2, b2, w3, n_out, slabs, dx);
   return launch_status();
 }

@@ -25,9 +25,8 @@ int launch_forward(hipStream_t s, const float *x, int64_t m, int d_in, const flo
                    const float *w2, const float *b2, const float *w3, const float *b3, int n_out, float *out) {
   constexpr size_t bytes = forward_lds_floats<H, KIN, KOUT>() * sizeof(float);
   static_assert(bytes * Geo<H>::kWgPerCU <= 160 * 1024, "forward LDS");
-  static LdsOptIn opt_in;
-  auto *kernel = &mlp_narrow_forward_kernel<H, KIN, KOUT>;
-  if (const int e = allow_dynamic_lds(opt_in, reinterpret_cast<const void *>(kernel), (int)bytes)) return e;
+  constexpr auto *kernel = &mlp_narrow_forward_kernel<H, KIN, KOUT>;
+  if (const int e = allow_dynamic_lds<kernel>((int)bytes)) return e;
   kernel<<<grid_for<H>(m), kThreads, bytes, s>>>(x, m, d_in, w1, b1, w2, b2, w3, b3, n_out, out);
   return launch_status();
 }
@@ -37,9 +36,8 @@ int launch_backward(hipStream_t s, const float *x, const float *dout, int64_t m,
                     const float *b1, const float *w2, const float *b2, const float *w3, int n_out, float *slabs) {
   constexpr size_t bytes = backward_lds_floats<H, KIN, KOUT>() * sizeof(float);
   static_assert(bytes * Geo<H>::kWgPerCU <= 160 * 1024, "backward LDS");
-  static LdsOptIn opt_in;
-  auto *kernel = &mlp_narrow_backward_kernel<H, KIN, KOUT>;
-  if (const int e = allow_dynamic_lds(opt_in, reinterpret_cast<const void *>(kernel), (int)bytes)) return e;
+  constexpr auto *kernel = &mlp_narrow_backward_kernel<H, KIN, KOUT>;
+  if (const int e = allow_dynamic_lds<kernel>((int)bytes)) return e;
   kernel<<<grid_for<H>(m), kThreads, bytes, s>>>(x, dout, m, d_in, w1, b1, w2, b2, w3, n_out, slabs, nullptr);
   return launch_status();
 }

@@ -32,6 +32,7 @@
 // (first MFMA operand = W2 fragment): a lane holds, for row (lane & 15) + 16 rt and column tile ct, the four
 // consecutive columns 16 ct + 4 (lane >> 4) + r -- quads, a row being shared by the four lanes of equal lane & 15.
 #include "split_tile.hip.h"
+#include "tower_launch.hip.h"
 
 namespace rl8 {
 
@@ -1530,26 +1531,27 @@ static int launch_rows_backward_gate(int grid, hipStream_t s, const float *x, co
                                      int64_t m, const void *w2ts, float *partials, int stride, int head_rows,
                                      const uint32_t *gate2, int d_in) {
   constexpr int kRing = DIN == 1 ? 4 : 3;
-  auto kernel = &mlp_rows_backward_gate_kernel<DIN, NOUT, kRing>;
-  static LdsOptIn lds_attr_set_0;
-  if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(kernel), 160 * 1024)) return e_lds_attr_set_0;
+  constexpr auto kernel = &mlp_rows_backward_gate_kernel<DIN, NOUT, kRing>;
+  if (const int e = allow_dynamic_lds<kernel>()) return e;
   constexpr int kLds = DIN > 3 ? rows8_dgrad_lds_bytes(kRing, 0) : rows_dgrad_lds_bytes(kRing, DIN);
   kernel<<<grid, kBlock, kLds, s>>>(x, w1, b1, dout, m, w2ts, partials, stride, head_rows, gate2, d_in);
   return launch_status();
 }
 
-// The gate-mode data gradient behind rl8_mlp_tower_backward_gate_f16_f32 for d_in <= 3 (-1: no variant: the caller keeps
-// the previous kernel).  Same grid and partial rows as that kernel.
+// The input classes of the data-gradient kernels: widths 1..3 by themselves, 4..7 in class 8 (which keeps M slot 7 for
+// db1: seven inputs); 0: none.
+static int rows_backward_in_class(int d_in) { return d_in <= 3 ? d_in : d_in <= 7 ? 8 : 0; }
+using RowsBackwardInClasses = Widths<1, 2, 3, 8>;
+
+// The gate-mode data gradient behind rl8_mlp_tower_backward_gate_f16_f32 (kNoVariant: none for this width).
 int mlp_rows_backward_gate_dispatch(int grid, hipStream_t s, const float *x, const float *w1, const float *b1, const float *dout,
                                     int64_t m, int d_in, const void *w2ts, int n_out, float *partials, int stride, int head_rows,
                                     const uint32_t *gate2) {
-  const int dc = d_in <= 3 ? d_in : d_in <= 7 ? 8 : 0;  // (class 8 keeps M slot 7 for db1: seven inputs)
-#define RL8_ROWS_BWD(D, N) \
-  if (dc == D && n_out == N) return launch_rows_backward_gate<D, N>(grid, s, x, w1, b1, dout, m, w2ts, partials, stride, head_rows, gate2, d_in);
-  RL8_ROWS_BWD(1, 1) RL8_ROWS_BWD(1, 2) RL8_ROWS_BWD(2, 1) RL8_ROWS_BWD(2, 2) RL8_ROWS_BWD(3, 1) RL8_ROWS_BWD(3, 2)
-  RL8_ROWS_BWD(8, 1) RL8_ROWS_BWD(8, 2)
-#undef RL8_ROWS_BWD
-  return -1;
+  return dispatch_width(rows_backward_in_class(d_in), RowsBackwardInClasses{}, [&](auto d) {
+    return dispatch_width(n_out, Widths<1, 2>{}, [&](auto n) {
+      return launch_rows_backward_gate<d(), n()>(grid, s, x, w1, b1, dout, m, w2ts, partials, stride, head_rows, gate2, d_in);
+    });
+  });
 }
 
 // ---- data gradient of GENERAL heads in the same structure (round 5) ------------------------
@@ -2072,30 +2074,28 @@ static int launch_rows_backward_general(int grid, hipStream_t s, const float *x,
                                         int64_t m, const void *w2ts, const float *w3, float *partials, int stride, int head_rows,
                                         const uint32_t *gate2, int n_out, int d_in) {
   constexpr int kRing = 3;
-  auto kernel = &mlp_rows_backward_general_kernel<DIN, KOUT, kRing>;
-  static LdsOptIn opt;
-  if (const int e = allow_dynamic_lds(opt, reinterpret_cast<const void *>(kernel), 160 * 1024)) return e;
+  constexpr auto kernel = &mlp_rows_backward_general_kernel<DIN, KOUT, kRing>;
+  if (const int e = allow_dynamic_lds<kernel>()) return e;
   constexpr int kLds = DIN > 3 ? rows8_dgrad_lds_bytes(kRing, KOUT) : rows_dgrad_general_lds_bytes(kRing, DIN, KOUT);
   kernel<<<grid, kBlock, kLds, s>>>(x, w1, b1, dout, m, w2ts, w3, partials, stride, head_rows, gate2, n_out, d_in);
   return launch_status();
 }
 
-// The general data gradient behind rl8_mlp_tower_backward_f16_f32 for d_in <= 3, n_out 2..4 (-1: no variant: the caller
-// keeps the tile kernel).  Same grid and partial rows as that kernel.
+// The general data gradient behind rl8_mlp_tower_backward_f16_f32 for n_out 2..4 (kNoVariant: none: the caller keeps the
+// tile kernel).  Same grid and partial rows as that kernel.
 int mlp_rows_backward_general_dispatch(int grid, hipStream_t s, const float *x, const float *w1, const float *b1, const float *dout,
                                        int64_t m, int d_in, const void *w2ts, const float *w3, int n_out, float *partials, int stride,
                                        int head_rows, const uint32_t *gate2) {
-  const int dc = d_in <= 3 ? d_in : d_in <= 7 ? 8 : 0;  // (class 8 keeps M slot 7 for db1: seven inputs)
-#define RL8_ROWS_BWD_GENERAL(D) \
-  if (dc == D && n_out == 2) return launch_rows_backward_general<D, 2>(grid, s, x, w1, b1, dout, m, w2ts, w3, partials, stride, head_rows, gate2, n_out, d_in); \
-  if (dc == D && (n_out == 3 || n_out == 4)) return launch_rows_backward_general<D, 4>(grid, s, x, w1, b1, dout, m, w2ts, w3, partials, stride, head_rows, gate2, n_out, d_in);
-  RL8_ROWS_BWD_GENERAL(1) RL8_ROWS_BWD_GENERAL(2) RL8_ROWS_BWD_GENERAL(3) RL8_ROWS_BWD_GENERAL(8)
-#undef RL8_ROWS_BWD_GENERAL
-  // one output in GENERAL mode (h2 given, no gate pack: the product takes the gate mode for it) at d_in 6, 7 -- widths the
-  // tile kernel of mlp_f16_kernels.hip is not compiled for: the two-output class with a zero second record
-  if (dc == 8 && d_in >= 6 && n_out == 1)
-    return launch_rows_backward_general<8, 2>(grid, s, x, w1, b1, dout, m, w2ts, w3, partials, stride, head_rows, gate2, n_out, d_in);
-  return -1;
+  // output classes 2 and 4.  One output in GENERAL mode (h2 given, no gate pack: the product takes the gate mode for it)
+  // has a variant at d_in 6, 7 only -- widths the tile kernel of mlp_f16_kernels.hip is not compiled for: the two-output
+  // class with a zero second record
+  const int kc = n_out == 2 || (n_out == 1 && d_in >= 6) ? 2 : n_out == 3 || n_out == 4 ? 4 : 0;
+  return dispatch_width(rows_backward_in_class(d_in), RowsBackwardInClasses{}, [&](auto d) {
+    return dispatch_width(kc, Widths<2, 4>{}, [&](auto k) {
+      return launch_rows_backward_general<d(), k()>(grid, s, x, w1, b1, dout, m, w2ts, w3, partials, stride, head_rows, gate2, n_out,
+                                                    d_in);
+    });
+  });
 }
 
 template <int DIN, int NOUT, int SAVE>
@@ -2122,13 +2122,9 @@ static int launch_rows_forward(hipStream_t s, const float *x, int64_t m, const f
       e != hipSuccess)
     return (int)e;
 #else
-  static LdsOptIn lds_forward;
-  if (const int e = allow_dynamic_lds(lds_forward, reinterpret_cast<const void *>(kernel), 160 * 1024)) return e;
+  if (const int e = allow_dynamic_lds<&mlp_rows_forward_kernel<DIN, NOUT, SAVE, kRing>>()) return e;
 #endif
-  const int64_t tiles = (m + 127) / 128;
-  static const int cap = env_int("RL8_MLP_GRID_CAP");
-  const int max_grid = cap > 0 ? cap : 2 * kCUs;
-  const int grid = (int)(tiles < max_grid ? tiles : max_grid);
+  const int grid = tower_grid(m, 128);
 #ifdef RL8_ROWS_STAMP
   const char *sp = getenv("RL8_ROWS_STAMP_PTR");
   kernel<<<grid, kBlock, kLds, s>>>(x, m, w1, b1, w2s, b2, w3, b3, out, h1, h2, gate, d_in, n_out,
@@ -2139,15 +2135,6 @@ static int launch_rows_forward(hipStream_t s, const float *x, int64_t m, const f
   return launch_status();
 }
 
-template <int DIN, int NOUT>
-static int launch_rows_forward_save(hipStream_t s, const float *x, int64_t m, const float *w1, const float *b1, const void *w2s,
-                                    const float *b2, const float *w3, const float *b3, float *out, float *h1, float *h2,
-                                    uint32_t *gate, int d_in, int n_out) {
-  return h2     ? launch_rows_forward<DIN, NOUT, 1>(s, x, m, w1, b1, w2s, b2, w3, b3, out, h1, h2, gate, d_in, n_out)
-         : gate ? launch_rows_forward<DIN, NOUT, 2>(s, x, m, w1, b1, w2s, b2, w3, b3, out, h1, h2, gate, d_in, n_out)
-                : launch_rows_forward<DIN, NOUT, 0>(s, x, m, w1, b1, w2s, b2, w3, b3, out, h1, h2, gate, d_in, n_out);
-}
-
 // Width classes (round 5): the smallest compiled class that holds the run-time width.
 int rows_in_class(int d_in) { return d_in <= 3 ? d_in : d_in <= 8 ? 8 : d_in <= 16 ? 16 : 0; }
 int rows_out_class(int n_out) { return n_out >= 1 && n_out <= 8 ? pad_out(n_out) : 0; }
@@ -2156,16 +2143,17 @@ int rows_out_class(int n_out) { return n_out >= 1 && n_out <= 8 ? pad_out(n_out)
 int mlp_rows_forward_dispatch(hipStream_t s, const float *x, int64_t m, int d_in, const float *w1, const float *b1,
                               const void *w2s, const float *b2, const float *w3, const float *b3, int n_out, float *out,
                               float *h1, float *h2, uint32_t *gate) {
-  const int dc = rows_in_class(d_in), nc = rows_out_class(n_out);
-#define RL8_ROWS(D, N) \
-  if (dc == D && nc == N) return launch_rows_forward_save<D, N>(s, x, m, w1, b1, w2s, b2, w3, b3, out, h1, h2, gate, d_in, n_out);
-  RL8_ROWS(1, 1) RL8_ROWS(1, 2) RL8_ROWS(1, 4) RL8_ROWS(1, 8)
-  RL8_ROWS(2, 1) RL8_ROWS(2, 2) RL8_ROWS(2, 4) RL8_ROWS(2, 8)
-  RL8_ROWS(3, 1) RL8_ROWS(3, 2) RL8_ROWS(3, 4) RL8_ROWS(3, 8)
-  RL8_ROWS(8, 1) RL8_ROWS(8, 2) RL8_ROWS(8, 4) RL8_ROWS(8, 8)
-  RL8_ROWS(16, 1) RL8_ROWS(16, 2) RL8_ROWS(16, 4)  // (sixteen inputs x eight outputs: no room for the h2 scratch at two workgroups per CU)
-#undef RL8_ROWS
-  return RL8_ESIZE;
+  const int save = h2 ? 1 : gate ? 2 : 0;  // SAVE mode: h2 (with its gate bits and h1 if given), the gate bits alone, nothing
+  return variant_status(dispatch_width(rows_in_class(d_in), Widths<1, 2, 3, 8, 16>{}, [&](auto d) {
+    return dispatch_width(rows_out_class(n_out), Widths<1, 2, 4, 8>{}, [&](auto n) {
+      // (sixteen inputs x eight outputs: no room for the h2 scratch at two workgroups per CU -- not compiled)
+      if constexpr (d() == 16 && n() == 8) return kNoVariant;
+      else
+        return dispatch_width(save, Widths<0, 1, 2>{}, [&](auto v) {
+          return launch_rows_forward<d(), n(), v()>(s, x, m, w1, b1, w2s, b2, w3, b3, out, h1, h2, gate, d_in, n_out);
+        });
+    });
+  }));
 }
 
 }  // namespace rl8

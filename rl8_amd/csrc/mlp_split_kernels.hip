@@ -17,6 +17,7 @@
 // mlp_f16_kernels.hip, everything else the fp32-MFMA generation of mlp_kernels.hip.
 #include <type_traits>
 #include "split_tile.hip.h"
+#include "tower_launch.hip.h"
 
 namespace rl8 {
 
@@ -40,15 +41,8 @@ namespace rl8 {
 // next step's first fragments are fetched right behind it (see do_step).  Partial sums leave
 // as one slab per workgroup, added up in slab order by mlp_wgrad_split_reduce_kernel
 // (bitwise reproducible; no atomics).
-// A launch covers at most this many samples; longer inputs are summed segment by segment
-// (dW2 through the slab reduction's accumulate mode, the head-gradient partial rows in
-// place).  Every accumulator is an fp32 chain over its workgroup's share of the samples:
-// at 2^25 rows in one launch dW2 was 7e-5 (of its largest entry) off an fp64 evaluation,
-// at 2^23 per launch 4e-5 -- the length the parity tests were validated at, kept
-// whatever the caller's pass size.
-constexpr int64_t kWgradSegmentRows = (int64_t)1 << 23;
+// A launch covers at most kWgradSegmentRows samples, in chunks of kWsChunk (tower_launch.hip.h, with the segment walk).
 constexpr int kWsThreads = 512;
-constexpr int kWsChunk = 16;                             // samples per k-step
 constexpr int kWsOperandBytes = 3 * 2 * kHidden * 16;    // [plane][sample half][column] x 16 B
 constexpr int kWsPlane = 2 * kHidden * 16;
 constexpr int kWsStageBytes = 2 * kWsOperandBytes;       // dZ2^T | h1
@@ -1160,9 +1154,8 @@ __global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_gate16_kernel(
 template <int DIN, bool PAIR>
 static int launch_wgrad_gate16(int grid, hipStream_t s, const float *x, const float *w1, const float *b1, int64_t m,
                                float *slabs, WgradFusedArgs fused) {
-  static LdsOptIn opt;
   if (m > kWgradSegmentRows) return RL8_ESIZE;  // (the kernel's 32-bit byte offsets)
-  if (const int e = allow_dynamic_lds(opt, reinterpret_cast<const void *>(&mlp_wgrad_gate16_kernel<DIN, PAIR>), 160 * 1024)) return e;
+  if (const int e = allow_dynamic_lds<&mlp_wgrad_gate16_kernel<DIN, PAIR>>()) return e;
   fused.late_bit = wgrad_late_bit();
   mlp_wgrad_gate16_kernel<DIN, PAIR><<<grid, kW16Threads, kW16Stages * kW16StageBytes + kHidden * 4, s>>>(x, w1, b1, m, slabs, fused);
   return launch_status();
@@ -1423,8 +1416,7 @@ __global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_fused16_kernel(
 template <int DIN, int NOUT>
 static int launch_wgrad_fused16(int grid, hipStream_t s, const float *h2, const float *x, const float *w1, const float *b1,
                                 int64_t m, float *slabs, WgradFusedArgs fused) {
-  static LdsOptIn opt;
-  if (const int e = allow_dynamic_lds(opt, reinterpret_cast<const void *>(&mlp_wgrad_fused16_kernel<DIN, NOUT>), 160 * 1024)) return e;
+  if (const int e = allow_dynamic_lds<&mlp_wgrad_fused16_kernel<DIN, NOUT>>()) return e;
   mlp_wgrad_fused16_kernel<DIN, NOUT><<<grid, kW16Threads, kW16Stages * kW16FusedStageBytes + 2 * kHidden * 4, s>>>(h2, x, w1, b1, m, slabs, fused);
   return launch_status();
 }
@@ -1488,8 +1480,7 @@ __global__ __launch_bounds__(kBlock) void mlp_wgrad_split_reduce_kernel(const fl
 template <int DIN>
 static int launch_wgrad_split(int grid, hipStream_t s, const float *dz2, const float *x, const float *w1,
                               const float *b1, int64_t m, int d_in, float *slabs) {
-  static LdsOptIn lds_attr_set_0;
-  if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&mlp_wgrad_split_kernel<DIN>), 160 * 1024)) return e_lds_attr_set_0;
+  if (const int e = allow_dynamic_lds<&mlp_wgrad_split_kernel<DIN>>()) return e;
   mlp_wgrad_split_kernel<DIN><<<grid, kWsThreads, 2 * kWsStageBytes, s>>>(dz2, x, w1, b1, m, d_in, slabs, WgradFusedArgs{},
                                                                            WgradOperands{});
   return launch_status();
@@ -1498,8 +1489,7 @@ static int launch_wgrad_split(int grid, hipStream_t s, const float *dz2, const f
 template <int DIN, int NOUT>
 static int launch_wgrad_fused(int grid, hipStream_t s, const float *h2, const float *x, const float *w1,
                               const float *b1, int64_t m, int d_in, float *slabs, WgradFusedArgs fused) {
-  static LdsOptIn lds_attr_set_0;
-  if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&mlp_wgrad_split_kernel<DIN, NOUT, false>), 160 * 1024)) return e_lds_attr_set_0;
+  if (const int e = allow_dynamic_lds<&mlp_wgrad_split_kernel<DIN, NOUT, false>>()) return e;
   mlp_wgrad_split_kernel<DIN, NOUT, false><<<grid, kWsThreads, 2 * kWsStageBytes, s>>>(
       h2, x, w1, b1, m, d_in, slabs, fused, WgradOperands{});
   return launch_status();
@@ -1508,8 +1498,7 @@ static int launch_wgrad_fused(int grid, hipStream_t s, const float *h2, const fl
 template <int DIN, bool PAIR = false, bool BITS = false>
 static int launch_wgrad_gate(int grid, hipStream_t s, const float *h2, const float *x, const float *w1,
                              const float *b1, int64_t m, float *slabs, WgradFusedArgs fused) {
-  static LdsOptIn lds_attr_set_0;
-  if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&mlp_wgrad_gate_kernel<DIN, PAIR, BITS>), 160 * 1024)) return e_lds_attr_set_0;
+  if (const int e = allow_dynamic_lds<&mlp_wgrad_gate_kernel<DIN, PAIR, BITS>>()) return e;
   mlp_wgrad_gate_kernel<DIN, PAIR, BITS><<<grid, kWsThreads, 4 * kWgStageBytes, s>>>(
       h2, x, w1, b1, m, slabs, fused);
   return launch_status();
@@ -1583,21 +1572,22 @@ __global__ __launch_bounds__(kBlock) void wgrad_bounds_kernel(const float *__res
   }
 }
 
+using BackwardInWidths = Widths<1, 2, 3, 4, 5, 6, 7>;  // rl8_mlp_backward_f16_supports: compiled per width
+
 // the bounds behind the slabs of the caller's workspace (rl8_mlp_wgrad_workspace_bytes), filled for the whole call
-template <int NOUT>
-static uint32_t *launch_wgrad_bounds(hipStream_t s, const float *dout, const float *x, int64_t m, int d_in, float *workspace) {
+static uint32_t *launch_wgrad_bounds(hipStream_t s, const float *dout, const float *x, int64_t m, int d_in, int n_out,
+                                     float *workspace) {
   uint32_t *bounds = reinterpret_cast<uint32_t *>(workspace + (int64_t)kCUs * kHidden * kHidden);
   if (hipMemsetAsync(bounds, 0, 128, s) != hipSuccess) return nullptr;  // words 0 .. 31; the lifetime counters sit at 32, 33
   const int64_t want = m / (4 * kBlock);
   const int grid = (int)(want < 1 ? 1 : want > 4 * kCUs ? 4 * kCUs : want);  // (one atomic per block and column: 12 ns each)
-  if (d_in == 1) wgrad_bounds_kernel<1, NOUT><<<grid, kBlock, 0, s>>>(dout, x, m, bounds);
-  else if (d_in == 2) wgrad_bounds_kernel<2, NOUT><<<grid, kBlock, 0, s>>>(dout, x, m, bounds);
-  else if (d_in == 3) wgrad_bounds_kernel<3, NOUT><<<grid, kBlock, 0, s>>>(dout, x, m, bounds);
-  else if (d_in == 4) wgrad_bounds_kernel<4, NOUT><<<grid, kBlock, 0, s>>>(dout, x, m, bounds);
-  else if (d_in == 5) wgrad_bounds_kernel<5, NOUT><<<grid, kBlock, 0, s>>>(dout, x, m, bounds);
-  else if (d_in == 6) wgrad_bounds_kernel<6, NOUT><<<grid, kBlock, 0, s>>>(dout, x, m, bounds);
-  else if (d_in == 7) wgrad_bounds_kernel<7, NOUT><<<grid, kBlock, 0, s>>>(dout, x, m, bounds);
-  else return nullptr;
+  const int status = dispatch_width(d_in, BackwardInWidths{}, [&](auto d) {
+    return dispatch_width(n_out, Widths<1, 2, 3, 4>{}, [&](auto n) {
+      wgrad_bounds_kernel<d(), n()><<<grid, kBlock, 0, s>>>(dout, x, m, bounds);
+      return 0;
+    });
+  });
+  if (status == kNoVariant) return nullptr;
   return bounds;
 }
 
@@ -1734,9 +1724,6 @@ __global__ __launch_bounds__(kBlock) void dout_pair_check_kernel(const uint32_t 
 
 using namespace rl8;
 
-// Grids of the two halves of the fused backward: see fused_backward_grids below.
-static void fused_backward_grids(int64_t m, int *g1, int *g2);
-
 /* dW2 (+)= dZ2^T h1 with h1 recomputed from the observations (see the kernel). */
 RL8_API int rl8_mlp_wgrad_split_f32(const float *dz2, const float *x, const float *w1, const float *b1,
                                     int64_t m, int d_in, float *workspace, float *dw2_out, int accumulate,
@@ -1745,32 +1732,22 @@ RL8_API int rl8_mlp_wgrad_split_f32(const float *dz2, const float *x, const floa
   if (m <= 0 || d_in <= 0 || d_in > kMaxIn) return RL8_ESIZE;
   if (!aligned16(dz2) || !aligned16(workspace) || !aligned16(dw2_out)) return RL8_EALIGN;
   hipStream_t s = (hipStream_t)stream;
-  // Segments of kWgradSegmentRows samples, summed in order (see there).
-  for (int64_t at = 0; at < m; at += kWgradSegmentRows) {
-    const int64_t rows = m - at < kWgradSegmentRows ? m - at : kWgradSegmentRows;
-    const int64_t chunks = (rows + kWsChunk - 1) / kWsChunk;
-    const int grid = (int)(chunks < kCUs ? chunks : kCUs);
-    const float *dz = dz2 + at * kHidden, *xs = x + at * d_in;
-    int status;
-    switch (d_in) {
-      case 1: status = launch_wgrad_split<1>(grid, s, dz, xs, w1, b1, rows, d_in, workspace); break;
-      case 2: status = launch_wgrad_split<2>(grid, s, dz, xs, w1, b1, rows, d_in, workspace); break;
-      case 3: status = launch_wgrad_split<3>(grid, s, dz, xs, w1, b1, rows, d_in, workspace); break;
-      case 5: status = launch_wgrad_split<5>(grid, s, dz, xs, w1, b1, rows, d_in, workspace); break;
-      default: status = launch_wgrad_split<0>(grid, s, dz, xs, w1, b1, rows, d_in, workspace); break;
-    }
-    if (status != 0) return status;
-    mlp_wgrad_split_reduce_kernel<<<kHidden * kHidden / kBlock, kBlock, 0, s>>>(workspace, grid, dw2_out,
-                                                                                 accumulate || at > 0);
-  }
-  return launch_status();
+  const int status = for_each_wgrad_segment(m, 1, [&](const WgradSegment &seg) {
+    const int st = dispatch_width_or_runtime(d_in, Widths<1, 2, 3, 5>{}, [&](auto d) {
+      return launch_wgrad_split<d()>(seg.grid, s, dz2 + seg.at * kHidden, x + seg.at * d_in, w1, b1, seg.rows, d_in, workspace);
+    });
+    if (st != 0) return st;
+    mlp_wgrad_split_reduce_kernel<<<kHidden * kHidden / kBlock, kBlock, 0, s>>>(workspace, seg.grid, dw2_out,
+                                                                                 accumulate || seg.later);
+    return 0;
+  });
+  return status ? status : launch_status();
 }
 
 template <int DIN>
 static int launch_wgrad_loadh(int grid, hipStream_t s, const float *dz, const float *x, int64_t rows, float *workspace,
                               const WgradOperands &ops) {
-  static LdsOptIn lds_attr_set_0;
-  if (const int e_lds_attr_set_0 = allow_dynamic_lds(lds_attr_set_0, reinterpret_cast<const void *>(&mlp_wgrad_split_kernel<DIN, 0, true>), 160 * 1024)) return e_lds_attr_set_0;
+  if (const int e = allow_dynamic_lds<&mlp_wgrad_split_kernel<DIN, 0, true>>()) return e;
   mlp_wgrad_split_kernel<DIN, 0, true><<<grid, kWsThreads, 2 * kWsStageBytes, s>>>(
       dz, x, nullptr, nullptr, rows, DIN, workspace, WgradFusedArgs{}, ops);
   return launch_status();
@@ -1977,8 +1954,7 @@ __global__ __launch_bounds__(kW16Threads, 1) void mlp_wgrad_loadh16_kernel(
 template <int DIN>
 static int launch_wgrad_loadh16(int grid, hipStream_t s, const float *dz, const float *x, int64_t rows, float *workspace,
                                 const WgradOperands &ops) {
-  static LdsOptIn opt;
-  if (const int e = allow_dynamic_lds(opt, reinterpret_cast<const void *>(&mlp_wgrad_loadh16_kernel<DIN>), 160 * 1024)) return e;
+  if (const int e = allow_dynamic_lds<&mlp_wgrad_loadh16_kernel<DIN>>()) return e;
   mlp_wgrad_loadh16_kernel<DIN><<<grid, kW16Threads, kW16Stages * kW16FusedStageBytes, s>>>(dz, x, rows, workspace, ops);
   return launch_status();
 }
@@ -2003,48 +1979,25 @@ static int wgrad_strided(const float *dz, int64_t dz_pitch, const float *h, int6
   }
   hipStream_t s = (hipStream_t)stream;
   int first_grid = 0;
-  for (int64_t at = 0; at < m; at += kWgradSegmentRows) {  // segments summed in order, as above
-    const int64_t rows = m - at < kWgradSegmentRows ? m - at : kWgradSegmentRows;
-    const int64_t chunks = (rows + kWsChunk - 1) / kWsChunk;
-    int grid = (int)(chunks < kCUs ? chunks : kCUs);
-    if (groups == 4) {  // a multiple of 32 workgroups, a quarter of them per gate (each gate's share <= chunks)
-      const int64_t per_gate = chunks < kCUs / 4 ? chunks : kCUs / 4;
-      grid = (int)((per_gate / 8) * 8) * 4;
-      if (grid == 0) return RL8_ESIZE;  // (fewer than 128 rows: the caller uses the per-gate call)
-    }
-    if (at == 0) first_grid = grid;
-    if (grid > first_grid) grid = first_grid;  // (later segments add to the first one's rows)
-    const WgradOperands ops{h + at * h_pitch, (int)dz_pitch, (int)h_pitch, colsums, at > 0, dz_bound, h_bound,
+  const int status = for_each_wgrad_segment(m, groups, [&](const WgradSegment &seg) {
+    if (!seg.later) first_grid = seg.grid;
+    const WgradOperands ops{h + seg.at * h_pitch, (int)dz_pitch, (int)h_pitch, colsums, seg.later, dz_bound, h_bound,
                             groups, groups == 4 ? kHidden : 0};
-    const float *xs = colsums ? x + at * d_in : nullptr;
-    int status;
-    if (dz_bound) {  // fp16 planes behind the caller's bound: the sixteen-wave kernel
-      switch (colsums ? d_in : 1) {
-        case 1: status = launch_wgrad_loadh16<1>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        case 2: status = launch_wgrad_loadh16<2>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        case 3: status = launch_wgrad_loadh16<3>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        case 4: status = launch_wgrad_loadh16<4>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        case 5: status = launch_wgrad_loadh16<5>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        case 6: status = launch_wgrad_loadh16<6>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        default: status = launch_wgrad_loadh16<7>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-      }
-    } else {  // no bound: the exact bf16 planes
-      switch (colsums ? d_in : 1) {
-        case 1: status = launch_wgrad_loadh<1>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        case 2: status = launch_wgrad_loadh<2>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        case 3: status = launch_wgrad_loadh<3>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        case 4: status = launch_wgrad_loadh<4>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        case 5: status = launch_wgrad_loadh<5>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        case 6: status = launch_wgrad_loadh<6>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-        default: status = launch_wgrad_loadh<7>(grid, s, dz + at * dz_pitch, xs, rows, workspace, ops); break;
-      }
-    }
-    if (status != 0) return status;
-    for (int q = 0; q < groups; ++q)  // (gate q: slabs [q grid / groups, ...), dW block q)
+    const float *dzs = dz + seg.at * dz_pitch, *xs = colsums ? x + seg.at * d_in : nullptr;
+    const int st = variant_status(dispatch_width(colsums ? d_in : 1, BackwardInWidths{}, [&](auto d) {
+      // fp16 planes behind the caller's bound: the sixteen-wave kernel; no bound: the exact bf16 planes
+      return dz_bound ? launch_wgrad_loadh16<d()>(seg.grid, s, dzs, xs, seg.rows, workspace, ops)
+                      : launch_wgrad_loadh<d()>(seg.grid, s, dzs, xs, seg.rows, workspace, ops);
+    }));
+    if (st != 0) return st;
+    const int slabs = seg.grid / groups;
+    for (int q = 0; q < groups; ++q)  // (gate q: slabs [q slabs, ...), dW block q)
       mlp_wgrad_split_reduce_kernel<<<kHidden * kHidden / kBlock, kBlock, 0, s>>>(
-          workspace + (int64_t)q * (grid / groups) * kHidden * kHidden, grid / groups, dw_out + (int64_t)q * kHidden * kHidden,
-          accumulate || at > 0);
-  }
+          workspace + (int64_t)q * slabs * kHidden * kHidden, slabs, dw_out + (int64_t)q * kHidden * kHidden,
+          accumulate || seg.later);
+    return 0;
+  });
+  if (status != 0) return status;
   if (colsum_rows_out) *colsum_rows_out = first_grid / groups;
   return launch_status();
 }
@@ -2086,25 +2039,13 @@ RL8_API int rl8_lstm_wgrad_f16_f32(const float *dz, int64_t dz_pitch, const uint
                        h_bound, stream, 4);
 }
 
-// Grids of the two halves of the fused backward (both derive them from m alone,
-// so that each can zero the partial-row segments the other does not cover).
-static void fused_backward_grids(int64_t m, int *g1, int *g2) {
-  const int64_t tiles = (m + kSplitRows - 1) / kSplitRows;
-  const int64_t chunks = (m + kWsChunk - 1) / kWsChunk;
-  static const int cap = env_int("RL8_MLP_GRID_CAP");
-  const int max_grid = cap > 0 ? cap : 2 * kCUs;
-  *g1 = (int)(tiles < max_grid ? tiles : max_grid);
-  *g2 = (int)(chunks < kCUs ? chunks : kCUs);
-}
-
 RL8_API int rl8_mlp_wgrad_fused_split_f32(const float *h2, const float *dout, const float *x, const float *w1,
                                           const float *b1, const float *w3, int64_t m, int d_in, int n_out,
                                           float *workspace, float *dw2_out, float *partials, void *stream) {
   if (!h2 || !dout || !x || !w1 || !b1 || !w3 || !workspace || !dw2_out || !partials) return RL8_ENULL;
   if (m <= 0 || !rl8_mlp_backward_f16_supports(d_in, n_out)) return RL8_ESIZE;
   if (!aligned16(h2) || !aligned16(workspace) || !aligned16(dw2_out)) return RL8_EALIGN;
-  int g1, g2;
-  fused_backward_grids(m, &g1, &g2);
+  const int g1 = backward_grids(m).g1;  // (the data gradient's rows of partials; the walker's first grid is its g2)
   const int stride = (int)rl8_mlp_backward_partial_floats(d_in, n_out);
   hipStream_t s = (hipStream_t)stream;
   // Two fp16 planes per operand, three products -- unless the guard finds this call's dOut spread over too many
@@ -2115,10 +2056,7 @@ RL8_API int rl8_mlp_wgrad_fused_split_f32(const float *h2, const float *dout, co
   const bool f16 = planes != kPlanesBf16 && !(n_out == 1 && gate_kernel);
   uint32_t *bounds = nullptr;
   if (f16) {
-    bounds = n_out == 1 ? launch_wgrad_bounds<1>(s, dout, x, m, d_in, workspace)
-             : n_out == 2 ? launch_wgrad_bounds<2>(s, dout, x, m, d_in, workspace)
-             : n_out == 3 ? launch_wgrad_bounds<3>(s, dout, x, m, d_in, workspace)
-                          : launch_wgrad_bounds<4>(s, dout, x, m, d_in, workspace);
+    bounds = launch_wgrad_bounds(s, dout, x, m, d_in, n_out, workspace);
     if (!bounds) return launch_status() ? launch_status() : RL8_ESIZE;
     if (planes == kPlanesGuarded && launch_wgrad_tail(s, dout, m * n_out, bounds) != 0) return launch_status();
   }
@@ -2126,48 +2064,31 @@ RL8_API int rl8_mlp_wgrad_fused_split_f32(const float *h2, const float *dout, co
   // Segments of kWgradSegmentRows samples, summed in order (see there).  The first one
   // runs the grid the data-gradient kernel counted on (g2 rows of partials written, the
   // rest zeroed); later ones add to as many of those rows as they have workgroups.
-  for (int64_t at = 0; at < m; at += kWgradSegmentRows) {
-    const int64_t rows = m - at < kWgradSegmentRows ? m - at : kWgradSegmentRows;
-    const int64_t chunks = (rows + kWsChunk - 1) / kWsChunk;
-    const int grid = at == 0 ? g2 : (int)(chunks < g2 ? chunks : g2);
-    const WgradFusedArgs fused{dout + at * n_out, w3, partials, stride, g1, at > 0, nullptr, nullptr, bounds, guard, 0};
+  const int status = for_each_wgrad_segment(m, 1, [&](const WgradSegment &seg) {
+    const WgradFusedArgs fused{dout + seg.at * n_out, w3, partials, stride, g1, seg.later, nullptr, nullptr, bounds, guard, 0};
     WgradFusedArgs exact = fused;  // the same segment on the bf16 planes, should the guard have said so
     exact.guard_want = 1;
-    const float *h2s = h2 + at * kHidden, *xs = x + at * d_in;
-    int status = RL8_ESIZE;
-    // one output: the gate-plane kernel (three plane products per 16 samples instead of six)
-    if (n_out == 1 && gate_kernel) {
-      switch (d_in) {
-        case 1: status = launch_wgrad_gate<1>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-        case 2: status = launch_wgrad_gate<2>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-        case 3: status = launch_wgrad_gate<3>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-        case 4: status = launch_wgrad_gate<4>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-        case 5: status = launch_wgrad_gate<5>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-        case 6: status = launch_wgrad_gate<6>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-        default: status = launch_wgrad_gate<7>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-      }
-      if (status != 0) return status;
-      mlp_wgrad_split_reduce_kernel<<<kHidden * kHidden / kBlock, kBlock, 0, s>>>(workspace, grid, dw2_out, at > 0);
-      continue;
-    }
-#define RL8_WGRAD_FUSED(D, N) \
-  if (d_in == D && n_out == N) { \
-    status = f16 ? launch_wgrad_fused16<D, N>(grid, s, h2s, xs, w1, b1, rows, workspace, fused) \
-                 : launch_wgrad_fused<D, N>(grid, s, h2s, xs, w1, b1, rows, d_in, workspace, fused); \
-    if (status == 0 && guard) status = launch_wgrad_fused<D, N>(grid, s, h2s, xs, w1, b1, rows, d_in, workspace, exact); \
-  }
-    RL8_WGRAD_FUSED(1, 1) RL8_WGRAD_FUSED(1, 2) RL8_WGRAD_FUSED(1, 3) RL8_WGRAD_FUSED(1, 4)
-    RL8_WGRAD_FUSED(2, 1) RL8_WGRAD_FUSED(2, 2) RL8_WGRAD_FUSED(2, 3) RL8_WGRAD_FUSED(2, 4)
-    RL8_WGRAD_FUSED(3, 1) RL8_WGRAD_FUSED(3, 2) RL8_WGRAD_FUSED(3, 3) RL8_WGRAD_FUSED(3, 4)
-    RL8_WGRAD_FUSED(4, 1) RL8_WGRAD_FUSED(4, 2) RL8_WGRAD_FUSED(4, 3) RL8_WGRAD_FUSED(4, 4)
-    RL8_WGRAD_FUSED(5, 1) RL8_WGRAD_FUSED(5, 2) RL8_WGRAD_FUSED(5, 3) RL8_WGRAD_FUSED(5, 4)
-    RL8_WGRAD_FUSED(6, 1) RL8_WGRAD_FUSED(6, 2) RL8_WGRAD_FUSED(6, 3) RL8_WGRAD_FUSED(6, 4)
-    RL8_WGRAD_FUSED(7, 1) RL8_WGRAD_FUSED(7, 2) RL8_WGRAD_FUSED(7, 3)  // (7 x 4: rl8_mlp_backward_f16_supports)
-#undef RL8_WGRAD_FUSED
-    if (status != 0) return status;
-    mlp_wgrad_split_reduce_kernel<<<kHidden * kHidden / kBlock, kBlock, 0, s>>>(workspace, grid, dw2_out, at > 0);
-  }
-  return launch_status();
+    const float *h2s = h2 + seg.at * kHidden, *xs = x + seg.at * d_in;
+    const int st = variant_status(dispatch_width(d_in, BackwardInWidths{}, [&](auto d) {
+      // one output: the gate-plane kernel (three plane products per 16 samples instead of six)
+      if (n_out == 1 && gate_kernel) return launch_wgrad_gate<d()>(seg.grid, s, h2s, xs, w1, b1, seg.rows, workspace, fused);
+      return dispatch_width(n_out, Widths<1, 2, 3, 4>{}, [&](auto n) {
+        // 7 x 4 is not compiled: the exact kernel keeps a step's observations and dOut in scalar registers, and at that
+        // width the compiler parks the destination of a load still in flight (rl8_mlp_backward_f16_supports)
+        if constexpr (d() == 7 && n() == 4) return kNoVariant;
+        else {
+          int st = f16 ? launch_wgrad_fused16<d(), n()>(seg.grid, s, h2s, xs, w1, b1, seg.rows, workspace, fused)
+                       : launch_wgrad_fused<d(), n()>(seg.grid, s, h2s, xs, w1, b1, seg.rows, d_in, workspace, fused);
+          if (st == 0 && guard) st = launch_wgrad_fused<d(), n()>(seg.grid, s, h2s, xs, w1, b1, seg.rows, d_in, workspace, exact);
+          return st;
+        }
+      });
+    }));
+    if (st != 0) return st;
+    mlp_wgrad_split_reduce_kernel<<<kHidden * kHidden / kBlock, kBlock, 0, s>>>(workspace, seg.grid, dw2_out, seg.later);
+    return 0;
+  });
+  return status ? status : launch_status();
 }
 
 /* dout [m][2]: *flag_out (device int, zeroed here) becomes 1 unless dout[s][1] == -dout[s][0] bit for bit in every row. */
@@ -2193,30 +2114,19 @@ RL8_API int rl8_mlp_wgrad_fused_pair_f32(const float *h2, const float *dout, con
   if (!h2 || !dout || !x || !w1 || !b1 || !w3 || !workspace || !dw2_out || !partials) return RL8_ENULL;
   if (m <= 0 || !rl8_mlp_backward_f16_supports(d_in, 2)) return RL8_ESIZE;
   if (!aligned16(h2) || !aligned16(workspace) || !aligned16(dw2_out) || ((uintptr_t)dout & 7) != 0) return RL8_EALIGN;
-  int g1, g2;
-  fused_backward_grids(m, &g1, &g2);
+  const int g1 = backward_grids(m).g1;
   const int stride = (int)rl8_mlp_backward_partial_floats(d_in, 2);
   hipStream_t s = (hipStream_t)stream;
-  for (int64_t at = 0; at < m; at += kWgradSegmentRows) {  // segments summed in order, as rl8_mlp_wgrad_fused_split_f32
-    const int64_t rows = m - at < kWgradSegmentRows ? m - at : kWgradSegmentRows;
-    const int64_t chunks = (rows + kWsChunk - 1) / kWsChunk;
-    const int grid = at == 0 ? g2 : (int)(chunks < g2 ? chunks : g2);
-    const WgradFusedArgs fused{dout + at * 2, w3, partials, stride, g1, at > 0};
-    const float *h2s = h2 + at * kHidden, *xs = x + at * d_in;
-    int status;
-    switch (d_in) {
-      case 1: status = launch_wgrad_gate<1, true>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-      case 2: status = launch_wgrad_gate<2, true>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-      case 3: status = launch_wgrad_gate<3, true>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-      case 4: status = launch_wgrad_gate<4, true>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-      case 5: status = launch_wgrad_gate<5, true>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-      case 6: status = launch_wgrad_gate<6, true>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-      default: status = launch_wgrad_gate<7, true>(grid, s, h2s, xs, w1, b1, rows, workspace, fused); break;
-    }
-    if (status != 0) return status;
-    mlp_wgrad_split_reduce_kernel<<<kHidden * kHidden / kBlock, kBlock, 0, s>>>(workspace, grid, dw2_out, at > 0);
-  }
-  return launch_status();
+  const int status = for_each_wgrad_segment(m, 1, [&](const WgradSegment &seg) {
+    const WgradFusedArgs fused{dout + seg.at * 2, w3, partials, stride, g1, seg.later};
+    const int st = variant_status(dispatch_width(d_in, BackwardInWidths{}, [&](auto d) {
+      return launch_wgrad_gate<d(), true>(seg.grid, s, h2 + seg.at * kHidden, x + seg.at * d_in, w1, b1, seg.rows, workspace, fused);
+    }));
+    if (st != 0) return st;
+    mlp_wgrad_split_reduce_kernel<<<kHidden * kHidden / kBlock, kBlock, 0, s>>>(workspace, seg.grid, dw2_out, seg.later);
+    return 0;
+  });
+  return status ? status : launch_status();
 }
 
 /* The weight gradient of a rank-one head from the gate BITS alone (no h2): n_out = 1, or n_out = 2 with
@@ -2232,8 +2142,7 @@ RL8_API int rl8_mlp_wgrad_gate_bits_f32(const uint32_t *gate2, const float *dout
   if (!gate2 || !dout || !x || !w1 || !b1 || !w2 || !b2 || !w3 || !workspace || !dw2_out || !partials) return RL8_ENULL;
   if (m <= 0 || (n_out != 1 && n_out != 2) || !rl8_mlp_backward_f16_supports(d_in, n_out)) return RL8_ESIZE;
   if (!aligned16(gate2) || !aligned16(workspace) || !aligned16(dw2_out) || ((uintptr_t)dout & 7) != 0) return RL8_EALIGN;
-  int g1, g2;
-  fused_backward_grids(m, &g1, &g2);
+  const int g1 = backward_grids(m).g1;
   const int stride = (int)rl8_mlp_backward_partial_floats(d_in, n_out);
   const int off_dw3 = kHidden * d_in + 2 * kHidden;
   hipStream_t s = (hipStream_t)stream;
@@ -2243,37 +2152,29 @@ RL8_API int rl8_mlp_wgrad_gate_bits_f32(const uint32_t *gate2, const float *dout
   const bool f16 = planes != kPlanesBf16;
   uint32_t *bounds = nullptr;
   if (f16) {
-    bounds = n_out == 2 ? launch_wgrad_bounds<2>(s, dout, x, m, d_in, workspace) : launch_wgrad_bounds<1>(s, dout, x, m, d_in, workspace);
+    bounds = launch_wgrad_bounds(s, dout, x, m, d_in, n_out, workspace);
     if (!bounds) return launch_status() ? launch_status() : RL8_ESIZE;
     if (planes == kPlanesGuarded && launch_wgrad_tail(s, dout, m * n_out, bounds) != 0) return launch_status();
   }
   const uint32_t *guard = planes == kPlanesGuarded ? bounds : nullptr;
-  for (int64_t at = 0; at < m; at += kWgradSegmentRows) {  // segments summed in order, as rl8_mlp_wgrad_fused_split_f32
-    const int64_t rows = m - at < kWgradSegmentRows ? m - at : kWgradSegmentRows;
-    const int64_t chunks = (rows + kWsChunk - 1) / kWsChunk;
-    const int grid = at == 0 ? g2 : (int)(chunks < g2 ? chunks : g2);
-    const WgradFusedArgs fused{dout + at * n_out, w3, partials, stride, g1, at > 0, gate2 + at * 8, b2, bounds, guard, 0};
+  const int status = for_each_wgrad_segment(m, 1, [&](const WgradSegment &seg) {
+    const WgradFusedArgs fused{dout + seg.at * n_out, w3, partials, stride, g1, seg.later, gate2 + seg.at * 8, b2, bounds, guard, 0};
     WgradFusedArgs exact = fused;  // the same segment on the bf16 planes, should the guard have said so
     exact.guard_want = 1;
-    const float *xs = x + at * d_in;
-    int status = RL8_ESIZE;
-#define RL8_WGRAD_BITS(D) \
-  if (d_in == D) { \
-    status = f16 ? (n_out == 2 ? launch_wgrad_gate16<D, true>(grid, s, xs, w1, b1, rows, workspace, fused) \
-                               : launch_wgrad_gate16<D, false>(grid, s, xs, w1, b1, rows, workspace, fused)) \
-           : n_out == 2 ? launch_wgrad_gate<D, true, true>(grid, s, nullptr, xs, w1, b1, rows, workspace, fused) \
-                        : launch_wgrad_gate<D, false, true>(grid, s, nullptr, xs, w1, b1, rows, workspace, fused); \
-    if (status == 0 && guard) \
-      status = n_out == 2 ? launch_wgrad_gate<D, true, true>(grid, s, nullptr, xs, w1, b1, rows, workspace, exact) \
-                          : launch_wgrad_gate<D, false, true>(grid, s, nullptr, xs, w1, b1, rows, workspace, exact); \
-  }
-    RL8_WGRAD_BITS(1) RL8_WGRAD_BITS(2) RL8_WGRAD_BITS(3) RL8_WGRAD_BITS(4) RL8_WGRAD_BITS(5) RL8_WGRAD_BITS(6) RL8_WGRAD_BITS(7)
-#undef RL8_WGRAD_BITS
-    if (status != 0) return status;
-    if (n_out == 2)
-      mlp_wgrad_gate_reduce_kernel<true><<<kHidden, kBlock, 0, s>>>(workspace, grid, dw2_out, at > 0, w2, w3, partials + off_dw3);
-    else
-      mlp_wgrad_gate_reduce_kernel<false><<<kHidden, kBlock, 0, s>>>(workspace, grid, dw2_out, at > 0, w2, w3, partials + off_dw3);
-  }
-  return launch_status();
+    const float *xs = x + seg.at * d_in;
+    const int st = variant_status(dispatch_width(d_in, BackwardInWidths{}, [&](auto d) {
+      return dispatch_width(n_out, Widths<1, 2>{}, [&](auto n) {
+        constexpr bool kPair = n() == 2;
+        int st = f16 ? launch_wgrad_gate16<d(), kPair>(seg.grid, s, xs, w1, b1, seg.rows, workspace, fused)
+                     : launch_wgrad_gate<d(), kPair, true>(seg.grid, s, nullptr, xs, w1, b1, seg.rows, workspace, fused);
+        if (st == 0 && guard) st = launch_wgrad_gate<d(), kPair, true>(seg.grid, s, nullptr, xs, w1, b1, seg.rows, workspace, exact);
+        if (st != 0) return st;
+        mlp_wgrad_gate_reduce_kernel<kPair><<<kHidden, kBlock, 0, s>>>(workspace, seg.grid, dw2_out, seg.later, w2, w3,
+                                                                       partials + off_dw3);
+        return 0;
+      });
+    }));
+    return st;
+  });
+  return status ? status : launch_status();
 }

@@ -210,10 +210,9 @@ RL8_API int rl8_pw_tower_forward_f32(const float *x, int64_t m, const float *tab
   const int lds = (p + (p + 1) * (1 + 2 * n_out)) * 4;
   const int grid = grid_for(m, kBlock * 4, 8 * kCUs);
   hipStream_t s = (hipStream_t)stream;
-  static LdsOptIn opt[kPwMaxOut];
 #define RL8_PW_FWD(N) \
   if (n_out == N) { \
-    if (const int e = allow_dynamic_lds(opt[N - 1], reinterpret_cast<const void *>(&pw_forward_kernel<N>), 160 * 1024)) return e; \
+    if (const int e = allow_dynamic_lds<&pw_forward_kernel<N>>()) return e; \
     pw_forward_kernel<N><<<grid, kBlock, lds, s>>>(x, m, table, p, pw_top(p), out); \
   }
   RL8_PW_FWD(1) RL8_PW_FWD(2) RL8_PW_FWD(3)
@@ -238,10 +237,9 @@ RL8_API int rl8_pw_segment_sums_f32(const float *x, const float *dout, int64_t m
   const int64_t want = (m + kBlock * 8 - 1) / (kBlock * 8);
   const int cap = (per_cu > 8 ? 8 : per_cu) * kCUs;
   const int grid = (int)(want < 1 ? 1 : want > cap ? cap : want);
-  static LdsOptIn opt[kPwMaxOut];
 #define RL8_PW_SUMS(N) \
   if (n_out == N) { \
-    if (const int e = allow_dynamic_lds(opt[N - 1], reinterpret_cast<const void *>(&pw_segment_sums_kernel<N>), 160 * 1024)) return e; \
+    if (const int e = allow_dynamic_lds<&pw_segment_sums_kernel<N>>()) return e; \
     pw_segment_sums_kernel<N><<<grid, kBlock, lds, s>>>(x, dout, m, breaks, p, pw_top(p), bounds, acc); \
   }
   RL8_PW_SUMS(1) RL8_PW_SUMS(2) RL8_PW_SUMS(3)

@@ -680,8 +680,7 @@ template <bool DENSE>
 static int launch_pack_tiled(const PackedArgs &args, int64_t n, int64_t h, uint32_t *packed, hipStream_t stream) {
   rl8_pack_plan_t plan;
   if (const int bad = rl8_pack_plan(n, h, args.row_words, &plan)) return bad;
-  static LdsOptIn lds_pack;
-  if (const int e = allow_dynamic_lds(lds_pack, reinterpret_cast<const void *>(&pack_samples_tiled_kernel<DENSE>), 160 * 1024)) return e;
+  if (const int e = allow_dynamic_lds<&pack_samples_tiled_kernel<DENSE>>()) return e;
   pack_samples_tiled_kernel<DENSE><<<plan.grid, kBlock, plan.lds_bytes, stream>>>(n, h, packed, args, plan.tile_steps);
   return launch_status();
 }

@@ -3,6 +3,7 @@ specs, hparams validation, schedulers, batcher, stat tracker), the C-ABI library
 (loads, exports every symbol include/rl8_amd.h declares), and the "no CPU
 fallback" contract. No kernel is launched here."""
 
+import ctypes as C
 import os
 import re
 
@@ -51,6 +52,18 @@ def test_argument_checks_happen_before_any_launch():
     assert lib.rl8_dummy_env_step_f32(None, None, 1, None, 8, None) == -1
     assert lib.rl8_gae_scan_f32(None, None, None, None, 8, 4, 1, 0.9, 0.9, 1.0, 0, None, None, None) == -1
     assert lib.rl8_gather_minibatch(None, 1, 1, None, 1, None) == -1
+
+
+def test_four_gate_wgrad_rejects_a_short_segment_before_any_launch():
+    """rl8_lstm_wgrad_f16_f32 needs 128 rows in every 2^23-row segment of a call; a short LAST segment is refused before
+    the earlier ones are launched (they would add into dw_out).  The addresses are never read: nothing is launched."""
+    lib = hip.load()
+    dummy = 1 << 20  # non-null, 16-byte aligned
+    rows = C.c_int(-1)
+    for m in ((1 << 23) + 100, 127):
+        assert lib.rl8_lstm_wgrad_f16_f32(dummy, 1024, dummy, dummy, 256, dummy, m, dummy, dummy, 0, dummy, 1, dummy,
+                                          C.byref(rows), None) == -2, m  # RL8_ESIZE
+    assert rows.value == -1
 
 
 def test_cpu_tensors_are_refused_loudly():

@@ -12,6 +12,15 @@ Cases: rl8_mlp_wgrad_gate_bits_f32 at d_in 1 and 5, one output and an exact pair
 segments: the accumulate path); d_in 6 and 7 once each (scalar operands requested at the wait); the exact bf16
 planes by request at m = 65; the general mlp_wgrad_fused16_kernel
 and the LSTM's mlp_wgrad_loadh16_kernel at m = 17 and 65.
+
+The host launch code of the tower entries (grids, grid cap, segments, run-time width -> compiled variant) is held the
+same way, by a record made before it moved into rl8_amd/csrc/tower_launch.hip.h: every weight-gradient entry at every
+compiled width (m = 17: one chunk and a ragged row; the four-gate LSTM entry at 128, 129 and 2049 rows), both plane
+modes, the guard firing (the workspace's fires counter must rise by one), and the forward and data-gradient entries
+of both precisions at one width per class pair (m = 129: a tile and a row; 65536 and 65537 rows: 512 and 513 tiles
+against the grid cap of 512), with the digest of every buffer given and of the returned row count.  Widths that have
+no variant are asserted to return RL8_ESIZE.  The two-segment case of the bits entry speaks for the segment walk all
+weight-gradient entries share.
 """
 
 import importlib.util
@@ -52,8 +61,10 @@ def test_bits_are_those_of_the_record(case, record, workspace):
     again = rec.run(case, arrays, workspace)
     for k in got:
         assert torch.equal(torch.from_numpy(got[k]).view(torch.int32), torch.from_numpy(again[k]).view(torch.int32)), k
-    assert rec.digest(got["dw2"]) == str(record[case["id"] + "/dw2"]), "dW2"
-    assert rec.digest(got["small"]) == str(record[case["id"] + "/small"]), "partial rows"
+    assert {case["id"] + "/" + k for k in got} | {case["id"] + "/inputs"} == \
+        {k for k in record if k.split("/")[0] == case["id"] and not k.endswith("/dw2_full")}, "the outputs are not the recorded ones"
+    for k in got:  # (dw2: dW2; small: the partial rows or column sums; the tower entries: every buffer they were given)
+        assert rec.digest(got[k]) == str(record[case["id"] + "/" + k]), k
     if case["id"] in rec.FULL_CASES:
         want = torch.from_numpy(record[case["id"] + "/dw2_full"])
         assert torch.equal(torch.from_numpy(got["dw2"]).view(torch.int32), want.view(torch.int32))
