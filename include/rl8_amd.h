@@ -1065,6 +1065,45 @@ int rl8_mlp_narrow_backward_dx_f32(const float *x, const float *dout, int64_t m,
                                    const float *b1, const float *w2, const float *b2, const float *w3, int n_out,
                                    int hidden, float *workspace, float *dx, void *stream);
 
+/* ---- Wide-input towers: Linear(d_in, 256) ReLU Linear(256, 256) ReLU Linear(256, n_out), 17 <= d_in <= 128,
+ * 1 <= n_out <= 8 (mlp_wide_in_kernels.hip): fp32 throughout, every product but the head on v_mfma_f32_32x32x2_f32.
+ * The entries above keep their envelope (d_in <= 16); these are the widths behind it.
+ * rl8_mlp_wide_in_supports: 1 inside the envelope, else 0 (host only).
+ * rl8_mlp_wide_in_pack_w1_f32: w1 [256][d_in] (torch layout) -> w1_packed, rl8_mlp_wide_in_pack_floats(d_in) floats
+ *   (256 * 8 * ceil(d_in / 8)): MFMA fragment order, zeros past d_in.  w1_packed 16-byte aligned.
+ * rl8_mlp_wide_in_forward_f32: x [m][d_in] -> out [m][n_out]; w2_packed from rl8_mlp_pack_w2_f32(transposed = 0).
+ *   save_h1 / save_h2 ([m][256] each, 16-byte aligned): both or neither; with them the post-ReLU activations are
+ *   stored for the backward entries.
+ * rl8_mlp_wide_in_backward_f32: from h1, h2, dout [m][n_out], w3 [n_out][256] and w2t_packed
+ *   (rl8_mlp_pack_w2_f32(transposed = 1)) writes dz2_out [m][256] = (dout W3) . [h2 > 0] and dz1_out [m][256] =
+ *   (dZ2 W2) . [h1 > 0] (ReLU'(0) = 0), and one row of partials per workgroup, rl8_mlp_wide_in_partial_floats(n_out)
+ *   floats each: [db1 (256) | db2 (256) | dW3 (n_out * 256) | db3 (n_out)]; *partial_rows_out (host) rows, at most
+ *   rl8_mlp_wide_in_max_rows(), a function of m alone; the caller sums them in row order.  No gradient of x.
+ *   h1, h2, dz1_out, dz2_out, w2t_packed 16-byte aligned.
+ * rl8_mlp_wide_in_wgrad_f32: dw1_out [256][d_in] = (accumulate ? dw1_out : 0) + dz1^T x over the m rows, fp32 MFMA,
+ *   one slab per workgroup in `workspace` (rl8_mlp_wide_in_workspace_bytes(d_in) bytes, no initialisation) summed in
+ *   slab order; the grid is a function of m alone: bitwise reproducible.  dz1 16-byte aligned.
+ *   (dW2 = dz2^T h1 is rl8_mlp_wgrad_split_strided_f32 or rl8_mlp_wgrad_f32: both take their operands from memory.)
+ * rl8_mlp_wide_in_lds_bytes: the dynamic LDS of one workgroup of kernel 0 (forward, two workgroups per CU), 1 (data
+ *   gradient, two per CU) or 2 (weight gradient at d_in, one per CU); host only.
+ * Every other pointer 4-byte aligned; RL8_ENULL / RL8_ESIZE (m < 1, d_in or n_out outside the envelope) / RL8_EALIGN
+ * before any launch.  The helpers return RL8_ESIZE for a width outside the envelope. */
+int rl8_mlp_wide_in_supports(int d_in, int n_out);
+int64_t rl8_mlp_wide_in_lds_bytes(int kernel, int d_in);
+int64_t rl8_mlp_wide_in_pack_floats(int d_in);
+int rl8_mlp_wide_in_pack_w1_f32(const float *w1, int d_in, float *w1_packed, void *stream);
+int rl8_mlp_wide_in_forward_f32(const float *x, int64_t m, int d_in, const float *w1_packed, const float *b1,
+                                const float *w2_packed, const float *b2, const float *w3, const float *b3, int n_out,
+                                float *out, float *save_h1, float *save_h2, void *stream);
+int64_t rl8_mlp_wide_in_partial_floats(int n_out);
+int rl8_mlp_wide_in_max_rows(void);
+int rl8_mlp_wide_in_backward_f32(const float *h1, const float *h2, const float *dout, int64_t m,
+                                 const float *w2t_packed, const float *w3, int n_out, float *dz1_out, float *dz2_out,
+                                 float *partials, int *partial_rows_out /*host*/, void *stream);
+int64_t rl8_mlp_wide_in_workspace_bytes(int d_in);
+int rl8_mlp_wide_in_wgrad_f32(const float *dz1, const float *x, int64_t m, int d_in, float *workspace, float *dw1_out,
+                              int accumulate, void *stream);
+
 /* ---- BatchNorm1d behind the first layer of a narrow tower, folded into that layer (batchnorm_tower_kernels.hip).  In
  * training mode the norm of z1 = x W1^T + b1 over the batch is an affine map of x: with mu = mean_i x_i and the biased
  * covariance C = (1/m) sum_i (x_i - mu)(x_i - mu)^T, unit j has batch mean m_z_j = W1_j . mu + b1_j, batch variance

@@ -255,6 +255,16 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_mlp_narrow_backward_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "rl8_mlp_narrow_reduce_f32": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
     "rl8_mlp_narrow_backward_dx_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "rl8_mlp_wide_in_supports": [_i32, _i32],
+    "rl8_mlp_wide_in_lds_bytes": [_i32, _i32],
+    "rl8_mlp_wide_in_pack_floats": [_i32],
+    "rl8_mlp_wide_in_pack_w1_f32": [_vp, _i32, _vp, _vp],
+    "rl8_mlp_wide_in_forward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    "rl8_mlp_wide_in_partial_floats": [_i32],
+    "rl8_mlp_wide_in_max_rows": [],
+    "rl8_mlp_wide_in_backward_f32": [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(C.c_int), _vp],
+    "rl8_mlp_wide_in_workspace_bytes": [_i32],
+    "rl8_mlp_wide_in_wgrad_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp],
     "rl8_tower_limits": [C.POINTER(C.c_int)],
     "rl8_tower_moments_workspace_bytes": [_i64, _i32],
     "rl8_tower_moments_f64": [_vp, _i64, _i32, _vp, _vp, _vp, _vp],
@@ -311,7 +321,9 @@ def load() -> C.CDLL:
                             "rl8_mlp_f16_packed_bytes", "rl8_lstm_rows_backward_pack_bytes", "rl8_pw_workspace_bytes",
                             "rl8_mlp_narrow_workspace_bytes", "rl8_lstm_narrow_workspace_bytes",
                             "rl8_lstm_stack_workspace_bytes", "rl8_linear_heads_narrow_workspace_bytes",
-                            "rl8_feedforward_workspace_floats", "rl8_tower_moments_workspace_bytes")
+                            "rl8_feedforward_workspace_floats", "rl8_tower_moments_workspace_bytes",
+                            "rl8_mlp_wide_in_pack_floats", "rl8_mlp_wide_in_partial_floats", "rl8_mlp_wide_in_lds_bytes",
+                            "rl8_mlp_wide_in_workspace_bytes")
                 else C.c_int
             )
         built = int(lib.rl8_abi_version(None, 0))
@@ -1854,18 +1866,30 @@ def mlp_wgrad_split(dz2: torch.Tensor, x: torch.Tensor, w1: torch.Tensor, b1: to
     return out
 
 
-def mlp_wgrad(dz2: torch.Tensor, h1: torch.Tensor) -> torch.Tensor:
-    """dW2 [256, 256] = dz2^T @ h1 over the rows (fp32 MFMA, deterministic)."""
+def mlp_wgrad(dz2: torch.Tensor, h1: torch.Tensor, *, out: None | torch.Tensor = None,
+              accumulate: bool = False, planes: bool = False) -> torch.Tensor:
+    """dW2 [256, 256] = dz2^T @ h1 over the rows (fp32 MFMA, deterministic).  ``out`` with ``accumulate``: added to
+    what ``out`` holds (the segments of a long batch, in order).  ``planes``: the same product, both operands from
+    memory, on three exact bf16 planes per operand (``rl8_mlp_wgrad_split_strided_f32``: fp32 accuracy, deterministic)."""
     _dense(dz2, torch.float32, "dz2")
     _dense(h1, torch.float32, "h1")
     if dz2.shape != h1.shape or dz2.shape[1] != MLP_HIDDEN:
         raise ValueError("dz2 and h1 must both be [M, 256]")
     lib = load()
     ws = _wgrad_workspace(dz2.device)
-    out = torch.empty(MLP_HIDDEN, MLP_HIDDEN, dtype=torch.float32, device=dz2.device)
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs out")
+        out = torch.empty(MLP_HIDDEN, MLP_HIDDEN, dtype=torch.float32, device=dz2.device)
+    _shaped(out, (MLP_HIDDEN, MLP_HIDDEN), "out")
     with _timed("mlp_wgrad", dz2.shape[0]):
-        _check(lib.rl8_mlp_wgrad_f32(_ptr(dz2), _ptr(h1), dz2.shape[0], _ptr(ws), _ptr(out), 0, _stream()),
-               "rl8_mlp_wgrad_f32")
+        if planes:
+            _check(lib.rl8_mlp_wgrad_split_strided_f32(_ptr(dz2), MLP_HIDDEN, _ptr(h1), MLP_HIDDEN, dz2.shape[0], _ptr(ws),
+                                                       _ptr(out), int(accumulate), None, 0, None, None, _stream()),
+                   "rl8_mlp_wgrad_split_strided_f32")
+        else:
+            _check(lib.rl8_mlp_wgrad_f32(_ptr(dz2), _ptr(h1), dz2.shape[0], _ptr(ws), _ptr(out), int(accumulate), _stream()),
+                   "rl8_mlp_wgrad_f32")
     return out
 
 
@@ -1944,6 +1968,111 @@ def mlp_narrow_backward(x: torch.Tensor, dout: torch.Tensor, w1: torch.Tensor, b
     if dx is not None:
         got["x"] = dx
     return got
+
+
+# --------------------------------------------------------------------------- #
+# Wide-input towers: hidden width 256, 17 to 128 inputs (mlp_wide_in_kernels.hip).
+# --------------------------------------------------------------------------- #
+def mlp_wide_in_supports(d_in: int, n_out: int) -> bool:
+    return bool(load().rl8_mlp_wide_in_supports(int(d_in), int(n_out)))
+
+
+def mlp_wide_in_pack_w1(w1: torch.Tensor) -> torch.Tensor:
+    """[256, d_in] nn.Linear weight -> MFMA fragment order, zero-padded to whole k-groups of 8."""
+    w1 = _dense(w1.detach(), torch.float32, "w1")
+    if w1.ndim != 2 or w1.shape[0] != MLP_HIDDEN:
+        raise ValueError("w1 must be [256, d_in]")
+    lib = load()
+    floats = int(lib.rl8_mlp_wide_in_pack_floats(w1.shape[1]))
+    if floats < 0:
+        raise ValueError(f"no wide-input tower kernel for d_in={w1.shape[1]}")
+    packed = torch.empty(floats, dtype=torch.float32, device=w1.device)
+    _check(lib.rl8_mlp_wide_in_pack_w1_f32(_ptr(w1), w1.shape[1], _ptr(packed), _stream()), "rl8_mlp_wide_in_pack_w1_f32")
+    return packed
+
+
+def mlp_wide_in_forward(
+    x: torch.Tensor, w1_packed: torch.Tensor, b1: torch.Tensor, w2_packed: torch.Tensor, b2: torch.Tensor,
+    w3: torch.Tensor, b3: torch.Tensor, *, save: bool = False,
+) -> tuple[torch.Tensor, None | torch.Tensor, None | torch.Tensor]:
+    """x [M, d_in], 17 <= d_in <= 128 -> out [M, n_out]; with ``save`` also the post-ReLU activations h1, h2 ([M, 256])
+    for the backward pass.  ``w1_packed`` from ``mlp_wide_in_pack_w1``, ``w2_packed`` from ``mlp_pack_w2``."""
+    x = _dense(x.detach(), torch.float32, "x")
+    if x.ndim != 2:
+        raise ValueError("x must be [M, d_in]")
+    m, d_in = x.shape
+    n_out = w3.shape[0]
+    for name, t, shape in (("b1", b1, (MLP_HIDDEN,)), ("b2", b2, (MLP_HIDDEN,)), ("w3", w3, (n_out, MLP_HIDDEN)),
+                           ("b3", b3, (n_out,))):
+        _shaped(t, shape, name)
+    lib = load()
+    if m < 1 or not mlp_wide_in_supports(d_in, n_out):
+        raise ValueError(f"no wide-input tower kernel for m={m}, d_in={d_in}, n_out={n_out}")
+    if w1_packed.numel() != int(lib.rl8_mlp_wide_in_pack_floats(d_in)) or w1_packed.dtype != torch.float32:
+        raise ValueError("w1_packed must come from mlp_wide_in_pack_w1 for this d_in")
+    if w2_packed.numel() != MLP_HIDDEN * MLP_HIDDEN or w2_packed.dtype != torch.float32:
+        raise ValueError("w2_packed must come from mlp_pack_w2")
+    out = torch.empty(m, n_out, dtype=torch.float32, device=x.device)
+    h1 = torch.empty(m, MLP_HIDDEN, dtype=torch.float32, device=x.device) if save else None
+    h2 = torch.empty(m, MLP_HIDDEN, dtype=torch.float32, device=x.device) if save else None
+    with _timed("mlp_wide_in_forward_save" if save else "mlp_wide_in_forward", m):
+        _check(lib.rl8_mlp_wide_in_forward_f32(_ptr(x), m, d_in, _ptr(w1_packed), _ptr(b1.detach()), _ptr(w2_packed),
+                                               _ptr(b2.detach()), _ptr(w3.detach()), _ptr(b3.detach()), n_out, _ptr(out),
+                                               _ptr(h1), _ptr(h2), _stream()),
+               "rl8_mlp_wide_in_forward_f32")
+    return out, h1, h2
+
+
+def mlp_wide_in_backward(h1: torch.Tensor, h2: torch.Tensor, dout: torch.Tensor, w2t_packed: torch.Tensor,
+                         w3: torch.Tensor, dz1: torch.Tensor, dz2: torch.Tensor, partials: torch.Tensor) -> int:
+    """The data gradient of the ``rows`` = ``h1.shape[0]`` rows: fills ``dz1`` / ``dz2`` ([rows, 256]) and the first
+    rows of ``partials`` ([rl8_mlp_wide_in_max_rows, 512 + 257 n_out]: db1 | db2 | dW3 | db3 per workgroup); returns how
+    many partial rows were written."""
+    rows, n_out = h1.shape[0], w3.shape[0]
+    if rows < 1 or not 1 <= n_out <= MLP_MAX_OUT:
+        raise ValueError(f"no wide-input tower kernel for m={rows}, n_out={n_out}")
+    lib = load()
+    width = int(lib.rl8_mlp_wide_in_partial_floats(n_out))
+    for name, t, shape in (("h1", h1, (rows, MLP_HIDDEN)), ("h2", h2, (rows, MLP_HIDDEN)), ("dout", dout, (rows, n_out)),
+                           ("w3", w3, (n_out, MLP_HIDDEN)), ("dz1", dz1, (rows, MLP_HIDDEN)), ("dz2", dz2, (rows, MLP_HIDDEN)),
+                           ("partials", partials, (int(lib.rl8_mlp_wide_in_max_rows()), width))):
+        _shaped(t, shape, name)
+    if w2t_packed.numel() != MLP_HIDDEN * MLP_HIDDEN or w2t_packed.dtype != torch.float32:
+        raise ValueError("w2t_packed must come from mlp_pack_w2(..., transposed=True)")
+    written = C.c_int(0)
+    with _timed("mlp_wide_in_backward", rows):
+        _check(lib.rl8_mlp_wide_in_backward_f32(_ptr(h1), _ptr(h2), _ptr(dout), rows, _ptr(w2t_packed), _ptr(w3.detach()),
+                                                n_out, _ptr(dz1), _ptr(dz2), _ptr(partials), C.byref(written), _stream()),
+               "rl8_mlp_wide_in_backward_f32")
+    return written.value
+
+
+_wide_in_ws: dict[tuple[int, int], torch.Tensor] = {}
+
+
+def mlp_wide_in_wgrad(dz1: torch.Tensor, x: torch.Tensor, out: None | torch.Tensor = None, *,
+                      accumulate: bool = False) -> torch.Tensor:
+    """dW1 [256, d_in] = dz1^T @ x over the M rows (fp32 MFMA, deterministic).  ``out`` with ``accumulate``: added to
+    what ``out`` holds (the segments of a long batch, in order)."""
+    x = _dense(x.detach(), torch.float32, "x")
+    if x.ndim != 2:
+        raise ValueError("x must be [M, d_in]")
+    m, d_in = x.shape
+    _shaped(dz1, (m, MLP_HIDDEN), "dz1")
+    if m < 1 or not mlp_wide_in_supports(d_in, 1):
+        raise ValueError(f"no wide-input tower kernel for m={m}, d_in={d_in}")
+    lib = load()
+    nbytes = int(lib.rl8_mlp_wide_in_workspace_bytes(128))
+    ws = _per_stream(_wide_in_ws, x.device, lambda: torch.empty(nbytes // 4, dtype=torch.float32, device=x.device))
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs out")
+        out = torch.empty(MLP_HIDDEN, d_in, dtype=torch.float32, device=x.device)
+    _shaped(out, (MLP_HIDDEN, d_in), "out")
+    with _timed("mlp_wide_in_wgrad", m):
+        _check(lib.rl8_mlp_wide_in_wgrad_f32(_ptr(dz1), _ptr(x), m, d_in, _ptr(ws), _ptr(out), int(accumulate), _stream()),
+               "rl8_mlp_wide_in_wgrad_f32")
+    return out
 
 
 # --------------------------------------------------------------------------- #

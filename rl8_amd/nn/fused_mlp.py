@@ -21,6 +21,11 @@ two towers of ``MLPTrader`` and ``TransformerTrader``) run on those kernels too,
 second moments of x (``_NarrowBatchNormTower``; the algebra stands above it, and
 ``batchnorm_tower_reference`` is its torch expression).
 
+Width-256 towers whose first layer reads 17 to 128 floats (family "wide input",
+``mlp_wide_in_kernels.hip``, ``_WideInputTower``) run in fp32 MFMA throughout: layer 1 too is
+a matrix-core product, the forward saves h1 and h2, and the backward walks the rows in
+segments (dW2 alone on exact bf16 planes, ``WIDE_INPUT_DW2_PLANES``).  ``RL8_AMD_WIDE_INPUT_TOWERS=0`` sends them to the torch modules.
+
 ``tower_forward`` falls back to the module's own eager path whenever the tower
 is none of these shapes (other widths, activations, other norm layers, non-HIP or
 non-fp32 inputs), so custom models are unaffected.
@@ -751,6 +756,128 @@ def _batchnorm_tower_forward(l1: nn.Linear, norm: nn.BatchNorm1d, l2: nn.Linear,
     return _NarrowBatchNormTower.apply(x, *params, norm)
 
 
+# --------------------------------------------------------------------------- #
+# Wide-input towers: width 256 behind 17 to 128 inputs (mlp_wide_in_kernels.hip), fp32 MFMA throughout.  Never
+# recorded or replayed for the rollout (no planes), and no input gradient: a call whose x asks for one is declined.
+# --------------------------------------------------------------------------- #
+#: Rows per segment of the wide-input backward: dZ1 and dZ2 ([rows, 256] fp32 each) are scratch of one segment, so
+#: the two together never exceed 2 GiB however long the minibatch is.  Read on every call.
+WIDE_INPUT_SEGMENT_ROWS = 1 << 20
+#: dW2 = dZ2^T h1 of the wide-input backward on three exact bf16 planes per operand (``rl8_mlp_wgrad_split_strided_f32``:
+#: 0.67 against 1.03 ms per 2^20 rows at the same fp64 bars); False: ``rl8_mlp_wgrad_f32``.  Read on
+#: every call.
+WIDE_INPUT_DW2_PLANES = True
+
+
+def wide_input_towers_on() -> bool:
+    """``RL8_AMD_WIDE_INPUT_TOWERS=0`` (read on every call) sends the wide-input towers to the torch modules: the
+    tests' yardstick.  On by default."""
+    return os.environ.get("RL8_AMD_WIDE_INPUT_TOWERS", "1") != "0"
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_input_supported(d_in: int, n_out: int) -> bool:
+    """Compiled for this width: fixed by the build, asked once per width."""
+    return hip.mlp_wide_in_supports(d_in, n_out)
+
+
+def _wide_input_family(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[nn.Linear, nn.Linear]:
+    """(layer1, layer2) if ``trunk`` is the structure ``_family`` calls "wide" -- ``Sequential(MLP(Linear, ReLU,
+    Linear), ReLU)`` at width 256 with biased layers and biased heads (one at least) that read it -- whose first layer
+    reads MORE than ``hip.MLP_MAX_IN`` floats, up to what ``hip.mlp_wide_in_supports`` takes; else ``None``."""
+    if not isinstance(trunk, nn.Sequential) or len(trunk) < 2:
+        return None
+    mlp, act = trunk[0], trunk[1]
+    if not isinstance(mlp, nn.Sequential) or len(mlp) != 3 or not isinstance(act, nn.ReLU):
+        return None
+    l1, a1, l2 = mlp[0], mlp[1], mlp[2]
+    if not (isinstance(l1, nn.Linear) and isinstance(a1, nn.ReLU) and isinstance(l2, nn.Linear)):
+        return None
+    width = hip.MLP_HIDDEN
+    if l1.out_features != width or l2.in_features != width or l2.out_features != width:
+        return None
+    if l1.in_features <= hip.MLP_MAX_IN or l1.bias is None or l2.bias is None:
+        return None
+    if not heads or any(h.bias is None or h.in_features != width for h in heads):
+        return None
+    n_out = sum(h.out_features for h in heads)
+    if n_out > hip.MLP_MAX_OUT or not _wide_input_supported(l1.in_features, n_out):
+        return None
+    return l1, l2
+
+
+def _packed_w1(layer: nn.Linear) -> torch.Tensor:
+    """``hip.mlp_wide_in_pack_w1(layer.weight)``, cached on the layer as ``_packed`` caches W2: re-made when the
+    optimizer has changed the weight (version counter) or the weight tensor has been replaced / moved."""
+    w1 = layer.weight
+    hit = layer.__dict__.get("_rl8_w1_pack")
+    if hit is not None and hit[0] == w1._version and hit[1] == w1.data_ptr():
+        return hit[2]
+    packed = hip.mlp_wide_in_pack_w1(w1)
+    layer.__dict__["_rl8_w1_pack"] = (w1._version, w1.data_ptr(), packed)
+    return packed
+
+
+class _WideInputTower(torch.autograd.Function):
+    """A wide-input tower: one forward kernel (which stores h1 and h2 when a backward can follow); the backward walks
+    the rows in segments of ``WIDE_INPUT_SEGMENT_ROWS`` -- per segment the data gradient (dZ1, dZ2 into scratch, one
+    row of small-gradient partials per workgroup), dW1 += dZ1^T x and dW2 += dZ2^T h1 (``WIDE_INPUT_DW2_PLANES``) -- in
+    order, so the sums are the same bits from run to run."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3, layer1, layer2, grad_mode):  # type: ignore[override]
+        # (grad_mode: the caller's; inside forward() grad mode is always off -- see _FusedTower)
+        need_grad = grad_mode and any(ctx.needs_input_grad[1:7])
+        out, h1, h2 = hip.mlp_wide_in_forward(x, _packed_w1(layer1), b1, _packed(layer2, False, False), b2, w3, b3,
+                                              save=need_grad)
+        if need_grad:
+            ctx.layer2 = layer2
+            # (w1 and w2 are saved although the kernels read packed copies: autograd's version check then refuses a
+            # backward after an in-place change of a weight, as it would for the eager modules)
+            ctx.save_for_backward(x, h1, h2, w3, w1, w2)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):  # type: ignore[override]
+        x, h1, h2, w3, w1, w2 = ctx.saved_tensors
+        dout = dout.contiguous().float()
+        m, n_out, hidden = x.shape[0], w3.shape[0], hip.MLP_HIDDEN
+        segment, planes = max(int(WIDE_INPUT_SEGMENT_ROWS), 1), bool(WIDE_INPUT_DW2_PLANES)
+        w2t = _packed(ctx.layer2, True, False)
+        dz1 = torch.empty(min(m, segment), hidden, dtype=torch.float32, device=x.device)
+        dz2 = torch.empty_like(dz1)
+        partials = torch.empty(hip.load().rl8_mlp_wide_in_max_rows(), 2 * hidden + n_out * hidden + n_out,
+                               dtype=torch.float32, device=x.device)
+        dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+        small = None
+        for at in range(0, m, segment):
+            rows = slice(at, min(at + segment, m))
+            z1, z2 = dz1[: rows.stop - at], dz2[: rows.stop - at]
+            written = hip.mlp_wide_in_backward(h1[rows], h2[rows], dout[rows], w2t, w3, z1, z2, partials)
+            part = partials[:written].sum(0)
+            small = part if small is None else small + part
+            hip.mlp_wide_in_wgrad(z1, x[rows], dw1, accumulate=at > 0)
+            hip.mlp_wgrad(z2, h1[rows], out=dw2, accumulate=at > 0, planes=planes)
+        db1, db2, dw3, db3 = torch.split(small, (hidden, hidden, n_out * hidden, n_out))
+        return None, dw1, db1, dw2, db2, dw3.view(n_out, hidden), db3, None, None, None
+
+
+def _wide_input_tower_forward(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear], x: torch.Tensor) -> None | torch.Tensor:
+    """The wide-input route, or ``None`` when this call is not its: the switch off, autocast, an ``x`` that is not dense
+    or is empty or asks for its gradient (the family forms none, and must not drop one silently), parameters that are
+    not float32 on the device."""
+    if not wide_input_towers_on() or torch.is_autocast_enabled() or not x.is_contiguous() or x.shape[0] < 1:
+        return None
+    if x.shape[1] != l1.in_features or (x.requires_grad and torch.is_grad_enabled()):
+        return None
+    w3 = heads[0].weight if len(heads) == 1 else torch.cat([h.weight for h in heads], 0)
+    b3 = heads[0].bias if len(heads) == 1 else torch.cat([h.bias for h in heads], 0)
+    params = (l1.weight, l1.bias, l2.weight, l2.bias, w3, b3)
+    if not all(p.is_cuda and p.dtype == torch.float32 and p.device == x.device for p in params):
+        return None
+    return _WideInputTower.apply(x, *params, l1, l2, torch.is_grad_enabled())
+
+
 def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Tensor, *,
                   pair_gradients: None | bool = None) -> None | torch.Tensor:
     """``cat([head(trunk(x)) for head in heads], -1)`` through the fused kernels,
@@ -764,7 +891,10 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
     if not ENABLED or not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
         return None
     found = _family(trunk, heads)
-    if found is None or x.shape[1] != found[1].in_features:
+    if found is None:  # (only then: the wide-input family begins where _family's input limit ends)
+        wide = _wide_input_family(trunk, heads)
+        return None if wide is None else _wide_input_tower_forward(*wide, heads, x)
+    if x.shape[1] != found[1].in_features:
         return None
     family, l1, l2 = found
     if family == "narrow_bn" and not batchnorm_towers_on():  # (opt-in: nothing else is done for it while it is off)
