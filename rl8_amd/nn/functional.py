@@ -335,6 +335,10 @@ def ppo_losses(
         Tensordict with scalar ``"entropy"``, ``"policy"``, ``"vf"``, ``"total"``;
         ``total.backward()`` propagates into the features and the values.
 
+    Raises:
+        ValueError: under grad mode, with a built-in distribution, a column of ``buffer_batch`` requires a gradient
+            (the fused loss forms none for buffer data).
+
     """
     values = sample_batch[DataKeys.VALUES]
     _require_hip(values, "values")
@@ -342,6 +346,15 @@ def ppo_losses(
     device = values.device
     if has_fused_loss(dist_cls):
         m = values.shape[0]
+        if torch.is_grad_enabled():
+            # (the loss kernels form gradients for the features and the values alone: a buffer column that asks for
+            # one is refused here, before any launch, never answered with ``None``)
+            for key in (DataKeys.ACTIONS, DataKeys.LOGP, DataKeys.ADVANTAGES, DataKeys.RETURNS):
+                if buffer_batch[key].requires_grad:
+                    raise ValueError(
+                        f"buffer_batch[{key!r}] requires a gradient, which the fused PPO loss does not form: it is"
+                        " rollout-buffer data here. Detach it, or compose the loss from torch operations."
+                    )
         need_grad = torch.is_grad_enabled() and (
             values.requires_grad
             or any(f.requires_grad for f in sample_distribution.features.values())
@@ -632,7 +645,8 @@ def masked_categorical_sample(
     """
     if (
         x.dim() == 2 and dim % 2 == 1 and _kernel_input(x) and _kernel_mask(mask, x.shape)
-        and (noise is None or (_kernel_input(noise) and noise.shape == x.shape))
+        # (a noise that asks for a gradient goes to the torch expression: the node forms none for it)
+        and (noise is None or (_kernel_input(noise) and noise.shape == x.shape and not _wants_grad(noise)))
     ):
         seed = step = row_offset = 0
         if noise is None:

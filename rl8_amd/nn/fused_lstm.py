@@ -29,7 +29,9 @@ forms the heads' data gradient itself (``lstm_heads_forward``); the reference's 
 The "narrow" and "stack" families return the gradient of their input ``x`` where it requires one -- a model with
 learned parameters in front of the LSTM, such as ``rl8_amd.envs.LSTMTrader``'s embedding -- from one more launch on
 the gate gradients the backward through time has left (``rl8_lstm_narrow_input_grad_f32``); an ``x`` that is
-rollout-buffer data costs nothing. The "256" family forms no input gradient.
+rollout-buffer data costs nothing. The "256" family forms no input gradient and declines an ``x`` that requires one
+under grad mode; no family forms a gradient for the initial states ``h0`` / ``c0``, and every entry point declines
+a call in which one of them requires it (``_declines``). The caller then runs the module, which forms them.
 
 """
 
@@ -93,6 +95,13 @@ def _input_ok(lstm: nn.LSTM, x: torch.Tensor) -> bool:
 def _family_for(lstm: nn.LSTM, x: torch.Tensor) -> None | str:
     """``_family(lstm)`` where ``x`` is an input its kernels take, else ``None``: all an entry point asks."""
     return _family(lstm) if _input_ok(lstm, x) else None
+
+
+def _declines(family: None | str, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor) -> bool:
+    """A gradient is asked for that ``family``'s node does not form -- of ``h0`` or ``c0`` (any family), of ``x`` at
+    "256" -- and grad mode is on: the entry returns ``None`` instead of handing autograd a ``None`` for it.  Three
+    attribute reads for rollout-buffer data; under ``torch.no_grad()`` nothing can follow and nothing is declined."""
+    return (h0.requires_grad or c0.requires_grad or (family == "256" and x.requires_grad)) and torch.is_grad_enabled()
 
 
 def _packs(lstm: nn.LSTM, kind: str):
@@ -325,8 +334,9 @@ def lstm_stack_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: tor
     [B, layers, H] (the rollout buffer's layout) -> ``(hs_top [B, L, H], h_n [B, layers, H], c_n [B, layers, H])``,
     or ``None`` when this LSTM / input is not eligible (one layer, other widths, d > 16, no bias, dropout,
     projections, bidirectional, non-HIP / non-fp32 inputs). ``x`` receives its gradient where it requires one (layer
-    0's dz x W_ih, one more launch); none flows to ``h0``, ``c0`` nor out of ``h_n``, ``c_n``."""
-    if _family_for(lstm, x) != "stack":
+    0's dz x W_ih, one more launch); none flows out of ``h_n``, ``c_n``, and a call whose ``h0`` or ``c0`` requires a
+    gradient under grad mode is declined (``None``)."""
+    if _family_for(lstm, x) != "stack" or _declines("stack", x, h0, c0):
         return None
     weights = [getattr(lstm, f"{name}_l{k}") for k in range(lstm.num_layers) for name in _STACK_PARAMS]
     hs, hn, cn = _StackLSTM.apply(
@@ -340,12 +350,15 @@ def lstm_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Ten
     """``lstm(x, (h0[None], c0[None]))`` for ``x`` [B, L, d], ``h0`` / ``c0`` [B, H]
     through the fused kernels: ``(hs [B, L, H], h_n [B, H], c_n [B, H])``, or
     ``None`` when this LSTM / input is not eligible (H = 256 with d <= 7, or H = 64 /
-    128 with d <= 16). No gradient flows to ``h0``, ``c0`` (rollout-buffer data) nor
-    out of ``c_n``. At H = 64 / 128 ``x`` receives its gradient where it requires one
-    (an encoder in front of the LSTM: one more launch, dz x W_ih); at H = 256 no
-    gradient flows to ``x``."""
+    128 with d <= 16). No gradient flows out of ``c_n``; ``h0`` / ``c0`` are rollout-buffer
+    data, and a call in which one of them requires a gradient under grad mode is declined
+    (``None``). At H = 64 / 128 ``x`` receives its gradient where it requires one (an
+    encoder in front of the LSTM: one more launch, dz x W_ih); at H = 256 the entry
+    declines such an ``x`` under grad mode."""
     family = _family_for(lstm, x)
     if family not in ("256", "narrow"):  # (a stack has its own entry and state layout: lstm_stack_forward)
+        return None
+    if _declines(family, x, h0, c0):
         return None
     args = (x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
             lstm.bias_ih_l0, lstm.bias_hh_l0)
@@ -423,9 +436,10 @@ def lstm_heads_forward(lstm: nn.LSTM, heads: list[nn.Linear], x: torch.Tensor, h
     ``([head_i(hs) as [B * L, n_i]], hs [B, L, H], h_n, c_n)``, or ``None`` when this combination is not eligible (no
     gradient wanted, a stack, more than four head outputs, the heads switched off or -- at 256 -- a plan that does not
     fuse them): the caller then runs :func:`lstm_forward` / :func:`lstm_stack_forward` and :func:`heads_forward`.
-    The gradient of ``x`` is as in :func:`lstm_forward`: formed at H = 64 / 128 where ``x`` requires it, none at 256."""
+    The gradient of ``x`` is as in :func:`lstm_forward`: formed at H = 64 / 128 where ``x`` requires it; at 256 the
+    entry declines such an ``x``, and at every width an ``h0`` or ``c0`` that requires a gradient."""
     family = _family_for(lstm, x) if torch.is_grad_enabled() else None
-    if family not in ("256", "narrow"):
+    if family not in ("256", "narrow") or _declines(family, x, h0, c0):
         return None
     plan = _plan(lstm.input_size, x.shape[0]) if family == "256" else None  # (the narrow family reads no plan)
     if not ((FUSE_HEADS if plan is None else plan.fuse_heads)

@@ -502,7 +502,9 @@ class replay:
             plan: _TowerPlan) -> None | _RecordedRows:
         """The recorded rows that stand for this tower call (the context's own ``x``, the recorded parameters), or ``None``."""
         got = self.rows.get(id(l2))
-        ok = (got is not None and x.data_ptr() == self.x.data_ptr() and x.shape == self.x.shape and x.is_contiguous()
+        # (an x that asks for its gradient is never replayed: ``_ReplayedTower`` forms none, see ``tower_forward``)
+        ok = (got is not None and not (x.requires_grad and torch.is_grad_enabled())
+              and x.data_ptr() == self.x.data_ptr() and x.shape == self.x.shape and x.is_contiguous()
               and got.key == _param_key(_tower_params(l1, l2, heads))
               and got.out.shape == (x.shape[0], n_out)
               and (got.h2 is not None or plan.gate_only))  # (a record without h2 serves rank-one calls)
@@ -887,7 +889,12 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
     ``pair_gradients`` (two-output towers only): ``True`` -- the caller expects the two outputs' gradients to be
     exact negatives (a two-way categorical under the fused loss), so the forward keeps the gate bits of h2 alone;
     ``False`` -- h2 is stored; ``None`` -- whatever this tower's previous backward found (a tower used outside
-    ``Algorithm``). Checked on the device in the backward either way."""
+    ``Algorithm``). Checked on the device in the backward either way.
+
+    The gradient of ``x``: the narrow families (64 / 128, with or without the BatchNorm) form it where ``x`` requires
+    one, from the same backward launch.  The 256-wide families -- the default kernels, the rollout replay, the
+    piecewise tables, the wide-input kernels -- form none and DECLINE such a call under grad mode (``None``: the caller
+    runs the modules, which form it); under ``torch.no_grad()`` no gradient can follow and the kernels run."""
     if not ENABLED or not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
         return None
     found = _family(trunk, heads)
@@ -897,6 +904,8 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
     if x.shape[1] != found[1].in_features:
         return None
     family, l1, l2 = found
+    if family == "wide" and x.requires_grad and torch.is_grad_enabled():
+        return None  # (no 256-wide route forms dL/dx, and none may drop it silently: one attribute read for buffer data)
     if family == "narrow_bn" and not batchnorm_towers_on():  # (opt-in: nothing else is done for it while it is off)
         return None
     # opt-in prototype: scalar observations from an exact piecewise-linear table

@@ -123,8 +123,9 @@ class _PiecewiseTower(torch.autograd.Function):
 
 
 def tower_forward(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear], x: torch.Tensor) -> None | torch.Tensor:
-    """``cat([head(trunk(x))])`` from the tower's table, or None (not a scalar observation, table too large)."""
-    if x.shape[1] != 1 or l1.in_features != 1:
+    """``cat([head(trunk(x))])`` from the tower's table, or None (not a scalar observation, table too large, or an
+    ``x`` that asks for its gradient under grad mode: the table route forms none and must not drop one silently)."""
+    if x.shape[1] != 1 or l1.in_features != 1 or (x.requires_grad and torch.is_grad_enabled()):
         return None
     table = _table_of(l1, l2, heads)
     if table is None:

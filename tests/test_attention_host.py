@@ -74,7 +74,9 @@ def test_attention_entries_refuse_bad_arguments_before_launching():
             assert forward(**{name: bad}) == -2, name
             assert backward(**{name: bad}) == -2, name
     for name in ("q_stride", "kv_stride"):
-        assert forward(**{name: 7}) == -2 and forward(**{name: 8}) != -2, name
+        # (a stride of exactly heads * d passes the size check: shown by the NEXT refusal, RL8_ECONFIG for tq = 65 --
+        # with every check passed the call would launch on the made-up pointers wherever a device is present)
+        assert forward(**{name: 7}) == -2 and forward(**{name: 8}, tq=65) == -4 and forward(**{name: 7}, tq=65) == -2, name
     for name in ("q_stride", "kv_stride", "dq_stride", "dkv_stride"):
         assert backward(**{name: 7}) == -2 and backward(**{name: -24}) == -2, name
     # RL8_EALIGN: a float pointer off 4 bytes (the byte mask may sit anywhere)
