@@ -93,6 +93,7 @@ extern "C" {
 #define RL8_ECONFIG (-4) /* unsupported combination of options */
 
 #define RL8_MAX_CLASSES 64 /* K upper bound for the categorical kernels */
+#define RL8_MAX_WIDE_CLASSES 65536 /* K upper bound for the wave-per-row (_wide_) categorical kernels */
 #define RL8_MAX_PARTIALS 2048 /* upper bound on per-launch partial rows */
 
 /* ABI / build identification: returns RL8_ABI_VERSION of the library's build; `arch` (host pointer, may be NULL)
@@ -174,6 +175,18 @@ int rl8_categorical_sample_logp_f32(const float *logits, const float *noise, int
                                     float *logp_out, int64_t m, int a, int k, uint64_t seed,
                                     uint64_t step, int64_t row_offset, int deterministic,
                                     void *stream);
+
+/* The same draw for rows of 2 <= k <= RL8_MAX_WIDE_CLASSES classes with a * k < 2^31 (else RL8_ESIZE, before any
+ * launch): one wave per row i, looping over the a action dimensions, lanes striding over the classes.  The arithmetic
+ * is that of the entry above operation for operation -- correctly rounded exp / log, nl_j = x_j - lse,
+ * p_j = exp(nl_j - max nl) / s2, argmax_j p_j / q_j with the first index on ties, logp = sum_d nl[class] -- except
+ * that the two sums and the maximum are taken lane by lane and then across the 64 lanes in a fixed xor butterfly, so
+ * s and s2 may differ in their last place from the sequential sums above.  Philox word d * k + j of
+ * (seed, i + row_offset, step), as above: for k <= RL8_MAX_CLASSES both entries see the same draws. */
+int rl8_categorical_wide_sample_logp_f32(const float *logits, const float *noise, int64_t *action_out,
+                                         float *logp_out, int64_t m, int a, int k, uint64_t seed,
+                                         uint64_t step, int64_t row_offset, int deterministic,
+                                         void *stream);
 
 /* Normal / SquashedNormal: mean, log_std [M][A]; noise: injected eps [M][A]
  * (may be NULL -> Philox); action_out [M][A] f32; logp_out [M]. */
@@ -410,6 +423,22 @@ int rl8_ppo_loss_categorical_fwd_bwd_f32(const float *logits, const float *value
                                          int k, const rl8_ppo_hparams *hp /*host*/,
                                          float *grad_logits, float *grad_value,
                                          double *loss_sums_out, void *scratch, void *stream);
+
+/* The same loss for 2 <= k <= RL8_MAX_WIDE_CLASSES classes with a * k < 2^31 (else RL8_ESIZE, before any launch):
+ * one wave per sample over all a dimensions, lanes striding over the classes, every access of a wave a run of 256
+ * contiguous bytes.  Per element the arithmetic is that of the generic kernel behind the entry above (expf / logf
+ * normalisation, masked classes clamped to the lowest float in the entropy, the action clamped for the gather, the
+ * same policy / value terms and gradient formula); sums and the maximum over a row run lane by lane and then across
+ * lanes in a fixed xor butterfly.  A row of up to 1024 classes stays in registers between the passes, a longer one
+ * is read again from cache.  Loss sums: one lane per wave adds each sample's four terms in double, then the fixed-
+ * order block and grid reduction of the entry above (at most RL8_MAX_PARTIALS rows; RL8_LOSS_GRID_CAP caps the grid).
+ * grad_logits == NULL (with grad_value == NULL): forward only. */
+int rl8_ppo_loss_categorical_wide_fwd_bwd_f32(const float *logits, const float *value,
+                                              const int64_t *action, const float *logp_old,
+                                              const float *adv, const float *ret, int64_t m, int a,
+                                              int k, const rl8_ppo_hparams *hp /*host*/,
+                                              float *grad_logits, float *grad_value,
+                                              double *loss_sums_out, void *scratch, void *stream);
 
 int rl8_ppo_loss_normal_fwd_bwd_f32(const float *mean, const float *log_std, const float *value,
                                     const float *action, const float *logp_old, const float *adv,

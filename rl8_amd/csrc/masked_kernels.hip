@@ -9,6 +9,7 @@
 
 #include "common.hip.h"
 #include "device_math.hip.h"
+#include "wave_rows.hip.h"
 
 namespace rl8 {
 namespace {
@@ -21,20 +22,6 @@ struct MaskedRow {
     return m ? x[j] + (m[j] ? 0.0f : -FLT_MAX) : x[j];
   }
 };
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    const float o = __shfl_xor(v, off, kWave);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {  // (a xor butterfly: the same tree, hence the same bits, in every lane)
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off, kWave);
-  return v;
-}
 
 // ---- pooling over T ----------------------------------------------------------------------------------------------
 // Lanes run over flattened (row, feature) pairs, the T loop inside the lane: a wave's loads of one t cover 64 / E runs
@@ -127,12 +114,6 @@ template <class F>
 __device__ __forceinline__ void for_each_lane_row(int64_t rows, F &&f) {
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < rows; r += stride) f(r);
-}
-template <class F>
-__device__ __forceinline__ void for_each_wave_row(int64_t rows, F &&f) {  // (the row is the same in all 64 lanes)
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave; r < rows; r += stride)
-    f(r, (int)(threadIdx.x & (kWave - 1)));
 }
 
 // F.log_softmax as torch evaluates it: (z - max z) - log(sum exp(z - max z)).

@@ -132,7 +132,9 @@ class Categorical(Distribution):
 
     def sample_with_logp(self, *, deterministic: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
         seed, step, row_offset = self._address()
-        return hip.categorical_sample_logp(
+        # (more classes than one lane's array holds: the wave-per-row kernel; up to MAX_CLASSES nothing changes)
+        wide = self.logits.shape[-1] > hip.MAX_CLASSES
+        return (hip.categorical_sample_logp_wide if wide else hip.categorical_sample_logp)(
             self.logits.contiguous(),
             None if deterministic else self.noise,
             seed=seed,

@@ -34,6 +34,7 @@ _ERRORS = {
 }
 
 MAX_CLASSES = 64
+MAX_WIDE_CLASSES = 65536  # RL8_MAX_WIDE_CLASSES: the wave-per-row categorical kernels
 MAX_GATHER_FIELDS = 8
 LAYOUT_ENV_MAJOR = 0
 LAYOUT_TIME_MAJOR = 1
@@ -149,6 +150,7 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_cartpole_step_f32": [_vp, _vp, C.POINTER(CartPoleCfg), _vp, _i64, _vp, _i64, _vp],
     "rl8_cartpole_reset_f32": [_vp, _i64, _f32, _u64, _u64, _i64, _vp, _i64, _vp],
     "rl8_categorical_sample_logp_f32": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _u64, _u64, _i64, _i32, _vp],
+    "rl8_categorical_wide_sample_logp_f32": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _u64, _u64, _i64, _i32, _vp],
     "rl8_normal_sample_logp_f32": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u64, _u64, _i64, _i32, _vp],
     "rl8_rollout_scatter_f32": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _vp],
     "rl8_rollout_scatter_leaves_f32": [_vp, _i64, _vp, _vp, _vp, C.POINTER(ScatterLeaf), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32,
@@ -176,6 +178,8 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_gae_plan": [_i64, _i64, _i32, _i32, C.POINTER(GaePlanStruct)],
     "rl8_advantage_normalise_route": [_i64, _i64, _i32, _i32],
     "rl8_ppo_loss_categorical_fwd_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(PPOHparams), _vp, _vp, _vp, _vp, _vp],
+    "rl8_ppo_loss_categorical_wide_fwd_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(PPOHparams), _vp, _vp, _vp,
+                                                  _vp, _vp],
     "rl8_ppo_loss_normal_fwd_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(PPOHparams), _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_gather_minibatch": [_vp, _i64, _i64, C.POINTER(GatherField), _i32, _vp],
     "rl8_gather_minibatch_plan": [_i32, _i64, _i64, C.POINTER(GatherField), _i32, C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -630,6 +634,43 @@ def categorical_sample_logp(
     return actions, logp
 
 
+def _check_wide_classes(a: int, k: int) -> None:
+    if k > MAX_WIDE_CLASSES:
+        raise ValueError(f"a categorical of {k} classes is above the limit of {MAX_WIDE_CLASSES} (MAX_WIDE_CLASSES)")
+    if a * k >= 1 << 31:
+        raise ValueError(f"{a} action dimensions of {k} classes: a * k must stay below 2^31")
+
+
+def categorical_sample_logp_wide(
+    logits: torch.Tensor,
+    noise: None | torch.Tensor,
+    *,
+    seed: int = 0,
+    step: int = 0,
+    row_offset: int = 0,
+    deterministic: bool = False,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """:func:`categorical_sample_logp` for 2 <= K <= ``MAX_WIDE_CLASSES``: one wave per row."""
+    logits = _dense(logits.detach(), torch.float32, "logits")
+    m, a, k = logits.shape
+    _check_wide_classes(a, k)
+    if noise is not None:
+        noise = _dense(noise, torch.float32, "noise")
+        if noise.shape != logits.shape:
+            raise ValueError("noise must have the shape of logits")
+    actions = torch.empty(m, a, dtype=torch.int64, device=logits.device)
+    logp = torch.empty(m, 1, dtype=torch.float32, device=logits.device)
+    with _timed("categorical_sample_logp_wide", m):
+        _check(
+            load().rl8_categorical_wide_sample_logp_f32(
+                _ptr(logits), _ptr(noise), _ptr(actions), _ptr(logp), m, a, k, seed, step, row_offset,
+                int(deterministic), _stream(),
+            ),
+            "rl8_categorical_wide_sample_logp_f32",
+        )
+    return actions, logp
+
+
 def normal_sample_logp(
     mean: torch.Tensor,
     log_std: torch.Tensor,
@@ -1033,6 +1074,30 @@ def ppo_loss_categorical(
                 C.byref(hp), _ptr(g_logits), _ptr(g_value), _ptr(sums), _ptr(scratch(logits.device)), _stream(),
             ),
             "rl8_ppo_loss_categorical_fwd_bwd_f32",
+        )
+    return sums, g_logits, g_value
+
+
+def ppo_loss_categorical_wide(
+    logits: torch.Tensor, value: torch.Tensor, action: torch.Tensor, logp_old: torch.Tensor, adv: torch.Tensor,
+    ret: torch.Tensor, hp: PPOHparams, *, with_grad: bool = True,
+) -> tuple[torch.Tensor, None | torch.Tensor, None | torch.Tensor]:
+    """:func:`ppo_loss_categorical` for 2 <= K <= ``MAX_WIDE_CLASSES``: one wave per sample."""
+    m, a, k = logits.shape
+    _check_wide_classes(a, k)
+    _loss_inputs(m, ("logits", logits, torch.float32, m * a * k), ("value", value, torch.float32, m),
+                 ("action", action, torch.int64, m * a), ("logp_old", logp_old, torch.float32, m),
+                 ("adv", adv, torch.float32, m), ("ret", ret, torch.float32, m))
+    sums = torch.empty(5, dtype=torch.float64, device=logits.device)
+    g_logits = torch.empty_like(logits) if with_grad else None
+    g_value = torch.empty_like(value) if with_grad else None
+    with _timed("ppo_loss_categorical_wide", m):
+        _check(
+            load().rl8_ppo_loss_categorical_wide_fwd_bwd_f32(
+                _ptr(logits), _ptr(value), _ptr(action), _ptr(logp_old), _ptr(adv), _ptr(ret), m, a, k,
+                C.byref(hp), _ptr(g_logits), _ptr(g_value), _ptr(sums), _ptr(scratch(logits.device)), _stream(),
+            ),
+            "rl8_ppo_loss_categorical_wide_fwd_bwd_f32",
         )
     return sums, g_logits, g_value
 

@@ -246,7 +246,9 @@ def fused_ppo_loss(
     flat = lambda t: t.detach().contiguous()  # noqa: E731
     if issubclass(distribution_cls, Categorical):
         logits = features["logits"]
-        sums, g_logits, g_values = hip.ppo_loss_categorical(
+        # (more classes than one lane's array holds: the wave-per-sample kernel; up to MAX_CLASSES nothing changes)
+        wide = logits.shape[-1] > hip.MAX_CLASSES
+        sums, g_logits, g_values = (hip.ppo_loss_categorical_wide if wide else hip.ppo_loss_categorical)(
             flat(logits).float(), flat(values).float(), flat(actions), flat(logp_old),
             flat(advantages), flat(returns), hp, with_grad=with_grad,
         )
