@@ -56,6 +56,9 @@
  *     recurrent  rl8_lstm_pack_split, rl8_lstm_split_state[_bound], rl8_lstm_step_split_f32,
  *                rl8_lstm_rows_backward_pack, rl8_lstm_rows_backward[_heads]_f32, rl8_lstm_wgrad_f16_f32,
  *                rl8_linear_heads_{forward,forward_pair,backward}_f32
+ *     recurrent, hidden width 256 behind an observation of 8 to 128 floats (RL8_AMD_WIDE_INPUT_LSTM=0: torch.nn.LSTM):
+ *                rl8_lstm_wide_in_{pack,forward,wgrad}_f32, rl8_lstm_backward_dgates_f32 (RL8_AMD_LSTM_BACKWARD_ROWS=0),
+ *                with the rows backward and the W_hh weight gradients above
  *     recurrent, hidden width 64 / 128 (model_config={"hidden_size": 64}): rl8_lstm_narrow_{forward,backward,reduce}_f32,
  *                rl8_lstm_narrow_backward_heads_f32 (one layer, heads of <= 4 outputs: the one-node training pass),
  *                rl8_lstm_narrow_input_grad_f32 (dL/dx of layer 0, for models with an encoder in front of the LSTM),
@@ -997,6 +1000,12 @@ int rl8_lstm_backward_f32(const float *x, int64_t b, int l, int d_in, const floa
                           const float *whht_packed, float *dgates, float *partials,
                           int *partial_rows_out /*host*/, void *stream);
 
+/* rl8_lstm_backward_f32's data-gradient kernel and nothing else (it reads no x): dgates [B][L][4][256] from dhs and
+ * what a forward saved, for any input width -- the all-fp32 backward through time of the wide-input family below.
+ * 32 * L * 4096 < 2^31; whht_packed 16-byte aligned. */
+int rl8_lstm_backward_dgates_f32(int64_t b, int l, const float *c0, const float *gates, const float *cs,
+                                 const float *dhs, const float *whht_packed, float *dgates, void *stream);
+
 /* The same data gradient with the recurrent product dL/dh_{t-1} = sum_q dG_q x W_hh[q] on the
  * 16-bit matrix pipe (bf16 planes, three per operand, six plane products: fp32-accurate), a
  * wave per 32 sequences for all L steps (lstm_rows_kernels.hip).  What torch.nn.LSTM's backward
@@ -1047,6 +1056,41 @@ int rl8_mlp_wgrad_f16_strided_f32(const float *dz, int64_t dz_pitch, const uint3
 int rl8_lstm_wgrad_f16_f32(const float *dz, int64_t dz_pitch, const uint32_t *dz_bound, const float *h, int64_t h_pitch,
                            const uint32_t *h_bound, int64_t m, float *workspace, float *dw_out, int accumulate,
                            const float *x, int d_in, float *colsums, int *colsum_rows_out, void *stream);
+
+/* ---------------------------------------------------------------------- *
+ * a-9, wide input: the same LSTM (one layer, hidden 256, fp32 on v_mfma_f32_32x32x2_f32, gates i, f, g, o) behind
+ *      observations of 8 <= d_in <= 128 floats (lstm_wide_in_kernels.hip).  The operand row of the recurrent product
+ *      is [h_{t-1} (256) | x_t (d_in) | 1 | 0..], K = 256 + 8 * ceil((d_in + 1) / 8).  The saved gates and cell states
+ *      have rl8_lstm_forward_f32's layouts: rl8_lstm_rows_backward[_heads]_f32 or rl8_lstm_backward_dgates_f32 form
+ *      dgates from them, the W_hh weight-gradient entries (colsums NULL) dW_hh, rl8_lstm_wide_in_wgrad_f32 dW_ih and db.
+ *
+ * rl8_lstm_wide_in_supports: 1 for 8 <= d_in <= 128, else 0 (host only).
+ * rl8_lstm_wide_in_lds_bytes: dynamic LDS of a launch at d_in: kernel 0 the forward (2 workgroups per CU), 1 the
+ *   weight gradient (1 per CU); RL8_ESIZE outside the envelope (host only).
+ * rl8_lstm_wide_in_pack_f32: torch-layout parameters (w_ih [1024][d_in], w_hh [1024][256], b_ih, b_hh [1024]) ->
+ *   `packed` (rl8_lstm_wide_in_pack_floats(d_in) = 1024 * K floats, 16-byte aligned): per gate the 256 x K matrix
+ *   [w_hh | w_ih | b_ih + b_hh | 0..] in MFMA fragment order.  Re-pack when a parameter changes.
+ * rl8_lstm_wide_in_forward_f32: x [B][L][d_in] dense; h0 (16-byte aligned), c0 [B][256] -> hs [B][L][256], hn, cn
+ *   [B][256]; save_gates [B][L][4][256] and save_c [B][L][256] both given (training) or both NULL (L = 1 with both
+ *   NULL is the rollout step).  32 * L * 4096 < 2^31.
+ * rl8_lstm_wide_in_wgrad_f32: dw_ih_out [1024][d_in] = dgates^T x and db_out [1024] = the column sums of dgates over
+ *   the m = B * L rows (dgates [m][1024] 16-byte aligned, x [m][d_in]); db comes from a ones column beside the x tile,
+ *   not from a second pass.  `workspace`: rl8_lstm_wide_in_workspace_bytes(d_in) bytes (one [256][d_in + 1] slab per
+ *   gate and workgroup).  The grid is a function of m and d_in alone and the slabs are summed in slab order: bitwise
+ *   reproducible.
+ * Every entry returns RL8_ENULL / RL8_ESIZE / RL8_EALIGN before any launch.
+ * ---------------------------------------------------------------------- */
+int rl8_lstm_wide_in_supports(int d_in);
+int64_t rl8_lstm_wide_in_lds_bytes(int kernel, int d_in);
+int64_t rl8_lstm_wide_in_pack_floats(int d_in);
+int rl8_lstm_wide_in_pack_f32(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, int d_in,
+                              float *packed, void *stream);
+int rl8_lstm_wide_in_forward_f32(const float *x, int64_t b, int l, int d_in, const float *h0, const float *c0,
+                                 const float *w_packed, float *hs, float *hn, float *cn, float *save_gates,
+                                 float *save_c, void *stream);
+int64_t rl8_lstm_wide_in_workspace_bytes(int d_in);
+int rl8_lstm_wide_in_wgrad_f32(const float *dgates, const float *x, int64_t m, int d_in, float *workspace,
+                               float *dw_ih_out, float *db_out, void *stream);
 
 /* The recurrent models' output heads (src/rl8/models/_recurrent.py:230-236, 287-292),
  * all of them at once: out [M][n] = h [M][256] x w^T + b, w [n][256] (the heads'

@@ -462,6 +462,21 @@ RL8_API int rl8_lstm_backward_f32(const float *x, int64_t b, int l, int d_in, co
   }
 }
 
+// The backward through time alone, for callers whose x is wider than this unit's forward takes (lstm_wide_in_kernels.hip:
+// dW_ih and the biases come from rl8_lstm_wide_in_wgrad_f32 there): lstm_backward_kernel reads no x.
+RL8_API int rl8_lstm_backward_dgates_f32(int64_t b, int l, const float *c0, const float *gates, const float *cs,
+                                         const float *dhs, const float *whht_packed, float *dgates, void *stream) {
+  if (!c0 || !gates || !cs || !dhs || !whht_packed || !dgates) return RL8_ENULL;
+  if (b <= 0 || l <= 0) return RL8_ESIZE;
+  if ((int64_t)kLstmRows * l * 4 * kHidden * 4 >= (int64_t)1 << 31) return RL8_ESIZE;
+  if (!aligned16(whht_packed)) return RL8_EALIGN;
+  const int64_t tiles = (b + kLstmRows - 1) / kLstmRows;
+  const int grid = (int)(tiles < 2 * kCUs ? tiles : 2 * kCUs);
+  lstm_backward_kernel<<<grid, kBlock, 2 * sizeof(float) * kLstmRows * kLdsStride, (hipStream_t)stream>>>(
+      b, l, c0, gates, cs, dhs, whht_packed, dgates);
+  return launch_status();
+}
+
 // ---------------------------------------------------------------------------
 // The recurrent models' output heads: a few Linear(256, n) layers on the LSTM's
 // outputs (src/rl8/models/_recurrent.py:230-236, 287-292), evaluated together:

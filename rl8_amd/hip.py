@@ -227,6 +227,14 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_lstm_backward_partial_floats": [_i32],
     "rl8_lstm_backward_max_rows": [],
     "rl8_lstm_backward_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int), _vp],
+    "rl8_lstm_backward_dgates_f32": [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rl8_lstm_wide_in_supports": [_i32],
+    "rl8_lstm_wide_in_lds_bytes": [_i32, _i32],
+    "rl8_lstm_wide_in_pack_floats": [_i32],
+    "rl8_lstm_wide_in_pack_f32": [_vp, _vp, _vp, _vp, _i32, _vp, _vp],
+    "rl8_lstm_wide_in_forward_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rl8_lstm_wide_in_workspace_bytes": [_i32],
+    "rl8_lstm_wide_in_wgrad_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "rl8_linear_heads_max_rows": [],
     "rl8_linear_heads_forward_f32": [_vp, _i64, _vp, _vp, _i32, _vp, _vp],
     "rl8_linear_heads_forward_pair_f32": [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp],
@@ -327,7 +335,8 @@ def load() -> C.CDLL:
                             "rl8_lstm_stack_workspace_bytes", "rl8_linear_heads_narrow_workspace_bytes",
                             "rl8_feedforward_workspace_floats", "rl8_tower_moments_workspace_bytes",
                             "rl8_mlp_wide_in_pack_floats", "rl8_mlp_wide_in_partial_floats", "rl8_mlp_wide_in_lds_bytes",
-                            "rl8_mlp_wide_in_workspace_bytes")
+                            "rl8_mlp_wide_in_workspace_bytes", "rl8_lstm_wide_in_pack_floats",
+                            "rl8_lstm_wide_in_lds_bytes", "rl8_lstm_wide_in_workspace_bytes")
                 else C.c_int
             )
         built = int(lib.rl8_abi_version(None, 0))
@@ -2344,6 +2353,73 @@ def lstm_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_packed: 
 
 
 # --------------------------------------------------------------------------- #
+# The same LSTM behind 8 to 128 input floats (lstm_wide_in_kernels.hip).
+# --------------------------------------------------------------------------- #
+def lstm_wide_in_supports(d_in: int) -> bool:
+    return bool(load().rl8_lstm_wide_in_supports(int(d_in)))
+
+
+def lstm_wide_in_pack(w_ih: torch.Tensor, w_hh: torch.Tensor, b_ih: torch.Tensor, b_hh: torch.Tensor) -> torch.Tensor:
+    """torch.nn.LSTM parameters (``weight_ih_l0`` [1024, d], 8 <= d <= 128, ``weight_hh_l0`` [1024, 256], the two
+    biases [1024]) -> per gate ``[w_hh | w_ih | b_ih + b_hh | 0..]`` in MFMA fragment order, K = 256 + 8 ceil((d + 1) / 8)."""
+    d_in = _lstm_pack_params(w_ih, w_hh, b_ih, b_hh)
+    lib = load()
+    floats = int(lib.rl8_lstm_wide_in_pack_floats(d_in))
+    if floats < 0:
+        raise ValueError(f"no wide-input LSTM kernel for d_in={d_in}")
+    packed = torch.empty(floats, dtype=torch.float32, device=w_hh.device)
+    _check(lib.rl8_lstm_wide_in_pack_f32(_ptr(w_ih.detach()), _ptr(w_hh.detach()), _ptr(b_ih.detach()), _ptr(b_hh.detach()),
+                                         d_in, _ptr(packed), _stream()), "rl8_lstm_wide_in_pack_f32")
+    return packed
+
+
+def lstm_wide_in_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_packed: torch.Tensor, *,
+                         save: bool = False):
+    """x [B, L, d], 8 <= d <= 128, h0 / c0 [B, 256] -> (hs [B, L, 256], hn, cn [B, 256], gates, cs) as
+    :func:`lstm_forward` returns them; ``w_packed`` from :func:`lstm_wide_in_pack` for this ``d``."""
+    x = _dense(x.detach(), torch.float32, "x")
+    if x.ndim != 3:
+        raise ValueError("x must be [B, L, d_in]")
+    b, l, d_in = x.shape
+    lib = load()
+    if b < 1 or l < 1 or not lstm_wide_in_supports(d_in):
+        raise ValueError(f"no wide-input LSTM kernel for b={b}, l={l}, d_in={d_in}")
+    _lstm_states_256(h0, c0, b)
+    if w_packed.numel() != int(lib.rl8_lstm_wide_in_pack_floats(d_in)) or w_packed.dtype != torch.float32:
+        raise ValueError("w_packed must come from lstm_wide_in_pack for this d_in")
+    hs, hn, cn, gates, cs = _lstm_outputs(b, l, LSTM_HIDDEN, x.device, save)
+    with _timed("lstm_wide_in_forward_save" if save else "lstm_wide_in_forward", b * l):
+        _check(lib.rl8_lstm_wide_in_forward_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_packed), _ptr(hs),
+                                                _ptr(hn), _ptr(cn), _ptr(gates), _ptr(cs), _stream()),
+               "rl8_lstm_wide_in_forward_f32")
+    return hs, hn, cn, gates, cs
+
+
+_lstm_wide_in_ws: dict[tuple[int, int], torch.Tensor] = {}
+
+
+def lstm_wide_in_wgrad(dgates: torch.Tensor, x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """(dW_ih [1024, d] = dgates^T @ x, db [1024] = the column sums of dgates) over the M rows of ``dgates`` [M, 1024]
+    and ``x`` [M, d], 8 <= d <= 128: one launch and its slab reduction, fp32 MFMA, deterministic."""
+    x = _dense(x.detach(), torch.float32, "x")
+    if x.ndim != 2:
+        raise ValueError("x must be [M, d_in]")
+    m, d_in = x.shape
+    _shaped(dgates, (m, 4 * LSTM_HIDDEN), "dgates")
+    if m < 1 or not lstm_wide_in_supports(d_in):
+        raise ValueError(f"no wide-input LSTM kernel for m={m}, d_in={d_in}")
+    lib = load()
+    nbytes = int(lib.rl8_lstm_wide_in_workspace_bytes(128))
+    ws = _per_stream(_lstm_wide_in_ws, x.device, lambda: torch.empty(nbytes // 4, dtype=torch.float32, device=x.device))
+    dw_ih = torch.empty(4 * LSTM_HIDDEN, d_in, dtype=torch.float32, device=x.device)
+    db = torch.empty(4 * LSTM_HIDDEN, dtype=torch.float32, device=x.device)
+    with _timed("lstm_wide_in_wgrad", m):
+        _check(lib.rl8_lstm_wide_in_wgrad_f32(_ptr(dgates), _ptr(x), m, d_in, _ptr(ws), _ptr(dw_ih), _ptr(db), _stream()),
+               "rl8_lstm_wide_in_wgrad_f32")
+    return dw_ih, db
+
+
+# --------------------------------------------------------------------------- #
 # Narrow LSTMs: one layer (or layer 0 of a stack), hidden width 64 or 128, d_in <= 16 (lstm_narrow_kernels.hip).
 # --------------------------------------------------------------------------- #
 LSTM_NARROW_HIDDEN = (64, 128)
@@ -2664,7 +2740,7 @@ def lstm_backward(
     x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, hs: torch.Tensor, gates: torch.Tensor, cs: torch.Tensor,
     dhs: None | torch.Tensor, whht_packed: None | torch.Tensor, *, wgrad: None | str = None, split: bool = True,
     rows_packed: None | torch.Tensor = None, h0_bound: None | torch.Tensor = None,
-    heads: None | tuple[torch.Tensor, torch.Tensor] = None, hs_bound: None | float = None,
+    heads: None | tuple[torch.Tensor, torch.Tensor] = None, hs_bound: None | float = None, wide_in: bool = False,
 ) -> dict[str, torch.Tensor]:
     """Parameter gradients of the LSTM given ``dhs`` [B, L, 256] (gradient of every
     ``h_t``) and what ``lstm_forward(..., save=True)`` returned. Returns ``w_ih``,
@@ -2681,9 +2757,14 @@ def lstm_backward(
     ``heads`` (with ``rows_packed``, ``dhs`` None): see :func:`lstm_rows_backward`.
     ``hs_bound``: a number >= max |hs| the caller vouches for -- 1.0 when ``hs`` is this LSTM's own output
     (|o * tanh(c)| < 1), which is what ``nn.fused_lstm`` passes; None: taken from ``hs`` here (one reduction over it).
-    The fp16 planes of the weight gradient are scaled by it: a value above the bound would overflow them."""
+    The fp16 planes of the weight gradient are scaled by it: a value above the bound would overflow them.
+    ``wide_in``: ``x`` is 8 to 128 floats wide (what :func:`lstm_wide_in_forward` saved): without ``rows_packed`` the
+    backward through time is ``rl8_lstm_backward_dgates_f32``, every ``W_hh`` launch runs without column sums (no
+    per-step copies of ``x``), and ``w_ih`` / ``b`` come from one :func:`lstm_wide_in_wgrad` launch over all rows."""
     x = _dense(x.detach(), torch.float32, "x")
     b, l, d_in = x.shape
+    if wide_in and not lstm_wide_in_supports(d_in):
+        raise ValueError(f"lstm_backward: wide_in with d_in={d_in}")
     if heads is not None and (rows_packed is None or dhs is not None):
         raise ValueError("lstm_backward: heads needs rows_packed and no dhs")
     for name, t, shape in (("h0", h0, (b, LSTM_HIDDEN)), ("c0", c0, (b, LSTM_HIDDEN)), ("hs", hs, (b, l, LSTM_HIDDEN)),
@@ -2706,6 +2787,11 @@ def lstm_backward(
     rows, partials = C.c_int(0), None
     if rows_packed is not None:
         dgates, dg_bound = lstm_rows_backward(c0, gates, cs, dhs, rows_packed, with_bound=True, heads=heads)
+    elif wide_in:  # the data-gradient kernel alone: it reads no x
+        dgates = torch.empty(b, l, 4, H, dtype=torch.float32, device=dev)
+        with _timed("lstm_backward", b * l):
+            _check(lib.rl8_lstm_backward_dgates_f32(b, l, _ptr(c0), _ptr(gates), _ptr(cs), _ptr(dhs), _ptr(whht_packed),
+                                                    _ptr(dgates), _stream()), "rl8_lstm_backward_dgates_f32")
     else:
         dgates = torch.empty(b, l, 4, H, dtype=torch.float32, device=dev)
         if not planes:  # dW_ih and the bias come out of this kernel's partials
@@ -2717,7 +2803,9 @@ def lstm_backward(
                    "rl8_lstm_backward_f32")
     ws, dw_hh = _wgrad_workspace(dev), torch.empty(4 * H, H, dtype=torch.float32, device=dev)
     dgp, hsp, h0p, wsp, dwp, stream = _ptr(dgates), _ptr(hs), _ptr(h0), _ptr(ws), _ptr(dw_hh), _stream()
-    if planes:
+    if wide_in:  # no per-step copies of x, no column sums: dW_ih and the bias come from one launch over dG below
+        small = None
+    elif planes:
         xt = [x[:, t].contiguous() for t in range(l)]            # dense [B][d] per step (the kernel's scalar loads)
         width = H * (d_in + 1)                                    # a column-sum row: dW_ih^T, then the bias
         # kept between calls: [gate][step][workgroup][...]; four gates per launch: [step][gate][workgroup of gate][...]
@@ -2748,9 +2836,13 @@ def lstm_backward(
             for t in range(l):
                 h_prev, h_pitch = (h0p, H) if t == 0 else (hsp + (t - 1) * H * 4, l * H)
                 h_scale = (_ptr(h0_bound if t == 0 else one),) if f16 else ()
-                col_sums = (_ptr(xt[t]), d_in, _ptr(cols[t] if four_gates else cols[q, t]), C.byref(crow)) if planes else ()
+                col_sums = (() if not planes else (None, 0, None, None) if wide_in else
+                            (_ptr(xt[t]), d_in, _ptr(cols[t] if four_gates else cols[q, t]), C.byref(crow)))
                 _check(getattr(lib, name)(dgp + (t * 4 * H + q * H) * 4, l * 4 * H, *dg_scale, h_prev, h_pitch, *h_scale, b,
                                           wsp, dwp + 4 * H * H * q, int(t > 0), *col_sums, stream), name)
+    if wide_in:
+        dw_ih, db = lstm_wide_in_wgrad(dgates.view(b * l, 4 * H), x.view(b * l, d_in))
+        return {"w_ih": dw_ih, "w_hh": dw_hh, "b": db}
     if not planes:
         return {"w_ih": small[: 4 * H * d_in].view(4 * H, d_in), "w_hh": dw_hh, "b": small[4 * H * d_in :]}
     if four_gates:  # (a step's rows sit gate-major, crow.value per gate -- 64 at the sizes that fill the chip)

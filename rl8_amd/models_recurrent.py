@@ -4,9 +4,11 @@ Interfaces follow the reference's ``src/rl8/models/_recurrent.py``:
 ``RecurrentModel`` :19-138 (``forward(batch, states) -> (features, states)``,
 ``state_spec``, ``init_states``), ``DefaultContinuousRecurrentModel`` :169-256,
 ``DefaultDiscreteRecurrentModel`` :259-341. Module names match, so reference
-``state_dict``s load unchanged. A one-layer LSTM of hidden width 256 (d_in <= 7) or
-64 / 128 (d_in <= 16) runs the fused HIP kernels (``nn/fused_lstm.py``), and so do
-the ``Linear`` heads on latents of those widths; any other runs the modules.
+``state_dict``s load unchanged. A one-layer LSTM of hidden width 256 (d_in <= 128: up
+to 7 floats on the plane kernels, 8 to 128 on the fp32 kernels of
+``lstm_wide_in_kernels.hip`` unless ``RL8_AMD_WIDE_INPUT_LSTM=0``) or 64 / 128
+(d_in <= 16) runs the fused HIP kernels (``nn/fused_lstm.py``), and so do the
+``Linear`` heads on latents of those widths; any other runs the modules.
 
 """
 

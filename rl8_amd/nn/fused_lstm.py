@@ -11,6 +11,11 @@ family    envelope                             kernels                          
 "256"     one layer, H = 256, d_in <= 7        lstm_kernels.hip, lstm_split_ /    ``lstm_forward``; with
           (``hip.lstm_supports``); the route   lstm_rows_kernels.hip (packs       heads: ``lstm_heads_forward``
           inside it comes from ``_plan``       cached on the module)              (``_FusedLSTMHeads``)
+"256-     one layer, H = 256, 8 <= d_in <=     lstm_wide_in_kernels.hip (fp32     the same two entries and
+wide-in"  128 (``hip.lstm_wide_in_supports``)  forward, dW_ih / db), the rows     nodes, after ``_family``
+          and ``RL8_AMD_WIDE_INPUT_LSTM`` not  backward and W_hh gradients of     has said ``None``
+          0: ``_wide_input_family``; routes    "256" (``_wide_input_plan``)
+          from ``_wide_input_plan``
 "narrow"  one layer, H = 64 / 128, d_in <= 16  lstm_narrow_kernels.hip (weights   ``lstm_forward``; with
           (``hip.lstm_narrow_supports``)       in torch layout: no plan, no       heads: ``lstm_heads_forward``
                                                packs, no planes)                  (``_NarrowLSTMHeads``)
@@ -29,8 +34,8 @@ forms the heads' data gradient itself (``lstm_heads_forward``); the reference's 
 The "narrow" and "stack" families return the gradient of their input ``x`` where it requires one -- a model with
 learned parameters in front of the LSTM, such as ``rl8_amd.envs.LSTMTrader``'s embedding -- from one more launch on
 the gate gradients the backward through time has left (``rl8_lstm_narrow_input_grad_f32``); an ``x`` that is
-rollout-buffer data costs nothing. The "256" family forms no input gradient and declines an ``x`` that requires one
-under grad mode; no family forms a gradient for the initial states ``h0`` / ``c0``, and every entry point declines
+rollout-buffer data costs nothing. The "256" and "256-wide-in" families form no input gradient and decline an ``x``
+that requires one under grad mode; no family forms a gradient for the initial states ``h0`` / ``c0``, and every entry point declines
 a call in which one of them requires it (``_declines``). The caller then runs the module, which forms them.
 
 """
@@ -97,16 +102,48 @@ def _family_for(lstm: nn.LSTM, x: torch.Tensor) -> None | str:
     return _family(lstm) if _input_ok(lstm, x) else None
 
 
+def wide_input_lstm_on() -> bool:
+    """``RL8_AMD_WIDE_INPUT_LSTM=0`` (read on every call) keeps width-256 LSTMs behind 8 to 128 input floats on the
+    torch module: the tests' and ``tools/lstm_wide_input_ab.py``'s yardstick.  On by default."""
+    return os.environ.get("RL8_AMD_WIDE_INPUT_LSTM", "1") != "0"
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_input_supported(d_in: int) -> bool:
+    """The wide-input kernels take this input width: fixed by the build, asked once per width."""
+    return hip.lstm_wide_in_supports(d_in)
+
+
+def _wide_input_family(lstm: nn.LSTM) -> None | str:
+    """"256-wide-in" for the modules ``_family`` leaves to torch only because ``hip.lstm_supports`` ends at 7 inputs:
+    one layer of width 256, batch_first, biased, no projection, one direction, behind 8 to 128 input floats
+    (``hip.lstm_wide_in_supports``), with ``ENABLED`` and the switch ``RL8_AMD_WIDE_INPUT_LSTM`` as they are now; else
+    ``None``.  Beside ``_family``, not inside it, as ``fused_mlp._wide_input_family`` is: ``_family``'s answers are
+    what the lean rollout and the narrow routes are built on."""
+    if not (ENABLED and lstm.batch_first and lstm.bias and not lstm.bidirectional and lstm.proj_size == 0):
+        return None
+    if lstm.hidden_size != hip.LSTM_HIDDEN or lstm.num_layers != 1 or not _wide_input_supported(lstm.input_size):
+        return None
+    return "256-wide-in" if wide_input_lstm_on() else None
+
+
+def _wide_input_family_for(lstm: nn.LSTM, x: torch.Tensor) -> None | str:
+    """``_wide_input_family(lstm)`` where ``x`` is an input its kernels take, else ``None``."""
+    return _wide_input_family(lstm) if _input_ok(lstm, x) else None
+
+
 def _declines(family: None | str, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor) -> bool:
     """A gradient is asked for that ``family``'s node does not form -- of ``h0`` or ``c0`` (any family), of ``x`` at
-    "256" -- and grad mode is on: the entry returns ``None`` instead of handing autograd a ``None`` for it.  Three
-    attribute reads for rollout-buffer data; under ``torch.no_grad()`` nothing can follow and nothing is declined."""
-    return (h0.requires_grad or c0.requires_grad or (family == "256" and x.requires_grad)) and torch.is_grad_enabled()
+    "256" and "256-wide-in" -- and grad mode is on: the entry returns ``None`` instead of handing autograd a ``None``
+    for it.  Three attribute reads for rollout-buffer data; under ``torch.no_grad()`` nothing can follow and nothing is
+    declined."""
+    return ((h0.requires_grad or c0.requires_grad or (family in ("256", "256-wide-in") and x.requires_grad))
+            and torch.is_grad_enabled())
 
 
 def _packs(lstm: nn.LSTM, kind: str):
-    """Fragment-ordered copies of the weights for one kernel ("step" / "split": the fp32 / plane forward step,
-    "transposed" / "rows": the fp32 / rows backward), cached ON the module and re-made when the optimizer has changed
+    """Fragment-ordered copies of the weights for one kernel ("step" / "split": the fp32 / plane forward step, "wide":
+    the fp32 forward behind 8 to 128 inputs, "transposed" / "rows": the fp32 / rows backward), cached ON the module and re-made when the optimizer has changed
     a parameter (version counters) or a parameter tensor has been replaced / moved."""
     params = (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0)
     stamp = tuple((p._version, p.data_ptr()) for p in params)
@@ -114,9 +151,9 @@ def _packs(lstm: nn.LSTM, kind: str):
     hit = cache.get(kind)
     if hit is not None and hit[0] == stamp:
         return hit[1]
-    pack = {"step": hip.lstm_pack, "split": hip.lstm_pack_split, "transposed": hip.lstm_pack_transposed,
-            "rows": hip.lstm_rows_backward_pack}[kind]
-    packed = pack(*params) if kind in ("step", "split") else pack(params[1])
+    pack = {"step": hip.lstm_pack, "split": hip.lstm_pack_split, "wide": hip.lstm_wide_in_pack,
+            "transposed": hip.lstm_pack_transposed, "rows": hip.lstm_rows_backward_pack}[kind]
+    packed = pack(*params) if kind in ("step", "split", "wide") else pack(params[1])
     cache[kind] = (stamp, packed)
     return packed
 
@@ -136,6 +173,7 @@ class _LstmPlan:
     backward_rows: bool  # the backward through time on planes (rows kernel), which leaves a bound on |dG|; else fp32 MFMA
     wgrad: str  # the weight gradient's route (hip.lstm_backward): "f16-gates", "f16", "bf16" or "f32"
     fuse_heads: bool  # a training pass through LSTM + heads as one node (lstm_heads_forward)
+    wide_in: bool = False  # the "256-wide-in" family: the forward of lstm_wide_in_kernels.hip, dW_ih / db from its launch
 
 
 def _plan(d_in: int, b: int) -> _LstmPlan:
@@ -148,6 +186,24 @@ def _plan(d_in: int, b: int) -> _LstmPlan:
              "bf16" if not backward_rows or os.environ.get("RL8_AMD_LSTM_WGRAD_PLANES", "f16") == "bf16" else
              "f16-gates" if four_gates else "f16")
     return _LstmPlan(forward_planes, backward_rows, wgrad, FUSE_HEADS and backward_rows)
+
+
+def _wide_input_plan(b: int) -> _LstmPlan:
+    """``_plan`` for the "256-wide-in" family and ``b`` sequences: the forward is the fp32 kernel of
+    lstm_wide_in_kernels.hip whatever ``RL8_AMD_LSTM_GEMM`` says (there is no plane forward at these widths); the
+    backward through time and the ``W_hh`` gradient follow the rules ``_plan`` applies behind the plane forward, since
+    neither reads ``x``."""
+    backward_rows = BACKWARD_ROWS
+    four_gates = b >= hip.LSTM_WGRAD_GATES_MIN_ROWS and os.environ.get("RL8_AMD_LSTM_WGRAD_GATES", "fused") != "separate"
+    wgrad = ("f32" if not backward_rows else
+             "bf16" if os.environ.get("RL8_AMD_LSTM_WGRAD_PLANES", "f16") == "bf16" else
+             "f16-gates" if four_gates else "f16")
+    return _LstmPlan(False, backward_rows, wgrad, FUSE_HEADS and backward_rows, wide_in=True)
+
+
+def _wide_args(plan: _LstmPlan) -> dict[str, bool]:
+    """``hip.lstm_backward``'s ``wide_in=`` for a plan of the "256-wide-in" family; nothing for every other plan."""
+    return {"wide_in": True} if plan.wide_in else {}
 
 
 #: The fp16 planes of the last training pass's initial hidden states and max |h0|: the SGD iterations of one step() read
@@ -184,7 +240,10 @@ class _FusedLSTM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, lstm, grad_mode, plan):  # type: ignore[override]
         need_grad = grad_mode and any(ctx.needs_input_grad[3:7])
-        if plan.forward_planes:
+        if plan.wide_in:
+            bound = None  # (hip.lstm_backward takes max |h0| itself where its planes need it)
+            hs, _, cn, gates, cs = hip.lstm_wide_in_forward(x, h0, c0, _packs(lstm, "wide"), save=need_grad)
+        elif plan.forward_planes:
             packed, wb = _packs(lstm, "split")
             # max |h0| for the backward's fp16-plane weight gradient comes out of the state split
             planes0, bound = _h0_planes(h0) if need_grad else (None, None)
@@ -208,7 +267,8 @@ class _FusedLSTM(torch.autograd.Function):
         packed = _packs(ctx.lstm, "rows" if ctx.plan.backward_rows else "transposed")
         whht, rows = (None, packed) if ctx.plan.backward_rows else (packed, None)
         g = hip.lstm_backward(x, h0, c0, hs, gates, cs, dhs, whht, wgrad=ctx.plan.wgrad, rows_packed=rows,
-                              h0_bound=ctx.h0_bound, hs_bound=1.0)  # (hs: this LSTM's own outputs, |o tanh c| < 1)
+                              h0_bound=ctx.h0_bound, hs_bound=1.0,  # (hs: this LSTM's own outputs, |o tanh c| < 1)
+                              **_wide_args(ctx.plan))
         return None, None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None, None, None
 
 
@@ -355,8 +415,8 @@ def lstm_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Ten
     (``None``). At H = 64 / 128 ``x`` receives its gradient where it requires one (an
     encoder in front of the LSTM: one more launch, dz x W_ih); at H = 256 the entry
     declines such an ``x`` under grad mode."""
-    family = _family_for(lstm, x)
-    if family not in ("256", "narrow"):  # (a stack has its own entry and state layout: lstm_stack_forward)
+    family = _family_for(lstm, x) or _wide_input_family_for(lstm, x)
+    if family not in ("256", "256-wide-in", "narrow"):  # (a stack has its own entry and state layout: lstm_stack_forward)
         return None
     if _declines(family, x, h0, c0):
         return None
@@ -365,7 +425,8 @@ def lstm_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Ten
     if family == "narrow":
         hs, cn = _NarrowLSTM.apply(*args, torch.is_grad_enabled())
     else:
-        hs, cn = _FusedLSTM.apply(*args, lstm, torch.is_grad_enabled(), _plan(lstm.input_size, x.shape[0]))
+        plan = _wide_input_plan(x.shape[0]) if family == "256-wide-in" else _plan(lstm.input_size, x.shape[0])
+        hs, cn = _FusedLSTM.apply(*args, lstm, torch.is_grad_enabled(), plan)
     return hs, hs[:, -1], cn  # h_n is h_{L-1}: a view, so a gradient into it reaches dhs by itself
 
 
@@ -397,9 +458,13 @@ class _FusedLSTMHeads(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, w_heads, b_heads, lstm, plan):  # type: ignore[override]
-        packed, wb = _packs(lstm, "split")
-        planes0, bound = _h0_planes(h0)
-        hs, _, cn, gates, cs = hip.lstm_forward_split(x, h0, c0, packed, wb, save=True, h0_planes=planes0)
+        if plan.wide_in:
+            bound = None
+            hs, _, cn, gates, cs = hip.lstm_wide_in_forward(x, h0, c0, _packs(lstm, "wide"), save=True)
+        else:
+            packed, wb = _packs(lstm, "split")
+            planes0, bound = _h0_planes(h0)
+            hs, _, cn, gates, cs = hip.lstm_forward_split(x, h0, c0, packed, wb, save=True, h0_planes=planes0)
         out = hip.linear_heads_forward(hs.view(-1, hip.LSTM_HIDDEN), w_heads, b_heads)
         ctx.set_materialize_grads(False)
         ctx.lstm, ctx.plan, ctx.h0_bound = lstm, plan, bound
@@ -410,7 +475,8 @@ class _FusedLSTMHeads(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, dhs, dcn):  # type: ignore[override]
         x, h0, c0, hs, gates, cs, w_heads = ctx.saved_tensors
-        common = dict(wgrad=ctx.plan.wgrad, rows_packed=_packs(ctx.lstm, "rows"), h0_bound=ctx.h0_bound, hs_bound=1.0)
+        common = dict(wgrad=ctx.plan.wgrad, rows_packed=_packs(ctx.lstm, "rows"), h0_bound=ctx.h0_bound, hs_bound=1.0,
+                      **_wide_args(ctx.plan))
         g, dw, db = _lstm_heads_backward(
             hs, w_heads, dout, dhs, hip.linear_heads_backward,
             lambda dhs, heads: hip.lstm_backward(x, h0, c0, hs, gates, cs, dhs, None, heads=heads, **common))
@@ -438,10 +504,11 @@ def lstm_heads_forward(lstm: nn.LSTM, heads: list[nn.Linear], x: torch.Tensor, h
     fuse them): the caller then runs :func:`lstm_forward` / :func:`lstm_stack_forward` and :func:`heads_forward`.
     The gradient of ``x`` is as in :func:`lstm_forward`: formed at H = 64 / 128 where ``x`` requires it; at 256 the
     entry declines such an ``x``, and at every width an ``h0`` or ``c0`` that requires a gradient."""
-    family = _family_for(lstm, x) if torch.is_grad_enabled() else None
-    if family not in ("256", "narrow") or _declines(family, x, h0, c0):
+    family = (_family_for(lstm, x) or _wide_input_family_for(lstm, x)) if torch.is_grad_enabled() else None
+    if family not in ("256", "256-wide-in", "narrow") or _declines(family, x, h0, c0):
         return None
-    plan = _plan(lstm.input_size, x.shape[0]) if family == "256" else None  # (the narrow family reads no plan)
+    plan = (_plan(lstm.input_size, x.shape[0]) if family == "256" else
+            _wide_input_plan(x.shape[0]) if family == "256-wide-in" else None)  # (the narrow family reads no plan)
     if not ((FUSE_HEADS if plan is None else plan.fuse_heads)
             and _heads_eligible(heads, hip.ROWS_BACKWARD_HEADS, lstm.hidden_size)
             and any(p.requires_grad for p in lstm.parameters())):
