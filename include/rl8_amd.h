@@ -1092,6 +1092,45 @@ int64_t rl8_lstm_wide_in_workspace_bytes(int d_in);
 int rl8_lstm_wide_in_wgrad_f32(const float *dgates, const float *x, int64_t m, int d_in, float *workspace,
                                float *dw_ih_out, float *db_out, void *stream);
 
+/* ---------------------------------------------------------------------- *
+ * a-9, stacks of width 256: a layer ABOVE the first of an LSTM with num_layers >= 2 (lstm_stack256_kernels.hip; fp32 on
+ *      v_mfma_f32_32x32x2_f32, gates i, f, g, o).  Its input row is the 256 floats of the layer below's hs[b][t]; the
+ *      operand row of the recurrent product is [h_{t-1} (256) | x_t (256) | 1 | 0 x 7], K = 520.  Layer 0 runs on the
+ *      entries of its own input width (rl8_lstm_forward_f32 / rl8_lstm_step_split_f32 / rl8_lstm_wide_in_forward_f32).
+ *      The saved gates and cell states have rl8_lstm_forward_f32's layouts: rl8_lstm_rows_backward_f32 or
+ *      rl8_lstm_backward_dgates_f32 form dgates from them; the W_hh weight-gradient entries (colsums NULL) form dW_hh
+ *      per step and, in one more accumulation over all m = B * L rows with h = the layer below's hs (pitch 256), dW_ih;
+ *      rl8_lstm_stack256_dx_f32 forms the layer below's dL/dhs and this layer's bias gradient.
+ *
+ * rl8_lstm_stack256_supports: 1 where the build has these kernels (host only).
+ * rl8_lstm_stack256_lds_bytes: dynamic LDS of a launch: kernel 0 the forward (66 688 B, 2 workgroups per CU), 1 the
+ *   input / bias gradient (65 792 B, 2 per CU); RL8_ESIZE for any other kernel (host only).
+ * rl8_lstm_stack256_pack_f32: torch-layout parameters of the layer (w_ih, w_hh [1024][256], b_ih, b_hh [1024]) ->
+ *   `packed` (rl8_lstm_stack256_pack_floats() = 1024 * 520 floats, 16-byte aligned): per gate the 256 x 520 matrix
+ *   [w_hh | w_ih | b_ih + b_hh | 0 x 7] in MFMA fragment order.  Re-pack when a parameter changes.
+ * rl8_lstm_stack256_forward_f32: x [B][L][256] dense (the layer below's hs) and h0, both 16-byte aligned, c0 [B][256] ->
+ *   hs [B][L][256], hn, cn [B][256]; save_gates [B][L][4][256] and save_c [B][L][256] both given (training) or both
+ *   NULL; either way the same bits in hs, hn, cn.  32 * L * 4096 < 2^31.
+ * rl8_lstm_stack256_dx_f32: dx_out [m][256] = dgates [m][1024] x w_ih and db_out [1024] = the column sums of dgates,
+ *   from one read of dgates (16-byte aligned).  `wiht_packed`: w_ih [1024][256] packed per gate by
+ *   rl8_mlp_pack_w2_f32(transposed = 1), as rl8_lstm_backward_f32 takes w_hh (4 x 65 536 floats, 16-byte aligned).
+ *   `workspace`: rl8_lstm_stack256_workspace_bytes(m) bytes (one [1024] slab of column sums per workgroup; RL8_ESIZE
+ *   for m < 1).  The grid is a function of m alone, each workgroup sums its rows in row order in fp32, and the slabs
+ *   are summed in slab order in fp64: bitwise reproducible.
+ * Every entry returns RL8_ENULL / RL8_ESIZE / RL8_EALIGN before any launch.
+ * ---------------------------------------------------------------------- */
+int rl8_lstm_stack256_supports(void);
+int64_t rl8_lstm_stack256_lds_bytes(int kernel);
+int64_t rl8_lstm_stack256_pack_floats(void);
+int rl8_lstm_stack256_pack_f32(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, float *packed,
+                               void *stream);
+int rl8_lstm_stack256_forward_f32(const float *x, int64_t b, int l, const float *h0, const float *c0,
+                                  const float *w_packed, float *hs, float *hn, float *cn, float *save_gates,
+                                  float *save_c, void *stream);
+int64_t rl8_lstm_stack256_workspace_bytes(int64_t m);
+int rl8_lstm_stack256_dx_f32(const float *dgates, int64_t m, const float *wiht_packed, float *workspace, float *dx_out,
+                             float *db_out, void *stream);
+
 /* The recurrent models' output heads (src/rl8/models/_recurrent.py:230-236, 287-292),
  * all of them at once: out [M][n] = h [M][256] x w^T + b, w [n][256] (the heads'
  * nn.Linear weights stacked), n <= 8.  Backward: dh_out [M][256] = dout x w and

@@ -235,6 +235,13 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_lstm_wide_in_forward_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_lstm_wide_in_workspace_bytes": [_i32],
     "rl8_lstm_wide_in_wgrad_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
+    "rl8_lstm_stack256_supports": [],
+    "rl8_lstm_stack256_lds_bytes": [_i32],
+    "rl8_lstm_stack256_pack_floats": [],
+    "rl8_lstm_stack256_pack_f32": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "rl8_lstm_stack256_forward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rl8_lstm_stack256_workspace_bytes": [_i64],
+    "rl8_lstm_stack256_dx_f32": [_vp, _i64, _vp, _vp, _vp, _vp, _vp],
     "rl8_linear_heads_max_rows": [],
     "rl8_linear_heads_forward_f32": [_vp, _i64, _vp, _vp, _i32, _vp, _vp],
     "rl8_linear_heads_forward_pair_f32": [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp],
@@ -336,7 +343,9 @@ def load() -> C.CDLL:
                             "rl8_feedforward_workspace_floats", "rl8_tower_moments_workspace_bytes",
                             "rl8_mlp_wide_in_pack_floats", "rl8_mlp_wide_in_partial_floats", "rl8_mlp_wide_in_lds_bytes",
                             "rl8_mlp_wide_in_workspace_bytes", "rl8_lstm_wide_in_pack_floats",
-                            "rl8_lstm_wide_in_lds_bytes", "rl8_lstm_wide_in_workspace_bytes")
+                            "rl8_lstm_wide_in_lds_bytes", "rl8_lstm_wide_in_workspace_bytes",
+                            "rl8_lstm_stack256_lds_bytes", "rl8_lstm_stack256_pack_floats",
+                            "rl8_lstm_stack256_workspace_bytes")
                 else C.c_int
             )
         built = int(lib.rl8_abi_version(None, 0))
@@ -2420,6 +2429,81 @@ def lstm_wide_in_wgrad(dgates: torch.Tensor, x: torch.Tensor) -> tuple[torch.Ten
 
 
 # --------------------------------------------------------------------------- #
+# The layers above the first of a width-256 stack: their input is the layer below's hs (lstm_stack256_kernels.hip).
+# --------------------------------------------------------------------------- #
+def lstm_stack256_supports() -> bool:
+    return bool(load().rl8_lstm_stack256_supports())
+
+
+def lstm_stack256_pack(w_ih: torch.Tensor, w_hh: torch.Tensor, b_ih: torch.Tensor, b_hh: torch.Tensor) -> torch.Tensor:
+    """An upper layer's torch.nn.LSTM parameters (``weight_ih_lk``, ``weight_hh_lk`` [1024, 256], the two biases
+    [1024]) -> per gate ``[w_hh | w_ih | b_ih + b_hh | 0 x 7]`` in MFMA fragment order, K = 520."""
+    if _lstm_pack_params(w_ih, w_hh, b_ih, b_hh) != LSTM_HIDDEN:
+        raise ValueError(f"w_ih must be [1024, {LSTM_HIDDEN}]")
+    lib = load()
+    packed = torch.empty(int(lib.rl8_lstm_stack256_pack_floats()), dtype=torch.float32, device=w_hh.device)
+    _check(lib.rl8_lstm_stack256_pack_f32(_ptr(w_ih.detach()), _ptr(w_hh.detach()), _ptr(b_ih.detach()), _ptr(b_hh.detach()),
+                                          _ptr(packed), _stream()), "rl8_lstm_stack256_pack_f32")
+    return packed
+
+
+def lstm_stack256_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_packed: torch.Tensor, *,
+                          save: bool = False, state_out: None | tuple[torch.Tensor, torch.Tensor] = None):
+    """x [B, L, 256] (the layer below's ``hs``), h0 / c0 [B, 256] -> (hs [B, L, 256], hn, cn [B, 256], gates, cs) as
+    :func:`lstm_forward` returns them; ``w_packed`` from :func:`lstm_stack256_pack`. ``state_out``: the caller's
+    ``(hn, cn)`` to write."""
+    x = _dense(x.detach(), torch.float32, "x")
+    if x.ndim != 3 or x.shape[2] != LSTM_HIDDEN or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"x must be [B, L, {LSTM_HIDDEN}]")
+    b, l = x.shape[0], x.shape[1]
+    lib = load()
+    _lstm_states_256(h0, c0, b)
+    if w_packed.numel() != int(lib.rl8_lstm_stack256_pack_floats()) or w_packed.dtype != torch.float32:
+        raise ValueError("w_packed must come from lstm_stack256_pack")
+    hs, hn, cn, gates, cs = _lstm_outputs(b, l, LSTM_HIDDEN, x.device, save, state_out)
+    with _timed("lstm_stack256_forward_save" if save else "lstm_stack256_forward", b * l):
+        _check(lib.rl8_lstm_stack256_forward_f32(_ptr(x), b, l, _ptr(h0), _ptr(c0), _ptr(w_packed), _ptr(hs), _ptr(hn),
+                                                 _ptr(cn), _ptr(gates), _ptr(cs), _stream()),
+               "rl8_lstm_stack256_forward_f32")
+    return hs, hn, cn, gates, cs
+
+
+_lstm_stack256_ws: dict[tuple[int, int], torch.Tensor] = {}
+
+
+def lstm_stack256_dx(dgates: torch.Tensor, wiht_packed: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """(dx [M, 256] = dgates @ w_ih, db [1024] = the column sums of dgates) from one read of ``dgates`` [M, 1024];
+    ``wiht_packed`` = :func:`lstm_pack_transposed` of the layer's ``weight_ih_lk`` [1024, 256]. fp32 MFMA; the column
+    sums in fp32 per workgroup, then over the workgroups in order in fp64: deterministic."""
+    dgates = _dense(dgates, torch.float32, "dgates")
+    if dgates.ndim != 2 or dgates.shape[1] != 4 * LSTM_HIDDEN or dgates.shape[0] < 1:
+        raise ValueError("dgates must be [M, 1024]")
+    if wiht_packed.numel() != 4 * LSTM_HIDDEN * LSTM_HIDDEN or wiht_packed.dtype != torch.float32:
+        raise ValueError("wiht_packed must come from lstm_pack_transposed(weight_ih)")
+    m, lib, dev = dgates.shape[0], load(), dgates.device
+    nbytes = int(lib.rl8_lstm_stack256_workspace_bytes(1 << 40))  # (the widest grid: one workspace per stream)
+    ws = _per_stream(_lstm_stack256_ws, dev, lambda: torch.empty(nbytes // 4, dtype=torch.float32, device=dev))
+    dx = torch.empty(m, LSTM_HIDDEN, dtype=torch.float32, device=dev)
+    db = torch.empty(4 * LSTM_HIDDEN, dtype=torch.float32, device=dev)
+    with _timed("lstm_stack256_dx", m):
+        _check(lib.rl8_lstm_stack256_dx_f32(_ptr(dgates), m, _ptr(wiht_packed), _ptr(ws), _ptr(dx), _ptr(db), _stream()),
+               "rl8_lstm_stack256_dx_f32")
+    return dx, db
+
+
+def lstm_stack256_backward(below: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, hs: torch.Tensor, gates: torch.Tensor,
+                           cs: torch.Tensor, dhs: torch.Tensor, whht_packed: None | torch.Tensor,
+                           wiht_packed: torch.Tensor, *, wgrad: str, rows_packed: None | torch.Tensor = None,
+                           h0_bound: None | torch.Tensor = None) -> dict[str, torch.Tensor]:
+    """The backward of a layer above the first of a width-256 stack: ``below`` [B, L, 256] is the layer below's ``hs``,
+    the rest what :func:`lstm_stack256_forward` saved. :func:`lstm_backward`'s backward through time and ``W_hh``
+    loop on its ``wgrad`` route; ``w_ih`` = dgates^T @ below from one more accumulation of that route's entry over all
+    B * L rows; ``b`` and ``dx`` [B, L, 256] -- dL/dhs of the layer below -- from :func:`lstm_stack256_dx`."""
+    return lstm_backward(below, h0, c0, hs, gates, cs, dhs, whht_packed, wgrad=wgrad, rows_packed=rows_packed,
+                         h0_bound=h0_bound, hs_bound=1.0, wide_in=True, upper=wiht_packed)
+
+
+# --------------------------------------------------------------------------- #
 # Narrow LSTMs: one layer (or layer 0 of a stack), hidden width 64 or 128, d_in <= 16 (lstm_narrow_kernels.hip).
 # --------------------------------------------------------------------------- #
 LSTM_NARROW_HIDDEN = (64, 128)
@@ -2734,6 +2818,8 @@ def lstm_rows_backward(c0: torch.Tensor, gates: torch.Tensor, cs: torch.Tensor, 
 _lstm_colsum_ws: dict[tuple, torch.Tensor] = {}
 #: fewest sequences the four-gate weight-gradient launch takes (rl8_lstm_wgrad_f16_f32)
 LSTM_WGRAD_GATES_MIN_ROWS = 128
+#: rows one launch of a weight-gradient kernel sums (tower_launch.hip.h: kWgradSegmentRows)
+WGRAD_SEGMENT_ROWS = 1 << 23
 
 
 def lstm_backward(
@@ -2741,6 +2827,7 @@ def lstm_backward(
     dhs: None | torch.Tensor, whht_packed: None | torch.Tensor, *, wgrad: None | str = None, split: bool = True,
     rows_packed: None | torch.Tensor = None, h0_bound: None | torch.Tensor = None,
     heads: None | tuple[torch.Tensor, torch.Tensor] = None, hs_bound: None | float = None, wide_in: bool = False,
+    upper: None | torch.Tensor = None,
 ) -> dict[str, torch.Tensor]:
     """Parameter gradients of the LSTM given ``dhs`` [B, L, 256] (gradient of every
     ``h_t``) and what ``lstm_forward(..., save=True)`` returned. Returns ``w_ih``,
@@ -2760,10 +2847,15 @@ def lstm_backward(
     The fp16 planes of the weight gradient are scaled by it: a value above the bound would overflow them.
     ``wide_in``: ``x`` is 8 to 128 floats wide (what :func:`lstm_wide_in_forward` saved): without ``rows_packed`` the
     backward through time is ``rl8_lstm_backward_dgates_f32``, every ``W_hh`` launch runs without column sums (no
-    per-step copies of ``x``), and ``w_ih`` / ``b`` come from one :func:`lstm_wide_in_wgrad` launch over all rows."""
+    per-step copies of ``x``), and ``w_ih`` / ``b`` come from one :func:`lstm_wide_in_wgrad` launch over all rows.
+    ``upper`` (with ``wide_in``; :func:`lstm_stack256_backward`): this is a layer above the first of a stack, ``x`` the 256-wide
+    ``hs`` of the layer below and ``upper`` its ``weight_ih`` from :func:`lstm_pack_transposed`: ``w_ih`` comes from one
+    more accumulation of the route's entry over all B * L rows, ``b`` and "dx" [B, L, 256] from :func:`lstm_stack256_dx`."""
     x = _dense(x.detach(), torch.float32, "x")
     b, l, d_in = x.shape
-    if wide_in and not lstm_wide_in_supports(d_in):
+    if upper is not None and not (wide_in and d_in == LSTM_HIDDEN):
+        raise ValueError(f"lstm_backward: upper needs wide_in and x [B, L, {LSTM_HIDDEN}]")
+    if wide_in and upper is None and not lstm_wide_in_supports(d_in):
         raise ValueError(f"lstm_backward: wide_in with d_in={d_in}")
     if heads is not None and (rows_packed is None or dhs is not None):
         raise ValueError("lstm_backward: heads needs rows_packed and no dhs")
@@ -2840,6 +2932,26 @@ def lstm_backward(
                             (_ptr(xt[t]), d_in, _ptr(cols[t] if four_gates else cols[q, t]), C.byref(crow)))
                 _check(getattr(lib, name)(dgp + (t * 4 * H + q * H) * 4, l * 4 * H, *dg_scale, h_prev, h_pitch, *h_scale, b,
                                           wsp, dwp + 4 * H * H * q, int(t > 0), *col_sums, stream), name)
+    if upper is not None:
+        # dW_ih = dG^T hs_below over all m rows: the W_hh product without the shift, so one accumulation per gate (or one
+        # for the four); |hs_below| < 1.  The plane entries walk their own segments; the fp32 one is handed them here,
+        # and the four-gate entry's last segment must hold its 128 rows.
+        m, dw_ih = b * l, torch.empty(4 * H, H, dtype=torch.float32, device=dev)
+        entry, gates_at_once = name, four_gates
+        if four_gates and (m - 1) % WGRAD_SEGMENT_ROWS + 1 < LSTM_WGRAD_GATES_MIN_ROWS:
+            entry, gates_at_once = "rl8_mlp_wgrad_f16_strided_f32", False
+        segment = m if planes else WGRAD_SEGMENT_ROWS
+        h_scale = (_ptr(torch.ones(1, dtype=torch.float32, device=dev)),) if f16 else ()
+        col_sums = (None, 0, None, None) if planes else ()
+        xp, dwip = _ptr(x), _ptr(dw_ih)
+        with _timed("lstm_wgrad", m):
+            for q in range(1 if gates_at_once else 4):
+                for at in range(0, m, segment):
+                    _check(getattr(lib, entry)(dgp + (at * 4 * H + q * H) * 4, 4 * H, *dg_scale, xp + at * H * 4, H, *h_scale,
+                                               min(segment, m - at), wsp, dwip + 4 * H * H * q, int(at > 0), *col_sums,
+                                               stream), entry)
+        dx, db = lstm_stack256_dx(dgates.view(m, 4 * H), upper)
+        return {"w_ih": dw_ih, "w_hh": dw_hh, "b": db, "dx": dx.view(b, l, H)}
     if wide_in:
         dw_ih, db = lstm_wide_in_wgrad(dgates.view(b * l, 4 * H), x.view(b * l, d_in))
         return {"w_ih": dw_ih, "w_hh": dw_hh, "b": db}

@@ -7,7 +7,9 @@ Interfaces follow the reference's ``src/rl8/models/_recurrent.py``:
 ``state_dict``s load unchanged. A one-layer LSTM of hidden width 256 (d_in <= 128: up
 to 7 floats on the plane kernels, 8 to 128 on the fp32 kernels of
 ``lstm_wide_in_kernels.hip`` unless ``RL8_AMD_WIDE_INPUT_LSTM=0``) or 64 / 128
-(d_in <= 16) runs the fused HIP kernels (``nn/fused_lstm.py``), and so do the
+(d_in <= 16) runs the fused HIP kernels (``nn/fused_lstm.py``), and so do stacks
+(``num_layers >= 2``, no dropout) of width 64 / 128 and -- on the upper-layer kernels of
+``lstm_stack256_kernels.hip``, unless ``RL8_AMD_LSTM_STACK_256=0`` -- of width 256, and the
 ``Linear`` heads on latents of those widths; any other runs the modules.
 
 """
@@ -114,7 +116,8 @@ def _run_lstm(lstm: nn.LSTM, obs: torch.Tensor, states: TensorDict) -> tuple[tor
         if fused is not None:
             fused = fused[0], fused[1].unsqueeze(1), fused[2].unsqueeze(1)
     else:
-        fused = fused_lstm.lstm_stack_forward(lstm, obs, h_first, c_first)
+        fused = (fused_lstm.lstm_stack_forward(lstm, obs, h_first, c_first)
+                 or fused_lstm.lstm_stack256_forward(lstm, obs, h_first, c_first))
     if fused is not None:
         latents, h_new, c_new = fused  # states [B, layers, hidden], the buffer's layout
     else:

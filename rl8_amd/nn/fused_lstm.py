@@ -22,6 +22,11 @@ wide-in"  128 (``hip.lstm_wide_in_supports``)  forward, dW_ih / db), the rows   
 "stack"   two or more layers of the narrow     layer 0 as "narrow", the layers    ``lstm_stack_forward``
           envelope, ``dropout == 0``           above on lstm_narrow_stack_*
           (``hip.lstm_stack_supports``)
+"stack-   two or more layers, H = 256, no      layer 0 as "256" / "256-wide-in"   ``lstm_stack256_forward``
+256"      dropout, layer 0's input inside one  (``_plan`` / ``_wide_input_plan``),  (the ``_StackLSTM`` node)
+          of those two envelopes, and          the layers above on
+          ``RL8_AMD_LSTM_STACK_256`` not 0:    lstm_stack256_kernels.hip, the rows
+          ``_stack256_family``                 backward and W_hh gradients of "256"
 heads     ``Linear(H, n_i)``, sum n_i <= 8,    lstm_kernels.hip (H = 256),        ``heads_forward``
           on latents of any of the widths      lstm_narrow_heads_kernels.hip
 ========  ===================================  =================================  ===========================
@@ -34,7 +39,7 @@ forms the heads' data gradient itself (``lstm_heads_forward``); the reference's 
 The "narrow" and "stack" families return the gradient of their input ``x`` where it requires one -- a model with
 learned parameters in front of the LSTM, such as ``rl8_amd.envs.LSTMTrader``'s embedding -- from one more launch on
 the gate gradients the backward through time has left (``rl8_lstm_narrow_input_grad_f32``); an ``x`` that is
-rollout-buffer data costs nothing. The "256" and "256-wide-in" families form no input gradient and decline an ``x``
+rollout-buffer data costs nothing. The "256", "256-wide-in" and "stack256" families form no input gradient and decline an ``x``
 that requires one under grad mode; no family forms a gradient for the initial states ``h0`` / ``c0``, and every entry point declines
 a call in which one of them requires it (``_declines``). The caller then runs the module, which forms them.
 
@@ -132,12 +137,34 @@ def _wide_input_family_for(lstm: nn.LSTM, x: torch.Tensor) -> None | str:
     return _wide_input_family(lstm) if _input_ok(lstm, x) else None
 
 
+def stack256_lstm_on() -> bool:
+    """``RL8_AMD_LSTM_STACK_256=0`` (read on every call) keeps width-256 LSTMs of two or more layers on the torch module:
+    the tests' and ``tools/lstm_stack256_ab.py``'s yardstick.  On by default."""
+    return os.environ.get("RL8_AMD_LSTM_STACK_256", "1") != "0"
+
+
+def _stack256_family(lstm: nn.LSTM) -> None | str:
+    """"stack256" for two or more layers of width 256 without dropout between them -- batch_first, biased, no
+    projection, one direction -- whose layer 0 reads an input width of the "256" (``hip.lstm_supports``) or, with its
+    switch on, the "256-wide-in" envelope (``hip.lstm_wide_in_supports``), with ``ENABLED`` and the switch
+    ``RL8_AMD_LSTM_STACK_256`` as they are now; else ``None``.  Beside ``_family`` and ``_wide_input_family``, which both
+    answer ``None`` for such a module: their answers are what the one-layer entries and the lean rollout are built on."""
+    if not (ENABLED and lstm.batch_first and lstm.bias and not lstm.bidirectional and lstm.proj_size == 0):
+        return None
+    if lstm.hidden_size != hip.LSTM_HIDDEN or lstm.num_layers < 2 or lstm.dropout != 0:
+        return None
+    d_in = lstm.input_size
+    if not (hip.lstm_supports(d_in) or (_wide_input_supported(d_in) and wide_input_lstm_on())):
+        return None
+    return "stack256" if stack256_lstm_on() and hip.lstm_stack256_supports() else None
+
+
 def _declines(family: None | str, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor) -> bool:
     """A gradient is asked for that ``family``'s node does not form -- of ``h0`` or ``c0`` (any family), of ``x`` at
-    "256" and "256-wide-in" -- and grad mode is on: the entry returns ``None`` instead of handing autograd a ``None``
+    "256", "256-wide-in" and "stack256" -- and grad mode is on: the entry returns ``None`` instead of handing autograd a ``None``
     for it.  Three attribute reads for rollout-buffer data; under ``torch.no_grad()`` nothing can follow and nothing is
     declined."""
-    return ((h0.requires_grad or c0.requires_grad or (family in ("256", "256-wide-in") and x.requires_grad))
+    return ((h0.requires_grad or c0.requires_grad or (family in ("256", "256-wide-in", "stack256") and x.requires_grad))
             and torch.is_grad_enabled())
 
 
@@ -154,6 +181,29 @@ def _packs(lstm: nn.LSTM, kind: str):
     pack = {"step": hip.lstm_pack, "split": hip.lstm_pack_split, "wide": hip.lstm_wide_in_pack,
             "transposed": hip.lstm_pack_transposed, "rows": hip.lstm_rows_backward_pack}[kind]
     packed = pack(*params) if kind in ("step", "split", "wide") else pack(params[1])
+    cache[kind] = (stamp, packed)
+    return packed
+
+
+def _layer_packs(params: tuple, kind: str):
+    """``_packs`` for layer k of a width-256 stack, whose node is handed the parameters and not the module:
+    ``params`` = (weight_ih_l{k}, weight_hh_l{k}, bias_ih_l{k}, bias_hh_l{k}).  Layer 0's kinds are ``_packs``'s; an
+    upper layer's are "stack256" (its fp32 forward), "transposed" / "rows" (its backward through time) and
+    "transposed-ih" (``weight_ih`` for dL/dhs of the layer below).  Cached ON the layer's ``weight_hh`` parameter under
+    the same stamp -- every parameter's ``(_version, data_ptr)`` -- so a pack lives as long as its layer and is re-made
+    when the optimizer has changed a parameter or a tensor has been replaced / moved, not per rollout step."""
+    stamp = tuple((p._version, p.data_ptr()) for p in params)
+    cache = params[1].__dict__.setdefault("_rl8_lstm_packs", {})
+    hit = cache.get(kind)
+    if hit is not None and hit[0] == stamp:
+        return hit[1]
+    if kind in ("step", "split", "wide", "stack256"):
+        packed = {"step": hip.lstm_pack, "split": hip.lstm_pack_split, "wide": hip.lstm_wide_in_pack,
+                  "stack256": hip.lstm_stack256_pack}[kind](*params)
+    elif kind == "rows":
+        packed = hip.lstm_rows_backward_pack(params[1])
+    else:
+        packed = hip.lstm_pack_transposed(params[0 if kind == "transposed-ih" else 1])
     cache[kind] = (stamp, packed)
     return packed
 
@@ -353,6 +403,8 @@ class _StackLSTM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h0, c0, grad_mode, *weights):  # type: ignore[override]
+        if h0.shape[2] == hip.LSTM_HIDDEN:
+            return _stack256_node_forward(ctx, x, h0, c0, grad_mode, weights)
         layers = len(weights) // 4
         need_grad = grad_mode and (any(ctx.needs_input_grad[4:]) or ctx.needs_input_grad[0])
         b, l, hidden = x.shape[0], x.shape[1], h0.shape[2]
@@ -373,6 +425,8 @@ class _StackLSTM(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dhs, dhn, dcn):  # type: ignore[override]
+        if hasattr(ctx, "plans"):
+            return _stack256_node_backward(ctx, dhs)
         x, h0, c0, *saved = ctx.saved_tensors
         layers = len(saved) // 5
         top = saved[5 * (layers - 1) + 2]
@@ -389,6 +443,94 @@ class _StackLSTM(torch.autograd.Function):
         return (g.get("dx"), None, None, None, *grads)
 
 
+def _stack256_node_forward(ctx, x, h0, c0, grad_mode, weights):
+    """:class:`_StackLSTM`'s forward at width 256: layer 0 by the calls :class:`_FusedLSTM` makes on its plan, every
+    upper layer by ``hip.lstm_stack256_forward`` on the lower layer's ``hs``.  The plans -- layer 0's from ``_plan`` or
+    ``_wide_input_plan``, the upper layers' the ``backward_rows`` / ``wgrad`` rules of ``_wide_input_plan`` (their
+    forward is fp32 whatever the switches say) -- are made here, from the shapes and the switches as they are now, and
+    kept on ``ctx``.  No gradient is formed for ``x``, ``h0`` or ``c0`` (``lstm_stack256_forward`` declines them)."""
+    layers = len(weights) // 4
+    need_grad = grad_mode and any(ctx.needs_input_grad[4:])
+    b, d_in = x.shape[0], x.shape[2]
+    plan0 = _plan(d_in, b) if hip.lstm_supports(d_in) else _wide_input_plan(b)
+    plans = (plan0, _wide_input_plan(b))
+    hn, cn = torch.empty_like(h0), torch.empty_like(c0)
+    w0, bound = weights[:4], None
+    if plan0.wide_in:
+        hs, hn0, cn0, gates, cs = hip.lstm_wide_in_forward(x, h0[0], c0[0], _layer_packs(w0, "wide"), save=need_grad)
+    elif plan0.forward_planes:
+        packed, wb = _layer_packs(w0, "split")
+        planes0, bound = _h0_planes(h0[0]) if need_grad else (None, None)
+        hs, hn0, cn0, gates, cs = hip.lstm_forward_split(x, h0[0], c0[0], packed, wb, save=need_grad, h0_planes=planes0)
+    else:
+        hs, hn0, cn0, gates, cs = hip.lstm_forward(x, h0[0], c0[0], _layer_packs(w0, "step"), save=need_grad)
+    hn[0].copy_(hn0)
+    cn[0].copy_(cn0)
+    saved = [hs, gates, cs]
+    for k in range(1, layers):
+        hs, _, _, gates, cs = hip.lstm_stack256_forward(hs, h0[k], c0[k], _layer_packs(weights[4 * k:4 * k + 4], "stack256"),
+                                                        save=need_grad, state_out=(hn[k], cn[k]))
+        saved += [hs, gates, cs]
+    ctx.set_materialize_grads(False)
+    if need_grad:
+        ctx.plans, ctx.weights, ctx.h0_bound = plans, weights, bound
+        ctx.save_for_backward(x, h0, c0, *saved)
+    ctx.mark_non_differentiable(hn, cn)
+    return hs, hn, cn
+
+
+def _stack256_node_backward(ctx, dhs):
+    """The backward of ``_stack256_node_forward``, on the plans it kept: the layers from the top down, each upper
+    layer's "dx" the ``dhs`` of the layer below (nothing else reads that layer's outputs), then layer 0 by
+    ``hip.lstm_backward`` as :class:`_FusedLSTM` calls it."""
+    x, h0, c0, *saved = ctx.saved_tensors
+    layers = len(saved) // 3
+    plan0, upper = ctx.plans
+    dhs = torch.zeros_like(saved[-3]) if dhs is None else dhs.contiguous().float()
+    grads: list = [None] * (4 * layers)
+
+    def through_time(params, plan):  # (whht_packed, rows_packed) of a layer, as _FusedLSTM.backward chooses them
+        packed = _layer_packs(params, "rows" if plan.backward_rows else "transposed")
+        return (None, packed) if plan.backward_rows else (packed, None)
+
+    for k in range(layers - 1, 0, -1):
+        params = ctx.weights[4 * k:4 * k + 4]
+        hs, gates, cs = saved[3 * k:3 * k + 3]
+        whht, rows = through_time(params, upper)
+        g = hip.lstm_stack256_backward(saved[3 * (k - 1)], h0[k], c0[k], hs, gates, cs, dhs, whht,
+                                       _layer_packs(params, "transposed-ih"), wgrad=upper.wgrad, rows_packed=rows)
+        grads[4 * k:4 * k + 4] = g["w_ih"], g["w_hh"], g["b"], g["b"]
+        dhs = g["dx"]
+    hs, gates, cs = saved[:3]
+    whht, rows = through_time(ctx.weights[:4], plan0)
+    g = hip.lstm_backward(x, h0[0], c0[0], hs, gates, cs, dhs, whht, wgrad=plan0.wgrad, rows_packed=rows,
+                          h0_bound=ctx.h0_bound, hs_bound=1.0, **_wide_args(plan0))
+    grads[:4] = g["w_ih"], g["w_hh"], g["b"], g["b"]
+    return (None, None, None, None, *grads)
+
+
+def _stack_apply(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
+    """``_StackLSTM`` on ``lstm``'s layers with the states turned from [B, layers, H] to the node's [layers, B, H] and
+    back."""
+    weights = [getattr(lstm, f"{name}_l{k}") for k in range(lstm.num_layers) for name in _STACK_PARAMS]
+    hs, hn, cn = _StackLSTM.apply(
+        x.contiguous(), h0.float().transpose(0, 1).contiguous(), c0.float().transpose(0, 1).contiguous(),
+        torch.is_grad_enabled(), *weights,
+    )
+    return hs, hn.transpose(0, 1), cn.transpose(0, 1)
+
+
+def lstm_stack256_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
+    """``lstm(x, (h0, c0))`` for a stack of two or more layers of width 256 (``_stack256_family``): ``x`` [B, L, d],
+    ``h0`` / ``c0`` [B, layers, 256] -> ``(hs_top [B, L, 256], h_n [B, layers, 256], c_n [B, layers, 256])``, or ``None``
+    when this LSTM / input is not eligible.  The stack forms no gradient for ``x``, ``h0`` or ``c0``: a call in which one
+    of them requires it under grad mode is declined (``None``) and the caller runs the module; under
+    ``torch.no_grad()`` nothing is declined.  None flows out of ``h_n``, ``c_n``."""
+    if not _input_ok(lstm, x) or _stack256_family(lstm) != "stack256" or _declines("stack256", x, h0, c0):
+        return None
+    return _stack_apply(lstm, x, h0, c0)
+
+
 def lstm_stack_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
     """``lstm(x, (h0, c0))`` for a stack of two or more layers of width 64 / 128: ``x`` [B, L, d], ``h0`` / ``c0``
     [B, layers, H] (the rollout buffer's layout) -> ``(hs_top [B, L, H], h_n [B, layers, H], c_n [B, layers, H])``,
@@ -398,12 +540,7 @@ def lstm_stack_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: tor
     gradient under grad mode is declined (``None``)."""
     if _family_for(lstm, x) != "stack" or _declines("stack", x, h0, c0):
         return None
-    weights = [getattr(lstm, f"{name}_l{k}") for k in range(lstm.num_layers) for name in _STACK_PARAMS]
-    hs, hn, cn = _StackLSTM.apply(
-        x.contiguous(), h0.float().transpose(0, 1).contiguous(), c0.float().transpose(0, 1).contiguous(),
-        torch.is_grad_enabled(), *weights,
-    )
-    return hs, hn.transpose(0, 1), cn.transpose(0, 1)
+    return _stack_apply(lstm, x, h0, c0)
 
 
 def lstm_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
