@@ -53,6 +53,9 @@
  *                rl8_mlp_wgrad_gate_bits_f32, rl8_mlp_wgrad_fused_split_f32, rl8_mlp_wgrad_fused_pair_f32,
  *                rl8_mlp_pack_w2_f16, rl8_mlp_pack_w2_f16_gate, rl8_mlp_dout_pair_check, the *_supports / *_bytes /
  *                *_floats / *_max_rows queries
+ *     towers, hidden width 256 with heads of 9 to 128 outputs in all (RL8_AMD_WIDE_HEAD_TOWERS=0: the torch modules):
+ *                rl8_mlp_wide_out_{pack,forward,backward,wgrad}_f32 and their *_supports / *_bytes / *_floats /
+ *                *_max_rows queries, with rl8_mlp_pack_w2_f32 and the dW2 entries of the wide-input towers
  *     recurrent  rl8_lstm_pack_split, rl8_lstm_split_state[_bound], rl8_lstm_step_split_f32,
  *                rl8_lstm_rows_backward_pack, rl8_lstm_rows_backward[_heads]_f32, rl8_lstm_wgrad_f16_f32,
  *                rl8_linear_heads_{forward,forward_pair,backward}_f32
@@ -1215,6 +1218,49 @@ int rl8_mlp_wide_in_backward_f32(const float *h1, const float *h2, const float *
 int64_t rl8_mlp_wide_in_workspace_bytes(int d_in);
 int rl8_mlp_wide_in_wgrad_f32(const float *dz1, const float *x, int64_t m, int d_in, float *workspace, float *dw1_out,
                               int accumulate, void *stream);
+
+/* ---- Wide-head towers (DEFAULT PRODUCT PATH): Linear(d_in, 256) ReLU Linear(256, 256) ReLU Linear(256, n_out),
+ * 1 <= d_in <= 128, 9 <= n_out <= 128 summed over the heads (mlp_wide_out_kernels.hip): fp32 throughout, every product,
+ * the head and its gradients included, on v_mfma_f32_32x32x2_f32.  The entries above keep their envelopes (n_out <= 8).
+ * rl8_mlp_wide_out_supports: 1 inside the envelope, else 0 (host only).
+ * rl8_mlp_wide_out_pack_f32: a torch-layout weight -> MFMA fragment order, zero-padded, rl8_mlp_wide_out_pack_floats(
+ *   matrix, n) floats, `packed` 16-byte aligned.  matrix 0: w = W1 [256][n], n = d_in in 1..128, for the forward
+ *   (256 * 8 * ceil(n / 8) floats); matrix 1: w = W3 [n][256], n = n_out, for the forward (32 * ceil(n / 32) * 256
+ *   floats); matrix 2: the same W3 for the data gradient (256 * 8 * ceil(n / 8) floats).
+ * rl8_mlp_wide_out_forward_f32: x [m][d_in] -> out [m][n_out] = b3 + h2 W3^T; w1_packed / w3_packed from matrix 0 / 1,
+ *   w2_packed from rl8_mlp_pack_w2_f32(transposed = 0).  save_h1 / save_h2 ([m][256] each, 16-byte aligned): both or
+ *   neither; with them the post-ReLU activations are stored for the backward entries; `out` is the same bits either way.
+ * rl8_mlp_wide_out_backward_f32: from h1, h2, dout [m][n_out], w3t_packed (matrix 2) and w2t_packed
+ *   (rl8_mlp_pack_w2_f32(transposed = 1)) writes dz2_out [m][256] = (dout W3) . [h2 > 0] and dz1_out [m][256] =
+ *   (dZ2 W2) . [h1 > 0] (ReLU'(0) = 0), and one row of partials per workgroup, rl8_mlp_wide_out_partial_floats(n_out)
+ *   floats each: [db1 (256) | db2 (256) | db3 (n_out)]; *partial_rows_out (host) rows, at most
+ *   rl8_mlp_wide_out_max_rows(), a function of m alone; the caller sums them in row order.  No dW3 (it is a product
+ *   over the rows: below) and no gradient of x.  h1, h2, dz1_out, dz2_out and the packs 16-byte aligned.
+ * rl8_mlp_wide_out_wgrad_f32: out [256][c] = (accumulate ? out : 0) + a^T b over the m rows, a [m][256] (16-byte
+ *   aligned), b [m][c], 1 <= c <= 128, fp32 MFMA, one slab per workgroup in `workspace`
+ *   (rl8_mlp_wide_out_workspace_bytes(c) bytes, no initialisation) summed in slab order; the grid is a function of m
+ *   alone: bitwise reproducible.  `transpose`: out is [c][256].  dW1 = dz1^T x (c = d_in, any d_in of the envelope) and
+ *   dW3 = (h2^T dout)^T (c = n_out, transpose = 1).  (dW2 = dz2^T h1 is rl8_mlp_wgrad_split_strided_f32 or
+ *   rl8_mlp_wgrad_f32.)
+ * rl8_mlp_wide_out_lds_bytes: the dynamic LDS of one workgroup of kernel 0 (forward, two workgroups per CU), 1 (data
+ *   gradient, two per CU) or 2 (weight gradient at c columns, one per CU); host only.
+ * Every other pointer 4-byte aligned; RL8_ENULL / RL8_ESIZE (m < 1, a width outside the envelope) / RL8_EALIGN before
+ * any launch.  The helpers return RL8_ESIZE for a width outside the envelope. */
+int rl8_mlp_wide_out_supports(int d_in, int n_out);
+int64_t rl8_mlp_wide_out_lds_bytes(int kernel, int c);
+int64_t rl8_mlp_wide_out_pack_floats(int matrix, int n);
+int rl8_mlp_wide_out_pack_f32(const float *w, int matrix, int n, float *packed, void *stream);
+int rl8_mlp_wide_out_forward_f32(const float *x, int64_t m, int d_in, const float *w1_packed, const float *b1,
+                                 const float *w2_packed, const float *b2, const float *w3_packed, const float *b3,
+                                 int n_out, float *out, float *save_h1, float *save_h2, void *stream);
+int64_t rl8_mlp_wide_out_partial_floats(int n_out);
+int rl8_mlp_wide_out_max_rows(void);
+int rl8_mlp_wide_out_backward_f32(const float *h1, const float *h2, const float *dout, int64_t m,
+                                  const float *w2t_packed, const float *w3t_packed, int n_out, float *dz1_out,
+                                  float *dz2_out, float *partials, int *partial_rows_out /*host*/, void *stream);
+int64_t rl8_mlp_wide_out_workspace_bytes(int c);
+int rl8_mlp_wide_out_wgrad_f32(const float *a, const float *b, int64_t m, int c, float *workspace, float *out,
+                               int accumulate, int transpose, void *stream);
 
 /* ---- BatchNorm1d behind the first layer of a narrow tower, folded into that layer (batchnorm_tower_kernels.hip).  In
  * training mode the norm of z1 = x W1^T + b1 over the batch is an affine map of x: with mu = mean_i x_i and the biased

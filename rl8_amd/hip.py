@@ -284,6 +284,16 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_mlp_wide_in_backward_f32": [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(C.c_int), _vp],
     "rl8_mlp_wide_in_workspace_bytes": [_i32],
     "rl8_mlp_wide_in_wgrad_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp],
+    "rl8_mlp_wide_out_supports": [_i32, _i32],
+    "rl8_mlp_wide_out_lds_bytes": [_i32, _i32],
+    "rl8_mlp_wide_out_pack_floats": [_i32, _i32],
+    "rl8_mlp_wide_out_pack_f32": [_vp, _i32, _i32, _vp, _vp],
+    "rl8_mlp_wide_out_forward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    "rl8_mlp_wide_out_partial_floats": [_i32],
+    "rl8_mlp_wide_out_max_rows": [],
+    "rl8_mlp_wide_out_backward_f32": [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(C.c_int), _vp],
+    "rl8_mlp_wide_out_workspace_bytes": [_i32],
+    "rl8_mlp_wide_out_wgrad_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp],
     "rl8_tower_limits": [C.POINTER(C.c_int)],
     "rl8_tower_moments_workspace_bytes": [_i64, _i32],
     "rl8_tower_moments_f64": [_vp, _i64, _i32, _vp, _vp, _vp, _vp],
@@ -343,6 +353,8 @@ def load() -> C.CDLL:
                             "rl8_feedforward_workspace_floats", "rl8_tower_moments_workspace_bytes",
                             "rl8_mlp_wide_in_pack_floats", "rl8_mlp_wide_in_partial_floats", "rl8_mlp_wide_in_lds_bytes",
                             "rl8_mlp_wide_in_workspace_bytes", "rl8_lstm_wide_in_pack_floats",
+                            "rl8_mlp_wide_out_pack_floats", "rl8_mlp_wide_out_partial_floats",
+                            "rl8_mlp_wide_out_lds_bytes", "rl8_mlp_wide_out_workspace_bytes",
                             "rl8_lstm_wide_in_lds_bytes", "rl8_lstm_wide_in_workspace_bytes",
                             "rl8_lstm_stack256_lds_bytes", "rl8_lstm_stack256_pack_floats",
                             "rl8_lstm_stack256_workspace_bytes")
@@ -2155,6 +2167,134 @@ def mlp_wide_in_wgrad(dz1: torch.Tensor, x: torch.Tensor, out: None | torch.Tens
     with _timed("mlp_wide_in_wgrad", m):
         _check(lib.rl8_mlp_wide_in_wgrad_f32(_ptr(dz1), _ptr(x), m, d_in, _ptr(ws), _ptr(out), int(accumulate), _stream()),
                "rl8_mlp_wide_in_wgrad_f32")
+    return out
+
+
+# --------------------------------------------------------------------------- #
+# Wide-head towers: hidden width 256, 1 to 128 inputs, heads of 9 to 128 outputs in all (mlp_wide_out_kernels.hip).
+# --------------------------------------------------------------------------- #
+MLP_WIDE_OUT_W1, MLP_WIDE_OUT_W3, MLP_WIDE_OUT_W3T = 0, 1, 2  # the `matrix` of rl8_mlp_wide_out_pack_f32
+
+
+def mlp_wide_out_supports(d_in: int, n_out: int) -> bool:
+    return bool(load().rl8_mlp_wide_out_supports(int(d_in), int(n_out)))
+
+
+def _mlp_wide_out_pack(w: torch.Tensor, matrix: int, n: int, name: str) -> torch.Tensor:
+    lib = load()
+    floats = int(lib.rl8_mlp_wide_out_pack_floats(matrix, n))
+    if floats < 0:
+        raise ValueError(f"no wide-head tower kernel for a {name} of {tuple(w.shape)}")
+    packed = torch.empty(floats, dtype=torch.float32, device=w.device)
+    _check(lib.rl8_mlp_wide_out_pack_f32(_ptr(w), matrix, n, _ptr(packed), _stream()), "rl8_mlp_wide_out_pack_f32")
+    return packed
+
+
+def mlp_wide_out_pack_w1(w1: torch.Tensor) -> torch.Tensor:
+    """[256, d_in] nn.Linear weight, 1 <= d_in <= 128 -> MFMA fragment order, zero-padded to whole k-groups of 8."""
+    w1 = _dense(w1.detach(), torch.float32, "w1")
+    if w1.ndim != 2 or w1.shape[0] != MLP_HIDDEN:
+        raise ValueError("w1 must be [256, d_in]")
+    return _mlp_wide_out_pack(w1, MLP_WIDE_OUT_W1, w1.shape[1], "w1")
+
+
+def mlp_wide_out_pack_w3(w3: torch.Tensor, *, transposed: bool = False) -> torch.Tensor:
+    """[n_out, 256] head weight (the heads of a tower concatenated), 9 <= n_out <= 128 -> MFMA fragment order: the B
+    operand of the forward's ``h2 @ w3.T`` (n_out zero-padded to 32-column tiles), or, ``transposed``, of the data
+    gradient's ``dout @ w3`` (n_out zero-padded to k-groups of 8)."""
+    w3 = _dense(w3.detach(), torch.float32, "w3")
+    if w3.ndim != 2 or w3.shape[1] != MLP_HIDDEN:
+        raise ValueError("w3 must be [n_out, 256]")
+    return _mlp_wide_out_pack(w3, MLP_WIDE_OUT_W3T if transposed else MLP_WIDE_OUT_W3, w3.shape[0], "w3")
+
+
+def mlp_wide_out_forward(
+    x: torch.Tensor, w1_packed: torch.Tensor, b1: torch.Tensor, w2_packed: torch.Tensor, b2: torch.Tensor,
+    w3_packed: torch.Tensor, b3: torch.Tensor, *, save: bool = False,
+) -> tuple[torch.Tensor, None | torch.Tensor, None | torch.Tensor]:
+    """x [M, d_in], 1 <= d_in <= 128 -> out [M, n_out], n_out = ``b3.shape[0]`` in 9..128; with ``save`` also the
+    post-ReLU activations h1, h2 ([M, 256]) for the backward pass (``out`` is the same bits either way).  ``w1_packed``
+    from ``mlp_wide_out_pack_w1``, ``w2_packed`` from ``mlp_pack_w2``, ``w3_packed`` from ``mlp_wide_out_pack_w3``."""
+    x = _dense(x.detach(), torch.float32, "x")
+    if x.ndim != 2:
+        raise ValueError("x must be [M, d_in]")
+    m, d_in = x.shape
+    n_out = b3.shape[0]
+    for name, t, shape in (("b1", b1, (MLP_HIDDEN,)), ("b2", b2, (MLP_HIDDEN,)), ("b3", b3, (n_out,))):
+        _shaped(t, shape, name)
+    lib = load()
+    if m < 1 or not mlp_wide_out_supports(d_in, n_out):
+        raise ValueError(f"no wide-head tower kernel for m={m}, d_in={d_in}, n_out={n_out}")
+    if w1_packed.numel() != int(lib.rl8_mlp_wide_out_pack_floats(MLP_WIDE_OUT_W1, d_in)) or w1_packed.dtype != torch.float32:
+        raise ValueError("w1_packed must come from mlp_wide_out_pack_w1 for this d_in")
+    if w2_packed.numel() != MLP_HIDDEN * MLP_HIDDEN or w2_packed.dtype != torch.float32:
+        raise ValueError("w2_packed must come from mlp_pack_w2")
+    if w3_packed.numel() != int(lib.rl8_mlp_wide_out_pack_floats(MLP_WIDE_OUT_W3, n_out)) or w3_packed.dtype != torch.float32:
+        raise ValueError("w3_packed must come from mlp_wide_out_pack_w3 for this n_out")
+    out = torch.empty(m, n_out, dtype=torch.float32, device=x.device)
+    h1 = torch.empty(m, MLP_HIDDEN, dtype=torch.float32, device=x.device) if save else None
+    h2 = torch.empty(m, MLP_HIDDEN, dtype=torch.float32, device=x.device) if save else None
+    with _timed("mlp_wide_out_forward_save" if save else "mlp_wide_out_forward", m):
+        _check(lib.rl8_mlp_wide_out_forward_f32(_ptr(x), m, d_in, _ptr(w1_packed), _ptr(b1.detach()), _ptr(w2_packed),
+                                                _ptr(b2.detach()), _ptr(w3_packed), _ptr(b3.detach()), n_out, _ptr(out),
+                                                _ptr(h1), _ptr(h2), _stream()),
+               "rl8_mlp_wide_out_forward_f32")
+    return out, h1, h2
+
+
+def mlp_wide_out_backward(h1: torch.Tensor, h2: torch.Tensor, dout: torch.Tensor, w2t_packed: torch.Tensor,
+                          w3t_packed: torch.Tensor, dz1: torch.Tensor, dz2: torch.Tensor, partials: torch.Tensor) -> int:
+    """The data gradient of the ``rows`` = ``h1.shape[0]`` rows: fills ``dz1`` / ``dz2`` ([rows, 256]) and the first
+    rows of ``partials`` ([rl8_mlp_wide_out_max_rows, 512 + n_out]: db1 | db2 | db3 per workgroup); returns how many
+    partial rows were written.  ``w3t_packed`` from ``mlp_wide_out_pack_w3(w3, transposed=True)``."""
+    rows, n_out = h1.shape[0], dout.shape[-1]
+    lib = load()
+    width = int(lib.rl8_mlp_wide_out_partial_floats(n_out))
+    if rows < 1 or width < 0:
+        raise ValueError(f"no wide-head tower kernel for m={rows}, n_out={n_out}")
+    for name, t, shape in (("h1", h1, (rows, MLP_HIDDEN)), ("h2", h2, (rows, MLP_HIDDEN)), ("dout", dout, (rows, n_out)),
+                           ("dz1", dz1, (rows, MLP_HIDDEN)), ("dz2", dz2, (rows, MLP_HIDDEN)),
+                           ("partials", partials, (int(lib.rl8_mlp_wide_out_max_rows()), width))):
+        _shaped(t, shape, name)
+    if w2t_packed.numel() != MLP_HIDDEN * MLP_HIDDEN or w2t_packed.dtype != torch.float32:
+        raise ValueError("w2t_packed must come from mlp_pack_w2(..., transposed=True)")
+    if w3t_packed.numel() != int(lib.rl8_mlp_wide_out_pack_floats(MLP_WIDE_OUT_W3T, n_out)) or w3t_packed.dtype != torch.float32:
+        raise ValueError("w3t_packed must come from mlp_wide_out_pack_w3(..., transposed=True) for this n_out")
+    written = C.c_int(0)
+    with _timed("mlp_wide_out_backward", rows):
+        _check(lib.rl8_mlp_wide_out_backward_f32(_ptr(h1), _ptr(h2), _ptr(dout), rows, _ptr(w2t_packed), _ptr(w3t_packed),
+                                                 n_out, _ptr(dz1), _ptr(dz2), _ptr(partials), C.byref(written), _stream()),
+               "rl8_mlp_wide_out_backward_f32")
+    return written.value
+
+
+def mlp_wide_out_wgrad(a: torch.Tensor, b: torch.Tensor, out: None | torch.Tensor = None, *, accumulate: bool = False,
+                       transpose: bool = False) -> torch.Tensor:
+    """[256, c] = a^T @ b over the M rows, a [M, 256], b [M, c], 1 <= c <= 128 (fp32 MFMA, deterministic); with
+    ``transpose`` the result is written [c, 256].  ``out`` with ``accumulate``: added to what ``out`` holds (the
+    segments of a long batch, in order).  dW1 = ``(dz1, x)``; dW3 = ``(h2, dout, transpose=True)``."""
+    b = _dense(b.detach(), torch.float32, "b")
+    if b.ndim != 2:
+        raise ValueError("b must be [M, c]")
+    m, c = b.shape
+    _shaped(a, (m, MLP_HIDDEN), "a")
+    lib = load()
+    nbytes = int(lib.rl8_mlp_wide_out_workspace_bytes(c))
+    if m < 1 or nbytes < 0:
+        raise ValueError(f"no wide-head tower kernel for m={m}, c={c}")
+    # (the slabs of the wide-input towers' dW1: the same size at 128 columns, the same stream order)
+    ws = _per_stream(_wide_in_ws, b.device, lambda: torch.empty(int(lib.rl8_mlp_wide_out_workspace_bytes(128)) // 4,
+                                                                 dtype=torch.float32, device=b.device))
+    shape = (c, MLP_HIDDEN) if transpose else (MLP_HIDDEN, c)
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs out")
+        out = torch.empty(shape, dtype=torch.float32, device=b.device)
+    _shaped(out, shape, "out")
+    with _timed("mlp_wide_out_wgrad", m):
+        _check(lib.rl8_mlp_wide_out_wgrad_f32(_ptr(a), _ptr(b), m, c, _ptr(ws), _ptr(out), int(accumulate), int(transpose),
+                                              _stream()),
+               "rl8_mlp_wide_out_wgrad_f32")
     return out
 
 

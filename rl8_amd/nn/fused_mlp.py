@@ -26,6 +26,10 @@ Width-256 towers whose first layer reads 17 to 128 floats (family "wide input",
 a matrix-core product, the forward saves h1 and h2, and the backward walks the rows in
 segments (dW2 alone on exact bf16 planes, ``WIDE_INPUT_DW2_PLANES``).  ``RL8_AMD_WIDE_INPUT_TOWERS=0`` sends them to the torch modules.
 
+Width-256 towers whose heads have 9 to 128 outputs in all, behind 1 to 128 inputs (family "wide head",
+``mlp_wide_out_kernels.hip``), run through the same node: there the head, ``dout @ W3`` and dW3 are
+matrix-core products as well.  ``RL8_AMD_WIDE_HEAD_TOWERS=0`` sends them to the torch modules.
+
 ``tower_forward`` falls back to the module's own eager path whenever the tower
 is none of these shapes (other widths, activations, other norm layers, non-HIP or
 non-fp32 inputs), so custom models are unaffected.
@@ -137,7 +141,8 @@ class _TowerPlan:
 
     @property
     def recordable(self) -> bool:
-        """Planes both ways: the rollout record / replay path."""
+        """Planes both ways: the rollout record / replay path.  (The wide-input and wide-head families have no planes
+        and no plan: ``tower_forward`` returns before the record and the replay are asked.)"""
         return self.backward_planes
 
 
@@ -808,15 +813,17 @@ def _wide_input_family(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | t
     return l1, l2
 
 
-def _packed_w1(layer: nn.Linear) -> torch.Tensor:
-    """``hip.mlp_wide_in_pack_w1(layer.weight)``, cached on the layer as ``_packed`` caches W2: re-made when the
-    optimizer has changed the weight (version counter) or the weight tensor has been replaced / moved."""
+def _packed_w1(layer: nn.Linear, family: str = "in") -> torch.Tensor:
+    """``hip.mlp_wide_in_pack_w1(layer.weight)`` (``family`` "out": ``hip.mlp_wide_out_pack_w1``, which takes any
+    1 <= d_in <= 128), cached on the layer as ``_packed`` caches W2: re-made when the optimizer has changed the weight
+    (version counter) or the weight tensor has been replaced / moved."""
     w1 = layer.weight
-    hit = layer.__dict__.get("_rl8_w1_pack")
+    key = "_rl8_w1_pack" if family == "in" else "_rl8_w1_pack_out"
+    hit = layer.__dict__.get(key)
     if hit is not None and hit[0] == w1._version and hit[1] == w1.data_ptr():
         return hit[2]
-    packed = hip.mlp_wide_in_pack_w1(w1)
-    layer.__dict__["_rl8_w1_pack"] = (w1._version, w1.data_ptr(), packed)
+    packed = hip.mlp_wide_in_pack_w1(w1) if family == "in" else hip.mlp_wide_out_pack_w1(w1)
+    layer.__dict__[key] = (w1._version, w1.data_ptr(), packed)
     return packed
 
 
@@ -830,8 +837,13 @@ class _WideInputTower(torch.autograd.Function):
     def forward(ctx, x, w1, b1, w2, b2, w3, b3, layer1, layer2, grad_mode):  # type: ignore[override]
         # (grad_mode: the caller's; inside forward() grad mode is always off -- see _FusedTower)
         need_grad = grad_mode and any(ctx.needs_input_grad[1:7])
-        out, h1, h2 = hip.mlp_wide_in_forward(x, _packed_w1(layer1), b1, _packed(layer2, False, False), b2, w3, b3,
-                                              save=need_grad)
+        if w3.shape[0] > hip.MLP_MAX_OUT:  # the wide-head family (mlp_wide_out_kernels.hip): the head on the matrix cores
+            # (W3 is packed per call: two heads arrive concatenated, a fresh tensor every time)
+            out, h1, h2 = hip.mlp_wide_out_forward(x, _packed_w1(layer1, "out"), b1, _packed(layer2, False, False), b2,
+                                                   hip.mlp_wide_out_pack_w3(w3), b3, save=need_grad)
+        else:
+            out, h1, h2 = hip.mlp_wide_in_forward(x, _packed_w1(layer1), b1, _packed(layer2, False, False), b2, w3, b3,
+                                                  save=need_grad)
         if need_grad:
             ctx.layer2 = layer2
             # (w1 and w2 are saved although the kernels read packed copies: autograd's version check then refuses a
@@ -848,27 +860,42 @@ class _WideInputTower(torch.autograd.Function):
         w2t = _packed(ctx.layer2, True, False)
         dz1 = torch.empty(min(m, segment), hidden, dtype=torch.float32, device=x.device)
         dz2 = torch.empty_like(dz1)
-        partials = torch.empty(hip.load().rl8_mlp_wide_in_max_rows(), 2 * hidden + n_out * hidden + n_out,
+        wide_head = n_out > hip.MLP_MAX_OUT  # (the family of the forward: its partial rows carry no dW3)
+        partials = torch.empty(hip.load().rl8_mlp_wide_in_max_rows(),
+                               2 * hidden + n_out if wide_head else 2 * hidden + n_out * hidden + n_out,
                                dtype=torch.float32, device=x.device)
         dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+        w3t, dw3 = (hip.mlp_wide_out_pack_w3(w3, transposed=True), torch.empty_like(w3)) if wide_head else (None, None)
         small = None
         for at in range(0, m, segment):
             rows = slice(at, min(at + segment, m))
             z1, z2 = dz1[: rows.stop - at], dz2[: rows.stop - at]
-            written = hip.mlp_wide_in_backward(h1[rows], h2[rows], dout[rows], w2t, w3, z1, z2, partials)
+            if wide_head:
+                written = hip.mlp_wide_out_backward(h1[rows], h2[rows], dout[rows], w2t, w3t, z1, z2, partials)
+            else:
+                written = hip.mlp_wide_in_backward(h1[rows], h2[rows], dout[rows], w2t, w3, z1, z2, partials)
             part = partials[:written].sum(0)
             small = part if small is None else small + part
-            hip.mlp_wide_in_wgrad(z1, x[rows], dw1, accumulate=at > 0)
+            if wide_head:
+                hip.mlp_wide_out_wgrad(z1, x[rows], dw1, accumulate=at > 0)
+                hip.mlp_wide_out_wgrad(h2[rows], dout[rows], dw3, accumulate=at > 0, transpose=True)
+            else:
+                hip.mlp_wide_in_wgrad(z1, x[rows], dw1, accumulate=at > 0)
             hip.mlp_wgrad(z2, h1[rows], out=dw2, accumulate=at > 0, planes=planes)
+        if wide_head:
+            db1, db2, db3 = torch.split(small, (hidden, hidden, n_out))
+            return None, dw1, db1, dw2, db2, dw3, db3, None, None, None
         db1, db2, dw3, db3 = torch.split(small, (hidden, hidden, n_out * hidden, n_out))
         return None, dw1, db1, dw2, db2, dw3.view(n_out, hidden), db3, None, None, None
 
 
-def _wide_input_tower_forward(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear], x: torch.Tensor) -> None | torch.Tensor:
-    """The wide-input route, or ``None`` when this call is not its: the switch off, autocast, an ``x`` that is not dense
-    or is empty or asks for its gradient (the family forms none, and must not drop one silently), parameters that are
-    not float32 on the device."""
-    if not wide_input_towers_on() or torch.is_autocast_enabled() or not x.is_contiguous() or x.shape[0] < 1:
+def _wide_input_tower_forward(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear], x: torch.Tensor, *,
+                              switch=wide_input_towers_on) -> None | torch.Tensor:
+    """The wide-input route (``switch``: ``wide_head_towers_on`` for the wide-head family, which runs through the same
+    node), or ``None`` when this call is not its: the switch off, autocast, an ``x`` that is not dense or is empty or
+    asks for its gradient (the family forms none, and must not drop one silently), parameters that are not float32 on
+    the device."""
+    if not switch() or torch.is_autocast_enabled() or not x.is_contiguous() or x.shape[0] < 1:
         return None
     if x.shape[1] != l1.in_features or (x.requires_grad and torch.is_grad_enabled()):
         return None
@@ -878,6 +905,50 @@ def _wide_input_tower_forward(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.L
     if not all(p.is_cuda and p.dtype == torch.float32 and p.device == x.device for p in params):
         return None
     return _WideInputTower.apply(x, *params, l1, l2, torch.is_grad_enabled())
+
+
+# --------------------------------------------------------------------------- #
+# Wide-head towers: width 256 with heads of 9 to 128 outputs in all, behind 1 to 128 inputs (mlp_wide_out_kernels.hip),
+# fp32 MFMA throughout, the head and its gradients included.  They run through ``_WideInputTower``, which takes its
+# entries from ``w3.shape[0]``.  Never recorded or replayed for the rollout (no planes: ``_Plan.recordable`` is not
+# even asked, the family has no plan), and no input gradient: a call whose x asks for one is declined.
+# --------------------------------------------------------------------------- #
+def wide_head_towers_on() -> bool:
+    """``RL8_AMD_WIDE_HEAD_TOWERS=0`` (read on every call) sends the wide-head towers to the torch modules: the
+    tests' yardstick.  On by default."""
+    return os.environ.get("RL8_AMD_WIDE_HEAD_TOWERS", "1") != "0"
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_head_supported(d_in: int, n_out: int) -> bool:
+    """Compiled for these widths: fixed by the build, asked once per pair."""
+    return hip.mlp_wide_out_supports(d_in, n_out)
+
+
+def _wide_head_family(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[nn.Linear, nn.Linear]:
+    """(layer1, layer2) if ``trunk`` is the structure ``_family`` calls "wide" -- ``Sequential(MLP(Linear, ReLU,
+    Linear), ReLU)`` at width 256 with biased layers and biased heads (one at least) that read it -- whose heads have
+    MORE than ``hip.MLP_MAX_OUT`` outputs in all, up to what ``hip.mlp_wide_out_supports`` takes, behind any input
+    width it takes; else ``None``.  Asked after ``_family`` and ``_wide_input_family`` have both said ``None``."""
+    if not isinstance(trunk, nn.Sequential) or len(trunk) < 2:
+        return None
+    mlp, act = trunk[0], trunk[1]
+    if not isinstance(mlp, nn.Sequential) or len(mlp) != 3 or not isinstance(act, nn.ReLU):
+        return None
+    l1, a1, l2 = mlp[0], mlp[1], mlp[2]
+    if not (isinstance(l1, nn.Linear) and isinstance(a1, nn.ReLU) and isinstance(l2, nn.Linear)):
+        return None
+    width = hip.MLP_HIDDEN
+    if l1.out_features != width or l2.in_features != width or l2.out_features != width:
+        return None
+    if l1.bias is None or l2.bias is None:
+        return None
+    if not heads or any(h.bias is None or h.in_features != width for h in heads):
+        return None
+    n_out = sum(h.out_features for h in heads)
+    if n_out <= hip.MLP_MAX_OUT or l1.in_features < 1 or not _wide_head_supported(l1.in_features, n_out):
+        return None
+    return l1, l2
 
 
 def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Tensor, *,
@@ -893,14 +964,17 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
 
     The gradient of ``x``: the narrow families (64 / 128, with or without the BatchNorm) form it where ``x`` requires
     one, from the same backward launch.  The 256-wide families -- the default kernels, the rollout replay, the
-    piecewise tables, the wide-input kernels -- form none and DECLINE such a call under grad mode (``None``: the caller
+    piecewise tables, the wide-input and wide-head kernels -- form none and DECLINE such a call under grad mode (``None``: the caller
     runs the modules, which form it); under ``torch.no_grad()`` no gradient can follow and the kernels run."""
     if not ENABLED or not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
         return None
     found = _family(trunk, heads)
     if found is None:  # (only then: the wide-input family begins where _family's input limit ends)
         wide = _wide_input_family(trunk, heads)
-        return None if wide is None else _wide_input_tower_forward(*wide, heads, x)
+        if wide is not None:
+            return _wide_input_tower_forward(*wide, heads, x)
+        wide = _wide_head_family(trunk, heads)  # (more than MLP_MAX_OUT outputs, behind any input width)
+        return None if wide is None else _wide_input_tower_forward(*wide, heads, x, switch=wide_head_towers_on)
     if x.shape[1] != found[1].in_features:
         return None
     family, l1, l2 = found
