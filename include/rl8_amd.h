@@ -56,6 +56,10 @@
  *     towers, hidden width 256 with heads of 9 to 128 outputs in all (RL8_AMD_WIDE_HEAD_TOWERS=0: the torch modules):
  *                rl8_mlp_wide_out_{pack,forward,backward,wgrad}_f32 and their *_supports / *_bytes / *_floats /
  *                *_max_rows queries, with rl8_mlp_pack_w2_f32 and the dW2 entries of the wide-input towers
+ *     towers, hidden width 64 / 128 behind 17 to 128 inputs or with heads of 9 to 128 outputs in all (opt-in:
+ *                RL8_AMD_NARROW_WIDE_TOWERS=1, read on every call by rl8_amd/nn/fused_mlp.py, takes them off the torch
+ *                modules): rl8_mlp_narrow_wide_{forward,backward,reduce}_f32 (their envelope:
+ *                rl8_mlp_narrow_wide_supports; their workspace and LDS: rl8_mlp_narrow_wide_workspace_bytes, _limits)
  *     recurrent  rl8_lstm_pack_split, rl8_lstm_split_state[_bound], rl8_lstm_step_split_f32,
  *                rl8_lstm_rows_backward_pack, rl8_lstm_rows_backward[_heads]_f32, rl8_lstm_wgrad_f16_f32,
  *                rl8_linear_heads_{forward,forward_pair,backward}_f32
@@ -1261,6 +1265,36 @@ int rl8_mlp_wide_out_backward_f32(const float *h1, const float *h2, const float 
 int64_t rl8_mlp_wide_out_workspace_bytes(int c);
 int rl8_mlp_wide_out_wgrad_f32(const float *a, const float *b, int64_t m, int c, float *workspace, float *out,
                                int accumulate, int transpose, void *stream);
+
+/* ---- Narrow towers behind wide inputs and wide heads (OPT-IN: RL8_AMD_NARROW_WIDE_TOWERS=1): the narrow tower with
+ * H = 64 or 128, 1 <= d_in <= 128, 1 <= n_out <= 128 summed over the heads, and d_in > 16 or n_out > 8
+ * (mlp_narrow_wide_kernels.hip): fp32 throughout, every product and every gradient on v_mfma_f32_32x32x2_f32.  The
+ * narrow entries above keep their envelope (16 x 8).  Weights in torch layout, unpacked, as for the narrow entries;
+ * every call packs what it needs into the front of `workspace` itself (one small launch).
+ * rl8_mlp_narrow_wide_supports: 1 inside the envelope, else 0 (host only).
+ * rl8_mlp_narrow_wide_workspace_bytes: the bytes `workspace` must hold (no initialisation) for a forward
+ *   (backward = 0: the packs) or for a backward and its reduce (backward = 1: the packs and one slab per workgroup; the
+ *   workgroups are a function of m, hidden and the classes of d_in and n_out alone); RL8_ECONFIG for another `backward`.
+ * rl8_mlp_narrow_wide_limits (host only): limits[0..1] = the dynamic LDS bytes of one workgroup and the workgroups per
+ *   CU of the forward (backward = 0) or backward (1) kernel compiled for this shape; RL8_ESIZE / RL8_ECONFIG as above.
+ * rl8_mlp_narrow_wide_forward_f32: x [m][d_in] -> out [m][n_out]; nothing else is stored.
+ * rl8_mlp_narrow_wide_backward_f32: recomputes the forward from x (the forward's bits) and writes one partial slab of
+ *   gradients per workgroup; dx [m][d_in] = dz1 W1 as well unless dx is NULL (the slabs hold the same bits either way).
+ *   ReLU'(0) = 0.  rl8_mlp_narrow_wide_reduce_f32 then sums the slabs of the same workspace in a fixed order (fp64)
+ *   into grads_out, laid out as rl8_mlp_narrow_reduce_f32 lays it out: bitwise reproducible, no float atomics.
+ * workspace 16-byte aligned, every other pointer 4-byte; RL8_ENULL / RL8_ESIZE (m < 1, a shape outside the envelope) /
+ * RL8_EALIGN before any launch. */
+int rl8_mlp_narrow_wide_supports(int hidden, int d_in, int n_out);
+int64_t rl8_mlp_narrow_wide_workspace_bytes(int64_t m, int hidden, int d_in, int n_out, int backward);
+int rl8_mlp_narrow_wide_limits(int backward, int hidden, int d_in, int n_out, int *limits /*host, 2*/);
+int rl8_mlp_narrow_wide_forward_f32(const float *x, int64_t m, int d_in, const float *w1, const float *b1,
+                                    const float *w2, const float *b2, const float *w3, const float *b3, int n_out,
+                                    int hidden, float *workspace, float *out, void *stream);
+int rl8_mlp_narrow_wide_backward_f32(const float *x, const float *dout, int64_t m, int d_in, const float *w1,
+                                     const float *b1, const float *w2, const float *b2, const float *w3, int n_out,
+                                     int hidden, float *workspace, float *dx, void *stream);
+int rl8_mlp_narrow_wide_reduce_f32(const float *workspace, int64_t m, int hidden, int d_in, int n_out, float *grads_out,
+                                   void *stream);
 
 /* ---- BatchNorm1d behind the first layer of a narrow tower, folded into that layer (batchnorm_tower_kernels.hip).  In
  * training mode the norm of z1 = x W1^T + b1 over the batch is an affine map of x: with mu = mean_i x_i and the biased

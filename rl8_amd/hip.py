@@ -284,6 +284,12 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_mlp_wide_in_backward_f32": [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(C.c_int), _vp],
     "rl8_mlp_wide_in_workspace_bytes": [_i32],
     "rl8_mlp_wide_in_wgrad_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp],
+    "rl8_mlp_narrow_wide_supports": [_i32, _i32, _i32],
+    "rl8_mlp_narrow_wide_workspace_bytes": [_i64, _i32, _i32, _i32, _i32],
+    "rl8_mlp_narrow_wide_limits": [_i32, _i32, _i32, _i32, C.POINTER(C.c_int)],
+    "rl8_mlp_narrow_wide_forward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "rl8_mlp_narrow_wide_backward_f32": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "rl8_mlp_narrow_wide_reduce_f32": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
     "rl8_mlp_wide_out_supports": [_i32, _i32],
     "rl8_mlp_wide_out_lds_bytes": [_i32, _i32],
     "rl8_mlp_wide_out_pack_floats": [_i32, _i32],
@@ -357,7 +363,7 @@ def load() -> C.CDLL:
                             "rl8_mlp_wide_out_lds_bytes", "rl8_mlp_wide_out_workspace_bytes",
                             "rl8_lstm_wide_in_lds_bytes", "rl8_lstm_wide_in_workspace_bytes",
                             "rl8_lstm_stack256_lds_bytes", "rl8_lstm_stack256_pack_floats",
-                            "rl8_lstm_stack256_workspace_bytes")
+                            "rl8_lstm_stack256_workspace_bytes", "rl8_mlp_narrow_wide_workspace_bytes")
                 else C.c_int
             )
         built = int(lib.rl8_abi_version(None, 0))
@@ -2057,6 +2063,82 @@ def mlp_narrow_backward(x: torch.Tensor, dout: torch.Tensor, w1: torch.Tensor, b
     with _timed("mlp_narrow_reduce", m):
         _check(lib.rl8_mlp_narrow_reduce_f32(_ptr(ws), m, hidden, d_in, n_out, _ptr(grads), _stream()),
                "rl8_mlp_narrow_reduce_f32")
+    parts = torch.split(grads, sizes)
+    shapes = ((hidden, d_in), (hidden,), (hidden, hidden), (hidden,), (n_out, hidden), (n_out,))
+    got = {k: p.view(s) for k, p, s in zip(("w1", "b1", "w2", "b2", "w3", "b3"), parts, shapes)}
+    if dx is not None:
+        got["x"] = dx
+    return got
+
+
+# --------------------------------------------------------------------------- #
+# Narrow towers behind wide inputs and wide heads: hidden width 64 or 128, 1 to 128 inputs, 1 to 128 outputs, more
+# than 16 inputs or more than 8 outputs (mlp_narrow_wide_kernels.hip).
+# --------------------------------------------------------------------------- #
+def mlp_narrow_wide_supports(hidden: int, d_in: int, n_out: int) -> bool:
+    return bool(load().rl8_mlp_narrow_wide_supports(int(hidden), int(d_in), int(n_out)))
+
+
+def _narrow_wide_params(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                        w3: torch.Tensor, b3: None | torch.Tensor) -> tuple[int, int, int, int]:
+    """(m, d_in, hidden, n_out) after the dtype / contiguity / shape checks of the narrow-wide entries."""
+    _dense(x, torch.float32, "x")
+    if x.ndim != 2:
+        raise ValueError("x must be [M, d_in]")
+    m, d_in = x.shape
+    hidden, n_out = w1.shape[0], w3.shape[0]
+    shapes = (("w1", w1, (hidden, d_in)), ("b1", b1, (hidden,)), ("w2", w2, (hidden, hidden)), ("b2", b2, (hidden,)),
+              ("w3", w3, (n_out, hidden)), ("b3", b3, (n_out,)))
+    for name, t, shape in shapes:
+        if t is not None:
+            _shaped(t, shape, name)
+    if m < 1 or not mlp_narrow_wide_supports(hidden, d_in, n_out):
+        raise ValueError(f"no narrow-wide tower kernel for m={m}, hidden={hidden}, d_in={d_in}, n_out={n_out}")
+    return m, d_in, hidden, n_out
+
+
+def _narrow_wide_workspace(m: int, hidden: int, d_in: int, n_out: int, backward: bool, device) -> torch.Tensor:
+    nbytes = int(load().rl8_mlp_narrow_wide_workspace_bytes(m, hidden, d_in, n_out, int(backward)))
+    if nbytes < 0:
+        _check(nbytes, "rl8_mlp_narrow_wide_workspace_bytes")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def mlp_narrow_wide_forward(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                            w3: torch.Tensor, b3: torch.Tensor) -> torch.Tensor:
+    """out [M, n_out] = relu(relu(x w1^T + b1) w2^T + b2) w3^T + b3 for hidden width 64 or 128 behind up to 128 inputs
+    and with up to 128 outputs, every product on fp32 MFMA (nothing saved)."""
+    x, w1, b1, w2, b2, w3, b3 = (t.detach() for t in (x, w1, b1, w2, b2, w3, b3))
+    m, d_in, hidden, n_out = _narrow_wide_params(x, w1, b1, w2, b2, w3, b3)
+    ws = _narrow_wide_workspace(m, hidden, d_in, n_out, False, x.device)
+    out = torch.empty(m, n_out, dtype=torch.float32, device=x.device)
+    with _timed("mlp_narrow_wide_forward", m):
+        _check(load().rl8_mlp_narrow_wide_forward_f32(_ptr(x), m, d_in, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(w3),
+                                                      _ptr(b3), n_out, hidden, _ptr(ws), _ptr(out), _stream()),
+               "rl8_mlp_narrow_wide_forward_f32")
+    return out
+
+
+def mlp_narrow_wide_backward(x: torch.Tensor, dout: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
+                             b2: torch.Tensor, w3: torch.Tensor, *, want_dx: bool = False) -> dict[str, torch.Tensor]:
+    """The dict :func:`mlp_narrow_backward` returns, for the narrow-wide envelope: the forward recomputed from x, every
+    gradient on fp32 MFMA, partial slabs per workgroup summed in a fixed order (deterministic).  ``want_dx``: "x"
+    ([M, d_in]) too, from the same launch; the parameter gradients hold the same bits either way."""
+    x, dout, w1, b1, w2, b2, w3 = (t.detach() for t in (x, dout, w1, b1, w2, b2, w3))
+    m, d_in, hidden, n_out = _narrow_wide_params(x, w1, b1, w2, b2, w3, None)
+    _shaped(dout, (m, n_out), "dout")
+    lib = load()
+    ws = _narrow_wide_workspace(m, hidden, d_in, n_out, True, x.device)
+    sizes = (hidden * d_in, hidden, hidden * hidden, hidden, n_out * hidden, n_out)
+    grads = torch.empty(sum(sizes), dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x) if want_dx else None
+    with _timed("mlp_narrow_wide_backward_dx" if want_dx else "mlp_narrow_wide_backward", m):
+        _check(lib.rl8_mlp_narrow_wide_backward_f32(_ptr(x), _ptr(dout), m, d_in, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
+                                                    _ptr(w3), n_out, hidden, _ptr(ws), _ptr(dx) if want_dx else None,
+                                                    _stream()), "rl8_mlp_narrow_wide_backward_f32")
+    with _timed("mlp_narrow_wide_reduce", m):
+        _check(lib.rl8_mlp_narrow_wide_reduce_f32(_ptr(ws), m, hidden, d_in, n_out, _ptr(grads), _stream()),
+               "rl8_mlp_narrow_wide_reduce_f32")
     parts = torch.split(grads, sizes)
     shapes = ((hidden, d_in), (hidden,), (hidden, hidden), (hidden,), (n_out, hidden), (n_out,))
     got = {k: p.view(s) for k, p, s in zip(("w1", "b1", "w2", "b2", "w3", "b3"), parts, shapes)}

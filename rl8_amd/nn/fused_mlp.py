@@ -581,13 +581,18 @@ class _NarrowTower(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, w3, b3):  # type: ignore[override]
         ctx.save_for_backward(x, w1, b1, w2, b2, w3, b3)
+        # (more than MLP_MAX_IN inputs or MLP_MAX_OUT outputs: the narrow-wide family, mlp_narrow_wide_kernels.hip)
+        if w1.shape[1] > hip.MLP_MAX_IN or w3.shape[0] > hip.MLP_MAX_OUT:
+            return hip.mlp_narrow_wide_forward(x, w1, b1, w2, b2, w3, b3)
         return hip.mlp_narrow_forward(x, w1, b1, w2, b2, w3, b3)
 
     @staticmethod
     def backward(ctx, dout):  # type: ignore[override]
         x, w1, b1, w2, b2, w3, _ = ctx.saved_tensors
+        wide = w1.shape[1] > hip.MLP_MAX_IN or w3.shape[0] > hip.MLP_MAX_OUT  # (the family of the forward)
+        backward = hip.mlp_narrow_wide_backward if wide else hip.mlp_narrow_backward
         # (an input that asks for its gradient -- a tower behind a learned encoder -- takes the entry that forms dx)
-        g = hip.mlp_narrow_backward(x, dout.contiguous().float(), w1, b1, w2, b2, w3, want_dx=ctx.needs_input_grad[0])
+        g = backward(x, dout.contiguous().float(), w1, b1, w2, b2, w3, want_dx=ctx.needs_input_grad[0])
         return g.get("x"), g["w1"], g["b1"], g["w2"], g["b2"], g["w3"], g["b3"]
 
 
@@ -951,6 +956,67 @@ def _wide_head_family(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tu
     return l1, l2
 
 
+# --------------------------------------------------------------------------- #
+# Narrow-wide towers: width 64 / 128 behind 1 to 128 inputs with heads of 1 to 128 outputs in all, more than
+# MLP_MAX_IN inputs or more than MLP_MAX_OUT outputs (mlp_narrow_wide_kernels.hip), fp32 MFMA throughout.  They run
+# through ``_NarrowTower``, which takes its entries from the shapes it is handed, and form dL/dx where x asks for it.
+# Opt-in until the tests that pin these towers to the torch modules flip with the default.
+# --------------------------------------------------------------------------- #
+def narrow_wide_towers_on() -> bool:
+    """``RL8_AMD_NARROW_WIDE_TOWERS=1`` (read on every call) takes the narrow-wide towers off the torch modules.
+    Off by default, and for any other value."""
+    return os.environ.get("RL8_AMD_NARROW_WIDE_TOWERS", "0") == "1"
+
+
+@functools.lru_cache(maxsize=None)
+def _narrow_wide_supported(hidden: int, d_in: int, n_out: int) -> bool:
+    """Compiled for these widths: fixed by the build, asked once per triple."""
+    return hip.mlp_narrow_wide_supports(hidden, d_in, n_out)
+
+
+def _narrow_wide_family(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[nn.Linear, nn.Linear]:
+    """(layer1, layer2) if ``trunk`` is the structure ``_family`` calls "narrow" -- ``Sequential(MLP(Linear, ReLU,
+    Linear), ReLU)`` at a width in ``hip.MLP_NARROW_HIDDEN`` with biased layers and biased heads (one at least) that
+    read it -- whose first layer reads MORE than ``hip.MLP_MAX_IN`` floats or whose heads have MORE than
+    ``hip.MLP_MAX_OUT`` outputs in all, up to what ``hip.mlp_narrow_wide_supports`` takes; else ``None``.  Asked after
+    ``_family``, ``_wide_input_family`` and ``_wide_head_family`` have all said ``None``."""
+    if not isinstance(trunk, nn.Sequential) or len(trunk) < 2:
+        return None
+    mlp, act = trunk[0], trunk[1]
+    if not isinstance(mlp, nn.Sequential) or len(mlp) != 3 or not isinstance(act, nn.ReLU):
+        return None
+    l1, a1, l2 = mlp[0], mlp[1], mlp[2]
+    if not (isinstance(l1, nn.Linear) and isinstance(a1, nn.ReLU) and isinstance(l2, nn.Linear)):
+        return None
+    width = l1.out_features
+    if width not in hip.MLP_NARROW_HIDDEN or l2.in_features != width or l2.out_features != width:
+        return None
+    if l1.bias is None or l2.bias is None:
+        return None
+    if not heads or any(h.bias is None or h.in_features != width for h in heads):
+        return None
+    d_in, n_out = l1.in_features, sum(h.out_features for h in heads)
+    if d_in <= hip.MLP_MAX_IN and n_out <= hip.MLP_MAX_OUT:
+        return None
+    if d_in < 1 or n_out < 1 or not _narrow_wide_supported(width, d_in, n_out):
+        return None
+    return l1, l2
+
+
+def _narrow_wide_tower_forward(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear],
+                               x: torch.Tensor) -> None | torch.Tensor:
+    """The narrow-wide route, or ``None`` when this call is not its: autocast, an ``x`` that is not dense or is empty
+    or of another width, parameters that are not float32 on the device."""
+    if torch.is_autocast_enabled() or not x.is_contiguous() or x.shape[0] < 1 or x.shape[1] != l1.in_features:
+        return None
+    w3 = heads[0].weight if len(heads) == 1 else torch.cat([h.weight for h in heads], 0)
+    b3 = heads[0].bias if len(heads) == 1 else torch.cat([h.bias for h in heads], 0)
+    params = (l1.weight, l1.bias, l2.weight, l2.bias, w3, b3)
+    if not all(p.is_cuda and p.dtype == torch.float32 and p.device == x.device for p in params):
+        return None
+    return _NarrowTower.apply(x, *params)
+
+
 def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Tensor, *,
                   pair_gradients: None | bool = None) -> None | torch.Tensor:
     """``cat([head(trunk(x)) for head in heads], -1)`` through the fused kernels,
@@ -962,7 +1028,11 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
     ``False`` -- h2 is stored; ``None`` -- whatever this tower's previous backward found (a tower used outside
     ``Algorithm``). Checked on the device in the backward either way.
 
-    The gradient of ``x``: the narrow families (64 / 128, with or without the BatchNorm) form it where ``x`` requires
+    Towers of width 64 / 128 behind more than ``hip.MLP_MAX_IN`` inputs or with more than ``hip.MLP_MAX_OUT`` outputs
+    in all (up to 128 of each) run the narrow-wide kernels with ``RL8_AMD_NARROW_WIDE_TOWERS=1``, read on every call,
+    and the modules (``None``) without it.
+
+    The gradient of ``x``: the narrow families (64 / 128, with or without the BatchNorm, narrow-wide too) form it where ``x`` requires
     one, from the same backward launch.  The 256-wide families -- the default kernels, the rollout replay, the
     piecewise tables, the wide-input and wide-head kernels -- form none and DECLINE such a call under grad mode (``None``: the caller
     runs the modules, which form it); under ``torch.no_grad()`` no gradient can follow and the kernels run."""
@@ -974,7 +1044,12 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
         if wide is not None:
             return _wide_input_tower_forward(*wide, heads, x)
         wide = _wide_head_family(trunk, heads)  # (more than MLP_MAX_OUT outputs, behind any input width)
-        return None if wide is None else _wide_input_tower_forward(*wide, heads, x, switch=wide_head_towers_on)
+        if wide is not None:
+            return _wide_input_tower_forward(*wide, heads, x, switch=wide_head_towers_on)
+        if not narrow_wide_towers_on():  # (opt-in: nothing else is done for it while it is off)
+            return None
+        wide = _narrow_wide_family(trunk, heads)  # (width 64 / 128 beyond the narrow kernels' 16 x 8)
+        return None if wide is None else _narrow_wide_tower_forward(*wide, heads, x)
     if x.shape[1] != found[1].in_features:
         return None
     family, l1, l2 = found
