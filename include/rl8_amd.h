@@ -71,6 +71,8 @@
  *                rl8_lstm_narrow_input_grad_f32 (dL/dx of layer 0, for models with an encoder in front of the LSTM),
  *                rl8_lstm_stack_* (layers 1..), rl8_linear_heads_narrow_{forward,forward_pair,backward}_f32,
  *                rl8_rollout_step_dummy_heads_narrow_f32 (the lean rollout's last launch of a timestep)
+ *     recurrent, hidden width 64 / 128 behind 17 to 128 input floats (opt-in, RL8_AMD_NARROW_WIDE_INPUT_LSTM=1):
+ *                rl8_lstm_narrow_wide_in_{forward,backward,backward_heads,reduce,input_grad}_f32
  *   PRODUCT, fallback (shapes outside the plane kernels' envelope -- d_in > 16, n_out > 8, hidden != 256 go to eager --
  *   or a switch: RL8_AMD_TOWER_GEMM=f32, RL8_WGRAD_PLANES=bf16, the LSTM switches below), and THE YARDSTICK the parity
  *   tests hold the plane kernels against beside fp64:
@@ -1412,6 +1414,49 @@ int rl8_lstm_stack_backward_f32(const float *x, int64_t b, int l, const float *h
                                 const float *w_hh, int hidden, const float *hs, const float *gates, const float *cs,
                                 const float *dhs, float *workspace, float *dx, void *stream);
 int rl8_lstm_stack_reduce_f32(const float *workspace, int64_t b, int l, int hidden, float *grads_out, void *stream);
+
+/* ---- Narrow LSTMs behind a wide input: one layer, biased, batch_first, fp32, H = 64 or 128 and 17 <= d_in <= 128
+ * input floats, any value in the range (lstm_narrow_wide_in_kernels.hip; the recurrent forward and the backward through
+ * time are those of the narrow and stacked entries).  Weights in torch layout, unpacked: w_ih [4H][d_in], w_hh [4H][H],
+ * b_ih / b_hh [4H], gate order i, f, g, o.  d_in is a run-time argument; nothing is compiled per width.
+ * rl8_lstm_narrow_wide_in_supports: 1 for hidden 64 / 128 and 17 <= d_in <= 128, else 0 (d_in <= 16: rl8_lstm_narrow_*).
+ * rl8_lstm_narrow_wide_in_forward_f32: the input projection of all b l row-steps, zin[n][4][H] = b_ih + b_hh + x[n] x
+ *   w_ih^T, into zin ([b][l][4][H] floats of scratch, 16-byte aligned, not needed after the call), then the recurrent
+ *   forward: x [b][l][d_in], h0 / c0 [b][H] -> hs [b][l][H], hn / cn [b][H].  save_gates ([b][l][4][H],
+ *   post-activation) and save_c ([b][l][H]) both NULL: inference; both set: training.  hs, hn and cn are bitwise the
+ *   same in both modes.
+ * rl8_lstm_narrow_wide_in_backward_f32: backward through time from dhs [b][l][H] and what the training forward saved,
+ *   then two weight-gradient launches (columns [x | 1]: dW_ih and db; columns [h_{t-1}]: dW_hh).  `workspace`
+ *   (rl8_lstm_narrow_wide_in_workspace_bytes(b, l, hidden, d_in) bytes = 4 (b l 4H + chunks 4H (H + d_in + 1)), chunks
+ *   = min(b, 256 at H = 64, 128 at H = 128) rounded to whole sequences per chunk; no initialisation) holds the gate
+ *   gradients dz [b][l][4][H] at its front and one partial slab per sequence chunk behind them.
+ * rl8_lstm_narrow_wide_in_backward_heads_f32: the same with dL/dh[b][t][u] = sum_q heads_dout[b][t][q] heads_w[q][u],
+ *   q < 4, formed inside the backward through time (heads_dout [b][l][4], 16-byte aligned, and heads_w [4][H], both
+ *   zero-padded beyond the heads' outputs), as rl8_lstm_narrow_backward_heads_f32 does.
+ * rl8_lstm_narrow_wide_in_reduce_f32: sums the slabs in chunk order (fp64) into grads_out = [dW_ih (4H d_in) | dW_hh
+ *   (4H H) | db (4H)] floats, db being the gradient of b_ih and of b_hh alike.
+ * rl8_lstm_narrow_wide_in_input_grad_f32: dx [b][l][d_in] = dz x w_ih from the dz either backward entry left at the
+ *   front of `workspace` (same b, l, hidden, d_in; before or after the reduce); exactly b l d_in floats are written.
+ * Every product is fp32 MFMA in a fixed k order and every grid a function of (b, l): all results are bitwise
+ * reproducible.  No gradient for h0 or c0; c_n is not differentiable.  Pointers 4-byte aligned, zin and workspace
+ * 16-byte aligned; b >= 1, 1 <= l < 2^31 / (256 H); RL8_ESIZE outside the envelope. */
+int rl8_lstm_narrow_wide_in_supports(int hidden, int d_in);
+int64_t rl8_lstm_narrow_wide_in_workspace_bytes(int64_t b, int l, int hidden, int d_in);
+int rl8_lstm_narrow_wide_in_forward_f32(const float *x, int64_t b, int l, int d_in, const float *h0, const float *c0,
+                                        const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                                        int hidden, float *zin, float *hs, float *hn, float *cn, float *save_gates,
+                                        float *save_c, void *stream);
+int rl8_lstm_narrow_wide_in_backward_f32(const float *x, int64_t b, int l, int d_in, const float *h0, const float *c0,
+                                         const float *w_hh, int hidden, const float *hs, const float *gates,
+                                         const float *cs, const float *dhs, float *workspace, void *stream);
+int rl8_lstm_narrow_wide_in_backward_heads_f32(const float *x, int64_t b, int l, int d_in, const float *h0,
+                                               const float *c0, const float *w_hh, int hidden, const float *hs,
+                                               const float *gates, const float *cs, const float *heads_dout,
+                                               const float *heads_w, float *workspace, void *stream);
+int rl8_lstm_narrow_wide_in_reduce_f32(const float *workspace, int64_t b, int l, int hidden, int d_in, float *grads_out,
+                                       void *stream);
+int rl8_lstm_narrow_wide_in_input_grad_f32(const float *workspace, int64_t b, int l, int d_in, const float *w_ih,
+                                           int hidden, float *dx, void *stream);
 
 /* ---- OPT-IN: towers of a SCALAR observation as exact piecewise-linear tables (round 4 prototype; VERDICT r3 item 10,
  * DESIGN.md section 9).  Special to d_in = 1 -- the dummy envs of BASELINE configs 2 and 4 -- and never a replacement

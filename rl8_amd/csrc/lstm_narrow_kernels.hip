@@ -37,6 +37,7 @@
 // LDS: forward [R][H + KIN + 4] (R = 32 / 16 rows at H = 64 / 128: 9-11 KiB), backward [32][4H + 4] (33 / 66 KiB),
 // weight gradient 64 rows of dz (64 columns) and of [h | x | 1] (<= 61 KiB).
 #include "lstm_gates.hip.h"
+#include "lstm_narrow_shared.hip.h"
 #include "mfma_tile.hip.h"
 
 namespace rl8 {
@@ -970,6 +971,51 @@ RL8_API int rl8_lstm_narrow_supports(int hidden, int d_in) {
 static bool lstm_narrow_sizes_ok(int64_t b, int l, int hidden) {
   return b >= 1 && l >= 1 && b * (int64_t)l < ((int64_t)1 << 40) && (int64_t)64 * l * 4 * hidden * 4 < ((int64_t)1 << 31);
 }
+
+// ---- lstm_narrow_shared.hip.h: the launchers lstm_narrow_wide_in_kernels.hip shares with this file (host code only).
+namespace rl8 {
+namespace lstm_narrow {
+
+bool shared_sizes_ok(int64_t b, int l, int hidden) { return lstm_narrow_sizes_ok(b, l, hidden); }
+
+void shared_chunks(int hidden, int64_t b, int64_t *per, int *count) {
+  if (hidden == 64) chunks_for<64>(b, per, count);
+  else chunks_for<128>(b, per, count);
+}
+
+template <int H>
+static int launch_recurrent_forward(hipStream_t s, const float *zin, int64_t b, int l, const float *h0, const float *c0,
+                                    const float *w_hh, float *hs, float *hn, float *cn, float *save_gates,
+                                    float *save_c) {
+  const int grid = tile_grid<H>(b, Geo<H>::R);
+  if (save_gates)
+    lstm_narrow_stack_forward_kernel<H, true><<<grid, Geo<H>::kThreads, 0, s>>>(zin, b, l, h0, c0, w_hh, hs, hn, cn,
+                                                                                save_gates, save_c);
+  else
+    lstm_narrow_stack_forward_kernel<H, false><<<grid, Geo<H>::kThreads, 0, s>>>(zin, b, l, h0, c0, w_hh, hs, hn, cn,
+                                                                                 save_gates, save_c);
+  return launch_status();
+}
+
+int shared_recurrent_forward(hipStream_t s, int hidden, const float *zin, int64_t b, int l, const float *h0,
+                             const float *c0, const float *w_hh, float *hs, float *hn, float *cn, float *save_gates,
+                             float *save_c) {
+  return hidden == 64 ? launch_recurrent_forward<64>(s, zin, b, l, h0, c0, w_hh, hs, hn, cn, save_gates, save_c)
+                      : launch_recurrent_forward<128>(s, zin, b, l, h0, c0, w_hh, hs, hn, cn, save_gates, save_c);
+}
+
+int shared_backward(hipStream_t s, int hidden, int64_t b, int l, const float *c0, const float *w_hh,
+                    const float *gates, const float *cs, const float *dhs, const float *heads_dout,
+                    const float *heads_w, float *dz) {
+  if (heads_dout)
+    return hidden == 64 ? launch_backward_heads<64>(s, b, l, c0, w_hh, gates, cs, heads_dout, heads_w, dz)
+                        : launch_backward_heads<128>(s, b, l, c0, w_hh, gates, cs, heads_dout, heads_w, dz);
+  return hidden == 64 ? launch_backward<64>(s, b, l, c0, w_hh, gates, cs, dhs, dz)
+                      : launch_backward<128>(s, b, l, c0, w_hh, gates, cs, dhs, dz);
+}
+
+}  // namespace lstm_narrow
+}  // namespace rl8
 
 RL8_API int64_t rl8_lstm_narrow_workspace_bytes(int64_t b, int l, int hidden, int d_in) {
   if (!lstm_narrow_sizes_ok(b, l, hidden) || !rl8_lstm_narrow_supports(hidden, d_in)) return RL8_ESIZE;

@@ -322,6 +322,15 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_lstm_stack_forward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_lstm_stack_backward_f32": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_lstm_stack_reduce_f32": [_vp, _i64, _i32, _i32, _vp, _vp],
+    "rl8_lstm_narrow_wide_in_supports": [_i32, _i32],
+    "rl8_lstm_narrow_wide_in_workspace_bytes": [_i64, _i32, _i32, _i32],
+    "rl8_lstm_narrow_wide_in_forward_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp],
+    "rl8_lstm_narrow_wide_in_backward_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rl8_lstm_narrow_wide_in_backward_heads_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp],
+    "rl8_lstm_narrow_wide_in_reduce_f32": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "rl8_lstm_narrow_wide_in_input_grad_f32": [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp],
 }
 
 
@@ -363,7 +372,8 @@ def load() -> C.CDLL:
                             "rl8_mlp_wide_out_lds_bytes", "rl8_mlp_wide_out_workspace_bytes",
                             "rl8_lstm_wide_in_lds_bytes", "rl8_lstm_wide_in_workspace_bytes",
                             "rl8_lstm_stack256_lds_bytes", "rl8_lstm_stack256_pack_floats",
-                            "rl8_lstm_stack256_workspace_bytes", "rl8_mlp_narrow_wide_workspace_bytes")
+                            "rl8_lstm_stack256_workspace_bytes", "rl8_mlp_narrow_wide_workspace_bytes",
+                            "rl8_lstm_narrow_wide_in_workspace_bytes")
                 else C.c_int
             )
         built = int(lib.rl8_abi_version(None, 0))
@@ -2729,6 +2739,8 @@ def lstm_stack256_backward(below: torch.Tensor, h0: torch.Tensor, c0: torch.Tens
 # Narrow LSTMs: one layer (or layer 0 of a stack), hidden width 64 or 128, d_in <= 16 (lstm_narrow_kernels.hip).
 # --------------------------------------------------------------------------- #
 LSTM_NARROW_HIDDEN = (64, 128)
+#: Widest input of the rl8_lstm_narrow_* entries; 17 to 128 floats run rl8_lstm_narrow_wide_in_* (below).
+LSTM_NARROW_MAX_IN = 16
 
 
 def lstm_narrow_supports(hidden: int, d_in: int) -> bool:
@@ -2737,10 +2749,10 @@ def lstm_narrow_supports(hidden: int, d_in: int) -> bool:
 
 def _lstm_layer_params(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: None | torch.Tensor, w_hh: torch.Tensor,
                        b_ih: None | torch.Tensor, b_hh: None | torch.Tensor, *,
-                       upper: bool = False) -> tuple[int, int, int, int]:
+                       upper: bool = False, wide: bool = False) -> tuple[int, int, int, int]:
     """(b, l, d_in, hidden) after the dtype / contiguity / shape checks of the narrow LSTM entries (``x`` [B, L, d_in],
-    H from ``w_hh``) or, with ``upper``, of the stacked ones (``x`` [B, L, H], the lower layer's hs: d_in = H). A
-    parameter the entry does not read is None."""
+    H from ``w_hh``; with ``wide`` those behind 17 to 128 input floats) or, with ``upper``, of the stacked ones (``x``
+    [B, L, H], the lower layer's hs: d_in = H). A parameter the entry does not read is None."""
     _dense(x, torch.float32, "x")
     if x.ndim != 3:
         raise ValueError("x must be [B, L, H]" if upper else "x must be [B, L, d_in]")
@@ -2751,7 +2763,9 @@ def _lstm_layer_params(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih
     for name, t, shape in shapes:
         if t is not None:
             _shaped(t, shape, name)
-    if b < 1 or l < 1 or not (lstm_stack_supports(hidden) if upper else lstm_narrow_supports(hidden, d_in)):
+    supported = (lstm_stack_supports(hidden) if upper else
+                 lstm_narrow_wide_in_supports(hidden, d_in) if wide else lstm_narrow_supports(hidden, d_in))
+    if b < 1 or l < 1 or not supported:
         raise ValueError(f"no stacked LSTM kernel for b={b}, l={l}, hidden={hidden}" if upper else
                          f"no narrow LSTM kernel for b={b}, l={l}, hidden={hidden}, d_in={d_in}")
     return b, l, d_in, hidden
@@ -2785,15 +2799,25 @@ def lstm_narrow_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_
     forms "dx" [B, L, d_in] = dz x w_ih, the gradient of x, from the gate gradients in the workspace, which are then
     returned as well ("dz" [B, L, 4, H], a view of the workspace). Without it: no gradient for x, nothing more launched
     or allocated."""
+    return _lstm_narrow_backward(False, x, h0, c0, w_hh, hs, gates, cs, dhs, heads, w_ih)
+
+
+def _lstm_narrow_backward(wide: bool, x, h0, c0, w_hh, hs, gates, cs, dhs, heads, w_ih) -> dict[str, torch.Tensor]:
+    """:func:`lstm_narrow_backward` (``wide`` False: the rl8_lstm_narrow_* entries and timer names) and
+    :func:`lstm_narrow_wide_in_backward` (True: rl8_lstm_narrow_wide_in_*): the same arguments, workspace layout,
+    launches in the same order and results."""
     if (heads is None) == (dhs is None):
         raise ValueError("lstm_narrow_backward: either dhs or heads")
+    entry = "rl8_lstm_narrow_wide_in" if wide else "rl8_lstm_narrow"
+    t_backward, t_reduce, t_dx = (("lstm_narrow_wide_in_wgrad", "lstm_narrow_wide_in_reduce", "lstm_narrow_wide_in_dx")
+                                  if wide else ("lstm_narrow_backward", "lstm_narrow_reduce", "lstm_narrow_input_grad"))
     x, h0, c0, w_hh, hs, gates, cs = (t.detach() for t in (x, h0, c0, w_hh, hs, gates, cs))
-    b, l, d_in, hidden = _lstm_layer_params(x, h0, c0, None, w_hh, None, None)
+    b, l, d_in, hidden = _lstm_layer_params(x, h0, c0, None, w_hh, None, None, wide=wide)
     for name, t, shape in (("hs", hs, (b, l, hidden)), ("gates", gates, (b, l, 4, hidden)), ("cs", cs, (b, l, hidden)),
                            *([("dhs", dhs.detach(), (b, l, hidden))] if heads is None else [])):
         _shaped(t, shape, name)
     lib = load()
-    ws = torch.empty(int(lib.rl8_lstm_narrow_workspace_bytes(b, l, hidden, d_in)) // 4, dtype=torch.float32,
+    ws = torch.empty(int(getattr(lib, entry + "_workspace_bytes")(b, l, hidden, d_in)) // 4, dtype=torch.float32,
                      device=x.device)
     sizes = (4 * hidden * d_in, 4 * hidden * hidden, 4 * hidden)
     grads = torch.empty(sum(sizes), dtype=torch.float32, device=x.device)
@@ -2804,29 +2828,66 @@ def lstm_narrow_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_
                 or dout.dtype != torch.float32 or w.dtype != torch.float32:
             raise ValueError(f"heads: float32 dout [B * L, n], w [n, {hidden}], n <= {ROWS_BACKWARD_HEADS}")
         dout4, w4 = _heads_padded(dout, w, n, b * l)
-        with _timed("lstm_narrow_backward", b * l):  # (one name for both forms, as "lstm_rows_backward" is at 256)
-            _check(lib.rl8_lstm_narrow_backward_heads_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_hh), hidden,
-                                                          _ptr(hs), _ptr(gates), _ptr(cs), _ptr(dout4), _ptr(w4),
-                                                          _ptr(ws), _stream()), "rl8_lstm_narrow_backward_heads_f32")
+        with _timed(t_backward, b * l):  # (one name for both forms, as "lstm_rows_backward" is at 256)
+            _check(getattr(lib, entry + "_backward_heads_f32")(
+                _ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_hh), hidden, _ptr(hs), _ptr(gates), _ptr(cs),
+                _ptr(dout4), _ptr(w4), _ptr(ws), _stream()), entry + "_backward_heads_f32")
     else:
-        with _timed("lstm_narrow_backward", b * l):
-            _check(lib.rl8_lstm_narrow_backward_f32(_ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_hh), hidden,
-                                                    _ptr(hs), _ptr(gates), _ptr(cs), _ptr(dhs.detach()), _ptr(ws),
-                                                    _stream()), "rl8_lstm_narrow_backward_f32")
-    with _timed("lstm_narrow_reduce", b * l):
-        _check(lib.rl8_lstm_narrow_reduce_f32(_ptr(ws), b, l, hidden, d_in, _ptr(grads), _stream()),
-               "rl8_lstm_narrow_reduce_f32")
+        with _timed(t_backward, b * l):
+            _check(getattr(lib, entry + "_backward_f32")(
+                _ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_hh), hidden, _ptr(hs), _ptr(gates), _ptr(cs),
+                _ptr(dhs.detach()), _ptr(ws), _stream()), entry + "_backward_f32")
+    with _timed(t_reduce, b * l):
+        _check(getattr(lib, entry + "_reduce_f32")(_ptr(ws), b, l, hidden, d_in, _ptr(grads), _stream()),
+               entry + "_reduce_f32")
     w_ih_grad, w_hh_grad, db = torch.split(grads, sizes)
     out = {"w_ih": w_ih_grad.view(4 * hidden, d_in), "w_hh": w_hh_grad.view(4 * hidden, hidden), "b": db}
     if w_ih is not None:
         w_ih = _shaped(w_ih.detach(), (4 * hidden, d_in), "w_ih")
         dx = torch.empty(b, l, d_in, dtype=torch.float32, device=x.device)
-        with _timed("lstm_narrow_input_grad", b * l):
-            _check(lib.rl8_lstm_narrow_input_grad_f32(_ptr(ws), b, l, d_in, _ptr(w_ih), hidden, _ptr(dx), _stream()),
-                   "rl8_lstm_narrow_input_grad_f32")
+        with _timed(t_dx, b * l):
+            _check(getattr(lib, entry + "_input_grad_f32")(_ptr(ws), b, l, d_in, _ptr(w_ih), hidden, _ptr(dx),
+                                                           _stream()), entry + "_input_grad_f32")
         out["dx"] = dx
         out["dz"] = ws[:b * l * 4 * hidden].view(b, l, 4, hidden)
     return out
+
+
+# --------------------------------------------------------------------------- #
+# Narrow LSTMs behind a wide input: one layer, hidden width 64 or 128, 17 <= d_in <= 128
+# (lstm_narrow_wide_in_kernels.hip: projection, weight gradient, input gradient; the recurrent forward and the backward
+# through time are the narrow family's). Timer names are those of the entry's own kernel.
+# --------------------------------------------------------------------------- #
+def lstm_narrow_wide_in_supports(hidden: int, d_in: int) -> bool:
+    return bool(load().rl8_lstm_narrow_wide_in_supports(int(hidden), int(d_in)))
+
+
+def lstm_narrow_wide_in_forward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_ih: torch.Tensor,
+                                w_hh: torch.Tensor, b_ih: torch.Tensor, b_hh: torch.Tensor, *, save: bool = False,
+                                state_out: None | tuple[torch.Tensor, torch.Tensor] = None):
+    """:func:`lstm_narrow_forward` for x [B, L, d], 17 <= d <= 128: the input projection of all B L row-steps into a
+    [B, L, 4, H] scratch made here (timed, with the recurrent forward behind it, as "lstm_narrow_wide_in_proj"), then
+    the recurrent forward. Returns what its narrow namesake returns."""
+    x, h0, c0, w_ih, w_hh, b_ih, b_hh = (t.detach() for t in (x, h0, c0, w_ih, w_hh, b_ih, b_hh))
+    b, l, d_in, hidden = _lstm_layer_params(x, h0, c0, w_ih, w_hh, b_ih, b_hh, wide=True)
+    zin = torch.empty(b, l, 4, hidden, dtype=torch.float32, device=x.device)
+    hs, hn, cn, gates, cs = _lstm_outputs(b, l, hidden, x.device, save, state_out)
+    with _timed("lstm_narrow_wide_in_proj", b * l):
+        _check(load().rl8_lstm_narrow_wide_in_forward_f32(
+            _ptr(x), b, l, d_in, _ptr(h0), _ptr(c0), _ptr(w_ih), _ptr(w_hh), _ptr(b_ih), _ptr(b_hh), hidden, _ptr(zin),
+            _ptr(hs), _ptr(hn), _ptr(cn), _ptr(gates), _ptr(cs), _stream()), "rl8_lstm_narrow_wide_in_forward_f32")
+    return hs, hn, cn, gates, cs
+
+
+def lstm_narrow_wide_in_backward(x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, w_hh: torch.Tensor,
+                                 hs: torch.Tensor, gates: torch.Tensor, cs: torch.Tensor, dhs: None | torch.Tensor, *,
+                                 heads: None | tuple[torch.Tensor, torch.Tensor] = None,
+                                 w_ih: None | torch.Tensor = None) -> dict[str, torch.Tensor]:
+    """:func:`lstm_narrow_backward` for x [B, L, d], 17 <= d <= 128, from what :func:`lstm_narrow_wide_in_forward`
+    saved: the backward through time and the two weight-gradient launches ("lstm_narrow_wide_in_wgrad"), the reduce
+    ("lstm_narrow_wide_in_reduce") and, with ``w_ih``, "dx" = dz x w_ih ("lstm_narrow_wide_in_dx"). Same arguments,
+    same results, deterministic."""
+    return _lstm_narrow_backward(True, x, h0, c0, w_hh, hs, gates, cs, dhs, heads, w_ih)
 
 
 # --------------------------------------------------------------------------- #

@@ -19,6 +19,11 @@ wide-in"  128 (``hip.lstm_wide_in_supports``)  forward, dW_ih / db), the rows   
 "narrow"  one layer, H = 64 / 128, d_in <= 16  lstm_narrow_kernels.hip (weights   ``lstm_forward``; with
           (``hip.lstm_narrow_supports``)       in torch layout: no plan, no       heads: ``lstm_heads_forward``
                                                packs, no planes)                  (``_NarrowLSTMHeads``)
+"narrow-  one layer, H = 64 / 128, 17 <= d_in  lstm_narrow_wide_in_kernels.hip    the same two entries and
+wide-in"  <= 128 (``hip.lstm_narrow_wide_in_   (input projection, dW_ih / db /    nodes, after ``_family`` and
+          supports``) and ``RL8_AMD_NARROW_    dW_hh, dL/dx), the recurrent       ``_wide_input_family`` have
+          WIDE_INPUT_LSTM=1`` (opt-in):        forward of "stack" and the         said ``None``
+          ``_narrow_wide_input_family``        backward through time of "narrow"
 "stack"   two or more layers of the narrow     layer 0 as "narrow", the layers    ``lstm_stack_forward``
           envelope, ``dropout == 0``           above on lstm_narrow_stack_*
           (``hip.lstm_stack_supports``)
@@ -36,9 +41,9 @@ forms the heads' data gradient itself (``lstm_heads_forward``); the reference's 
 ``nn.LSTM(d_in, 256, batch_first=True)`` (``src/rl8/models/_recurrent.py:201-321``), its example around
 ``nn.LSTM(4, 64)``.
 
-The "narrow" and "stack" families return the gradient of their input ``x`` where it requires one -- a model with
-learned parameters in front of the LSTM, such as ``rl8_amd.envs.LSTMTrader``'s embedding -- from one more launch on
-the gate gradients the backward through time has left (``rl8_lstm_narrow_input_grad_f32``); an ``x`` that is
+The "narrow", "narrow-wide-in" and "stack" families return the gradient of their input ``x`` where it requires one
+-- a model with learned parameters in front of the LSTM, such as ``rl8_amd.envs.LSTMTrader``'s embedding -- from one
+more launch on the gate gradients the backward through time has left (``rl8_lstm_narrow[_wide_in]_input_grad_f32``); an ``x`` that is
 rollout-buffer data costs nothing. The "256", "256-wide-in" and "stack256" families form no input gradient and decline an ``x``
 that requires one under grad mode; no family forms a gradient for the initial states ``h0`` / ``c0``, and every entry point declines
 a call in which one of them requires it (``_declines``). The caller then runs the module, which forms them.
@@ -135,6 +140,48 @@ def _wide_input_family(lstm: nn.LSTM) -> None | str:
 def _wide_input_family_for(lstm: nn.LSTM, x: torch.Tensor) -> None | str:
     """``_wide_input_family(lstm)`` where ``x`` is an input its kernels take, else ``None``."""
     return _wide_input_family(lstm) if _input_ok(lstm, x) else None
+
+
+def narrow_wide_input_lstm_on() -> bool:
+    """``RL8_AMD_NARROW_WIDE_INPUT_LSTM=1`` (read on every call; any other value, or unset, is off) puts width-64 / 128
+    LSTMs behind 17 to 128 input floats on lstm_narrow_wide_in_kernels.hip.  Opt-in: unset, such a module runs as
+    before, on torch, which is also ``tools/narrow_wide_input_lstm_ab.py``'s yardstick."""
+    return os.environ.get("RL8_AMD_NARROW_WIDE_INPUT_LSTM") == "1"
+
+
+@functools.lru_cache(maxsize=None)
+def _narrow_wide_input_supported(hidden: int, d_in: int) -> bool:
+    """The narrow-wide-in kernels take this (hidden, d_in): fixed by the build, asked once per pair."""
+    return hip.lstm_narrow_wide_in_supports(hidden, d_in)
+
+
+def _narrow_wide_input_family(lstm: nn.LSTM) -> None | str:
+    """"narrow-wide-in" for the modules ``_family`` leaves to torch only because ``hip.lstm_narrow_supports`` ends at 16
+    inputs: one layer of width 64 / 128, batch_first, biased, no projection, one direction, behind 17 to 128 input
+    floats (``hip.lstm_narrow_wide_in_supports``), with ``ENABLED`` and the switch ``RL8_AMD_NARROW_WIDE_INPUT_LSTM``
+    as they are now; else ``None``.  Beside ``_family``, not inside it, as ``_wide_input_family`` is: a stack whose
+    layer 0 is this wide and the lean rollout, which both ask ``_family``, stay where they were."""
+    if not (ENABLED and lstm.batch_first and lstm.bias and not lstm.bidirectional and lstm.proj_size == 0):
+        return None
+    if lstm.num_layers != 1 or not _narrow_wide_input_supported(lstm.hidden_size, lstm.input_size):
+        return None
+    return "narrow-wide-in" if narrow_wide_input_lstm_on() else None
+
+
+def _one_layer_family_for(lstm: nn.LSTM, x: torch.Tensor) -> None | str:
+    """What the one-layer entries ask: ``_family``, then ``_wide_input_family``, then ``_narrow_wide_input_family``,
+    where ``x`` is an input the kernels take; else ``None``."""
+    if not _input_ok(lstm, x):
+        return None
+    return _family(lstm) or _wide_input_family(lstm) or _narrow_wide_input_family(lstm)
+
+
+def _narrow_entries(d_in: int):
+    """(forward, backward) of ``hip`` for a narrow node whose ``x`` is ``d_in`` floats wide: the narrow family's up to
+    16, the narrow-wide-in family's beyond (the entry points have let nothing else through)."""
+    if d_in > hip.LSTM_NARROW_MAX_IN:
+        return hip.lstm_narrow_wide_in_forward, hip.lstm_narrow_wide_in_backward
+    return hip.lstm_narrow_forward, hip.lstm_narrow_backward
 
 
 def stack256_lstm_on() -> bool:
@@ -329,14 +376,15 @@ def _input_grad_args(ctx, w_ih: torch.Tensor) -> dict[str, torch.Tensor]:
 
 
 class _NarrowLSTM(torch.autograd.Function):
-    """A hidden-64 / 128 LSTM: the weights are read in torch layout (nothing packed, nothing cached); a training
+    """A hidden-64 / 128 LSTM, on the "narrow" or -- for an ``x`` of more than 16 floats -- the "narrow-wide-in" entries
+    (``_narrow_entries``): the weights are read in torch layout (nothing packed, nothing cached); a training
     pass saves the gates and cell states for the backward through time. Where ``x`` requires a gradient (learned
     parameters in front of the LSTM) the backward adds one launch, dL/dx = dz x W_ih (``_input_grad_args``)."""
 
     @staticmethod
     def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, grad_mode):  # type: ignore[override]
         need_grad = grad_mode and (any(ctx.needs_input_grad[3:7]) or ctx.needs_input_grad[0])
-        hs, _, cn, gates, cs = hip.lstm_narrow_forward(x, h0, c0, w_ih, w_hh, b_ih, b_hh, save=need_grad)
+        hs, _, cn, gates, cs = _narrow_entries(x.shape[2])[0](x, h0, c0, w_ih, w_hh, b_ih, b_hh, save=need_grad)
         ctx.set_materialize_grads(False)
         if need_grad:
             ctx.save_for_backward(x, h0, c0, w_ih, w_hh, hs, gates, cs)
@@ -347,7 +395,7 @@ class _NarrowLSTM(torch.autograd.Function):
     def backward(ctx, dhs, dcn):  # type: ignore[override]
         x, h0, c0, w_ih, w_hh, hs, gates, cs = ctx.saved_tensors
         dhs = torch.zeros_like(hs) if dhs is None else dhs.contiguous().float()
-        g = hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, dhs, **_input_grad_args(ctx, w_ih))
+        g = _narrow_entries(x.shape[2])[1](x, h0, c0, w_hh, hs, gates, cs, dhs, **_input_grad_args(ctx, w_ih))
         return g.get("dx"), None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], None
 
 
@@ -374,7 +422,7 @@ class _NarrowLSTMHeads(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, w_heads, b_heads):  # type: ignore[override]
-        hs, _, cn, gates, cs = hip.lstm_narrow_forward(x, h0, c0, w_ih, w_hh, b_ih, b_hh, save=True)
+        hs, _, cn, gates, cs = _narrow_entries(x.shape[2])[0](x, h0, c0, w_ih, w_hh, b_ih, b_hh, save=True)
         out = hip.linear_heads_narrow_forward(hs.view(-1, hs.shape[2]), w_heads, b_heads)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(x, h0, c0, w_ih, w_hh, hs, gates, cs, w_heads)
@@ -386,8 +434,8 @@ class _NarrowLSTMHeads(torch.autograd.Function):
         x, h0, c0, w_ih, w_hh, hs, gates, cs, w_heads = ctx.saved_tensors
         g, dw, db = _lstm_heads_backward(
             hs, w_heads, dout, dhs, hip.linear_heads_narrow_backward,
-            lambda dhs, heads: hip.lstm_narrow_backward(x, h0, c0, w_hh, hs, gates, cs, dhs, heads=heads,
-                                                        **_input_grad_args(ctx, w_ih)))
+            lambda dhs, heads: _narrow_entries(x.shape[2])[1](x, h0, c0, w_hh, hs, gates, cs, dhs, heads=heads,
+                                                              **_input_grad_args(ctx, w_ih)))
         return g.get("dx"), None, None, g["w_ih"], g["w_hh"], g["b"], g["b"], dw, db
 
 
@@ -546,20 +594,21 @@ def lstm_stack_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: tor
 def lstm_forward(lstm: nn.LSTM, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
     """``lstm(x, (h0[None], c0[None]))`` for ``x`` [B, L, d], ``h0`` / ``c0`` [B, H]
     through the fused kernels: ``(hs [B, L, H], h_n [B, H], c_n [B, H])``, or
-    ``None`` when this LSTM / input is not eligible (H = 256 with d <= 7, or H = 64 /
-    128 with d <= 16). No gradient flows out of ``c_n``; ``h0`` / ``c0`` are rollout-buffer
+    ``None`` when this LSTM / input is not eligible (H = 256 with d <= 7 -- to 128 on the wide-input
+    kernels --, or H = 64 / 128 with d <= 16 -- to 128 with ``RL8_AMD_NARROW_WIDE_INPUT_LSTM=1``).
+    No gradient flows out of ``c_n``; ``h0`` / ``c0`` are rollout-buffer
     data, and a call in which one of them requires a gradient under grad mode is declined
     (``None``). At H = 64 / 128 ``x`` receives its gradient where it requires one (an
     encoder in front of the LSTM: one more launch, dz x W_ih); at H = 256 the entry
     declines such an ``x`` under grad mode."""
-    family = _family_for(lstm, x) or _wide_input_family_for(lstm, x)
-    if family not in ("256", "256-wide-in", "narrow"):  # (a stack has its own entry and state layout: lstm_stack_forward)
+    family = _one_layer_family_for(lstm, x)
+    if family not in ("256", "256-wide-in", "narrow", "narrow-wide-in"):  # (a stack has its own entry and state layout)
         return None
     if _declines(family, x, h0, c0):
         return None
     args = (x.contiguous(), h0.contiguous().float(), c0.contiguous().float(), lstm.weight_ih_l0, lstm.weight_hh_l0,
             lstm.bias_ih_l0, lstm.bias_hh_l0)
-    if family == "narrow":
+    if family in ("narrow", "narrow-wide-in"):
         hs, cn = _NarrowLSTM.apply(*args, torch.is_grad_enabled())
     else:
         plan = _wide_input_plan(x.shape[0]) if family == "256-wide-in" else _plan(lstm.input_size, x.shape[0])
@@ -641,11 +690,11 @@ def lstm_heads_forward(lstm: nn.LSTM, heads: list[nn.Linear], x: torch.Tensor, h
     fuse them): the caller then runs :func:`lstm_forward` / :func:`lstm_stack_forward` and :func:`heads_forward`.
     The gradient of ``x`` is as in :func:`lstm_forward`: formed at H = 64 / 128 where ``x`` requires it; at 256 the
     entry declines such an ``x``, and at every width an ``h0`` or ``c0`` that requires a gradient."""
-    family = (_family_for(lstm, x) or _wide_input_family_for(lstm, x)) if torch.is_grad_enabled() else None
-    if family not in ("256", "256-wide-in", "narrow") or _declines(family, x, h0, c0):
+    family = _one_layer_family_for(lstm, x) if torch.is_grad_enabled() else None
+    if family not in ("256", "256-wide-in", "narrow", "narrow-wide-in") or _declines(family, x, h0, c0):
         return None
     plan = (_plan(lstm.input_size, x.shape[0]) if family == "256" else
-            _wide_input_plan(x.shape[0]) if family == "256-wide-in" else None)  # (the narrow family reads no plan)
+            _wide_input_plan(x.shape[0]) if family == "256-wide-in" else None)  # (the narrow families read no plan)
     if not ((FUSE_HEADS if plan is None else plan.fuse_heads)
             and _heads_eligible(heads, hip.ROWS_BACKWARD_HEADS, lstm.hidden_size)
             and any(p.requires_grad for p in lstm.parameters())):
