@@ -44,6 +44,9 @@
  *                heads of at most 16 floats, TransformerTrader among them; RL8_AMD_ATTENTION_KERNELS=0, read on every
  *                call by rl8_amd/nn/fused_attention.py, puts the core back on nn.MultiheadAttention's math backend)
  *                rl8_attention_f32, rl8_attention_backward_f32 (their envelope: rl8_attention_supports)
+ *                rl8_attention_wide_f32, rl8_attention_wide_backward_f32 (MFMA kernels for sequences of at most 128
+ *                cells and heads of at most 64 floats, their envelope: rl8_attention_wide_supports; the modules reach
+ *                them only with RL8_AMD_WIDE_ATTENTION=1, read on every call, for what the short kernels leave)
  *     feedforward (the LayerNorm -> Linear -> ReLU -> Linear block that ends every SelfAttention / CrossAttention, with
  *                its skip connection, on f32 HIP tensors of at most 32 features and 256 hidden units;
  *                opt-in: RL8_AMD_FEEDFORWARD_KERNELS=1, read on every call by rl8_amd/nn/fused_feedforward.py, takes
@@ -124,7 +127,8 @@ extern "C" {
  * rl8_rollout_stats_plan, rl8_gather_minibatch_plan, rl8_pack_plan).  Added under 107 without a bump (new entries
  * only): rl8_masked_rows_route, rl8_masked_pool_f32, rl8_masked_pool_backward_f32, rl8_masked_log_softmax_f32,
  * rl8_masked_log_softmax_backward_f32, rl8_masked_categorical_sample_f32; rl8_attention_supports, rl8_attention_f32,
- * rl8_attention_backward_f32; rl8_feedforward_supports, rl8_feedforward_limits, rl8_feedforward_workspace_floats,
+ * rl8_attention_backward_f32; rl8_attention_wide_supports, rl8_attention_wide_f32, rl8_attention_wide_backward_f32;
+ * rl8_feedforward_supports, rl8_feedforward_limits, rl8_feedforward_workspace_floats,
  * rl8_feedforward_f32, rl8_feedforward_backward_f32.  Widened under 107 without a bump (no entry added, none changed
  * in signature, and a binding of either age works with a library of either age): rl8_lstm_split_state[_bound] take an
  * h of any finite size -- they scale the call's planes by a power of two from max |h| and leave it in sixteen bytes
@@ -615,6 +619,25 @@ int rl8_attention_backward_f32(const float *q, int64_t q_stride, const float *k,
                                const float *dout, int64_t b, int tq, int tk, int heads, int d, float *dq,
                                int64_t dq_stride, float *dk, float *dv, int64_t dkv_stride, float *delta_workspace,
                                void *stream);
+
+/* The same operation on the matrix cores for longer sequences and wider heads (rl8_amd/csrc/attention_wide_kernels.hip):
+ * the argument lists, the operand contract (strides, 4-byte alignment, key_padding nonzero = PADDED, bias with -inf, a
+ * query without an admissible key), the two backward launches with delta in delta_workspace, and the refusals and
+ * their order are exactly those of rl8_attention_f32 / rl8_attention_backward_f32 above.
+ * One workgroup per (b, head, group of up to four 16-row strips), one wave per strip, the head's other sequence staged
+ *   in LDS once per workgroup (at most 69 KiB); v_mfma_f32_16x16x4_f32 on transposed score tiles whose accumulators
+ *   feed the second product directly.  Every sum inside one wave in a fixed order, no atomics: the same bits on every
+ *   run.  Envelope (rl8_attention_wide_supports, host only: 1 inside, 0 outside, RL8_ESIZE for an argument < 1):
+ *   tq, tk <= 128, d <= 64, any heads and b. */
+int rl8_attention_wide_supports(int tq, int tk, int heads, int d);
+int rl8_attention_wide_f32(const float *q, int64_t q_stride, const float *k, const float *v, int64_t kv_stride,
+                           const uint8_t *key_padding, const float *bias, int64_t b, int tq, int tk, int heads, int d,
+                           float *out, float *lse /*may be NULL*/, void *stream);
+int rl8_attention_wide_backward_f32(const float *q, int64_t q_stride, const float *k, const float *v, int64_t kv_stride,
+                                    const uint8_t *key_padding, const float *bias, const float *out, const float *lse,
+                                    const float *dout, int64_t b, int tq, int tk, int heads, int d, float *dq,
+                                    int64_t dq_stride, float *dk, float *dv, int64_t dkv_stride, float *delta_workspace,
+                                    void *stream);
 
 /* The fused feedforward block of the attention modules (rl8_amd/csrc/feedforward_kernels.hip), per row of x [rows][f]:
  *   n   = LayerNorm_f(x; gamma, beta, eps)      biased variance from the centred values, rstd = 1 / sqrt(var + eps)

@@ -197,6 +197,10 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_attention_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "rl8_attention_backward_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp,
                                    _i64, _vp, _vp, _i64, _vp, _vp],
+    "rl8_attention_wide_supports": [_i32, _i32, _i32, _i32],
+    "rl8_attention_wide_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "rl8_attention_wide_backward_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32,
+                                        _vp, _i64, _vp, _vp, _i64, _vp, _vp],
     "rl8_feedforward_supports": [_i32, _i32],
     "rl8_feedforward_limits": [C.POINTER(C.c_int)],
     "rl8_feedforward_workspace_floats": [_i64, _i32, _i32],
@@ -1415,7 +1419,8 @@ def masked_categorical_sample(x: torch.Tensor, mask: None | torch.Tensor, noise:
 
 
 # --------------------------------------------------------------------------- #
-# Short-sequence attention (rl8_amd/csrc/attention_kernels.hip).
+# Attention: the short-sequence kernels (rl8_amd/csrc/attention_kernels.hip) and, for what they leave, the MFMA kernels
+# for up to 128 cells and heads of up to 64 floats (rl8_amd/csrc/attention_wide_kernels.hip).
 # --------------------------------------------------------------------------- #
 def attention_supports(tq: int, tk: int, heads: int, d: int) -> bool:
     """Whether the attention kernels take ``tq`` queries over ``tk`` keys with ``heads`` heads of ``d`` floats (host
@@ -1423,6 +1428,19 @@ def attention_supports(tq: int, tk: int, heads: int, d: int) -> bool:
     status = int(load().rl8_attention_supports(tq, tk, heads, d))
     _check(min(status, 0), "rl8_attention_supports")
     return status == 1
+
+
+def attention_wide_supports(tq: int, tk: int, heads: int, d: int) -> bool:
+    """The same question of the MFMA attention kernels (host only)."""
+    status = int(load().rl8_attention_wide_supports(tq, tk, heads, d))
+    _check(min(status, 0), "rl8_attention_wide_supports")
+    return status == 1
+
+
+def _attention_entries(tq: int, tk: int, heads: int, d: int) -> tuple[str, str]:
+    """``(infix of the entries' names, prefix of their timer names)``: the short kernels where they take the shape, the
+    wide ones otherwise (which refuse what lies outside both envelopes)."""
+    return ("", "attention") if attention_supports(tq, tk, heads, d) else ("_wide", "attention_wide")
 
 
 def _rows(t: torch.Tensor, shape: tuple, what: str) -> int:
@@ -1466,9 +1484,11 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_padding: No
         _shaped(bias, (tq, tk), "bias")
     out = torch.empty(b, tq, e, dtype=torch.float32, device=q.device)
     lse = torch.empty(b, heads, tq, dtype=torch.float32, device=q.device) if want_lse else None
-    with _timed("attention", b):
-        _check(load().rl8_attention_f32(_ptr(q), q_stride, _ptr(k), _ptr(v), kv_stride, _ptr(key_padding), _ptr(bias), b,
-                                        tq, tk, heads, e // heads, _ptr(out), _ptr(lse), _stream()), "rl8_attention_f32")
+    infix, timer_name = _attention_entries(tq, tk, heads, e // heads)
+    entry = f"rl8_attention{infix}_f32"
+    with _timed(timer_name, b):
+        _check(getattr(load(), entry)(_ptr(q), q_stride, _ptr(k), _ptr(v), kv_stride, _ptr(key_padding), _ptr(bias), b,
+                                      tq, tk, heads, e // heads, _ptr(out), _ptr(lse), _stream()), entry)
     return out, lse
 
 
@@ -1493,11 +1513,12 @@ def attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pa
     _shaped(lse, (b, heads, tq), "lse")
     _shaped(dout, (b, tq, e), "dout")
     delta = torch.empty(b, heads, tq, dtype=torch.float32, device=q.device)
-    with _timed("attention_backward", b):
-        _check(load().rl8_attention_backward_f32(_ptr(q), q_stride, _ptr(k), _ptr(v), kv_stride, _ptr(key_padding),
-                                                 _ptr(bias), _ptr(out), _ptr(lse), _ptr(dout), b, tq, tk, heads,
-                                                 e // heads, _ptr(dq), dq_stride, _ptr(dk), _ptr(dv), dkv_stride,
-                                                 _ptr(delta), _stream()), "rl8_attention_backward_f32")
+    infix, timer_name = _attention_entries(tq, tk, heads, e // heads)
+    entry = f"rl8_attention{infix}_backward_f32"
+    with _timed(f"{timer_name}_backward", b):
+        _check(getattr(load(), entry)(_ptr(q), q_stride, _ptr(k), _ptr(v), kv_stride, _ptr(key_padding), _ptr(bias),
+                                      _ptr(out), _ptr(lse), _ptr(dout), b, tq, tk, heads, e // heads, _ptr(dq), dq_stride,
+                                      _ptr(dk), _ptr(dv), dkv_stride, _ptr(delta), _stream()), entry)
 
 
 # --------------------------------------------------------------------------- #

@@ -5,7 +5,9 @@
 ``F.linear`` for self-attention, two for cross-attention), the kernels on the packed projection in place, the module's
 own out-projection. The module, its parameters and its ``state_dict`` are untouched; an input the kernels do not take
 returns ``None`` and the caller runs the module as before. ``RL8_AMD_ATTENTION_KERNELS=0`` (read on every call) does the
-same for every input.
+same for every input. With ``RL8_AMD_WIDE_ATTENTION=1`` (read on every call; opt-in) the route also takes what the MFMA
+kernels of ``rl8_amd/csrc/attention_wide_kernels.hip`` serve and the short ones do not: up to 128 cells, heads of up to
+64 features. ``hip.attention`` / ``hip.attention_backward`` pick the family from the shape.
 
 :func:`attention_reference` is the torch expression of what the kernels compute, in any dtype on any device: the
 yardstick of the tests.
@@ -121,6 +123,16 @@ def attention_kernels_on() -> bool:
     return os.environ.get("RL8_AMD_ATTENTION_KERNELS", "1") != "0"
 
 
+def wide_attention_on() -> bool:
+    """``RL8_AMD_WIDE_ATTENTION=1`` (read on every call) lets the route take what only the MFMA kernels serve."""
+    return os.environ.get("RL8_AMD_WIDE_ATTENTION") == "1"
+
+
+def _kernels_take(tq: int, tk: int, heads: int, d: int) -> bool:
+    return hip.attention_supports(tq, tk, heads, d) or (wide_attention_on()
+                                                        and hip.attention_wide_supports(tq, tk, heads, d))
+
+
 def _on_device(x: torch.Tensor) -> bool:
     return x.is_cuda
 
@@ -149,7 +161,8 @@ def multihead_attention(mha: nn.MultiheadAttention, q: torch.Tensor, kv: torch.T
     ``None`` when this call is not theirs: anything but float32 HIP ``[B, T, E]`` inputs outside autocast, a module
     with separate projection weights, ``batch_first=False``, ``bias_k`` / ``add_zero_attn``, active dropout, masks of other
     types or shapes than ``key_padding_mask [B, Tk]`` bool / uint8 and ``attention_mask [Tq, Tk]`` bool or float without
-    a gradient, a shape outside ``hip.attention_supports``, or ``RL8_AMD_ATTENTION_KERNELS=0``."""
+    a gradient, a shape outside ``hip.attention_supports`` (and, with ``RL8_AMD_WIDE_ATTENTION=1``, outside
+    ``hip.attention_wide_supports`` too), or ``RL8_AMD_ATTENTION_KERNELS=0``."""
     if not (attention_kernels_on() and _kernel_input(q) and _kernel_input(kv)) or torch.is_autocast_enabled():
         return None
     if (not mha._qkv_same_embed_dim or not mha.batch_first or mha.bias_k is not None or mha.bias_v is not None
@@ -163,7 +176,7 @@ def multihead_attention(mha: nn.MultiheadAttention, q: torch.Tensor, kv: torch.T
                                              and tuple(key_padding_mask.shape) == (b, tk)):
         return None
     taken, bias = _kernel_bias(attention_mask, tq, tk)
-    if not taken or not hip.attention_supports(tq, tk, heads, e // heads):
+    if not taken or not _kernels_take(tq, tk, heads, e // heads):
         return None
     if key_padding_mask is not None:
         key_padding_mask = key_padding_mask.contiguous()
