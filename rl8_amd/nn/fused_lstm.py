@@ -128,8 +128,8 @@ def _wide_input_family(lstm: nn.LSTM) -> None | str:
     """"256-wide-in" for the modules ``_family`` leaves to torch only because ``hip.lstm_supports`` ends at 7 inputs:
     one layer of width 256, batch_first, biased, no projection, one direction, behind 8 to 128 input floats
     (``hip.lstm_wide_in_supports``), with ``ENABLED`` and the switch ``RL8_AMD_WIDE_INPUT_LSTM`` as they are now; else
-    ``None``.  Beside ``_family``, not inside it, as ``fused_mlp._wide_input_family`` is: ``_family``'s answers are
-    what the lean rollout and the narrow routes are built on."""
+    ``None``.  Beside ``_family``, not inside it: ``_family``'s answers are what the lean rollout and the narrow
+    routes are built on."""
     if not (ENABLED and lstm.batch_first and lstm.bias and not lstm.bidirectional and lstm.proj_size == 0):
         return None
     if lstm.hidden_size != hip.LSTM_HIDDEN or lstm.num_layers != 1 or not _wide_input_supported(lstm.input_size):

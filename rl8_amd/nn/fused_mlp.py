@@ -8,33 +8,67 @@ per call) -- instead of ~8 (forward) / ~20 (backward) eager launches whose 256-w
 activations each make an HBM round trip. Parameters stay ordinary ``torch.nn.Linear``
 weights; this module only changes how the tower is evaluated.
 
-Towers of hidden width 64 or 128 (same structure, ``d_in <= 16``, ``n_out <= 8``) run
-their own kernel family (``mlp_narrow_kernels.hip``, ``_NarrowTower``): fp32 MFMA for
-layer 2, nothing saved by the forward, activations recomputed by the one backward
-kernel.  They are never recorded for rollout replay.  An input that asks for its
-gradient (a tower behind a learned encoder) gets it from the same backward launch
+Which kernels a tower gets is decided once per call: ``_classify`` reads the module structure and names the family,
+``_ROUTES`` gives the family's switch and launcher, and ``tower_forward`` returns ``None`` for anything else (other
+widths, activations, other norm layers, non-HIP or non-fp32 inputs, an ``x`` of another width), so the caller runs the
+modules and custom models are unaffected.  The envelopes are disjoint: H is the hidden width, d_in what layer 1 reads,
+n_out the outputs of the heads in all; "16 x 8" is ``hip.MLP_MAX_IN`` x ``hip.MLP_MAX_OUT``.
+
+=============  ====================================  ==============================  =====================================
+family         envelope                              switch (read on every call)     kernels; autograd node
+=============  ====================================  ==============================  =====================================
+"wide"         H = 256, d_in <= 16, n_out <= 8       none (``ENABLED``); the routes  mlp_kernels.hip, mlp_f16_ / _split_
+                                                     inside it are ``_plan``'s       / _rows_kernels.hip; ``_FusedTower``,
+                                                                                     ``_ReplayedTower``
+"wide_in"      H = 256, 17 <= d_in <= 128, n_out     ``RL8_AMD_WIDE_INPUT_TOWERS``,  mlp_wide_in_kernels.hip;
+               <= 8 (``hip.mlp_wide_in_supports``)   on unless 0                     ``_WideInputTower``
+"wide_head"    H = 256, 1 <= d_in <= 128, 9 <=       ``RL8_AMD_WIDE_HEAD_TOWERS``,   mlp_wide_out_kernels.hip;
+               n_out <= 128 (``hip.mlp_wide_out_     on unless 0                     ``_WideInputTower``
+               supports``)
+"narrow"       H = 64 / 128, d_in <= 16, n_out <= 8  none (``ENABLED``)              mlp_narrow_ / mlp_narrow_dx_
+                                                                                     kernels.hip; ``_NarrowTower``
+"narrow_bn"    "narrow" with an affine BatchNorm1d   ``RL8_AMD_BATCHNORM_TOWERS``,   the "narrow" kernels behind ``rl8_
+               that tracks running statistics        off unless 1                    tower_moments_f64`` and ``rl8_
+               behind layer 1                                                        batchnorm_fold_f32``;
+                                                                                     ``_NarrowBatchNormTower``
+"narrow_wide"  H = 64 / 128, 1 <= d_in <= 128, 1 <=  ``RL8_AMD_NARROW_WIDE_TOWERS``, mlp_narrow_wide_kernels.hip;
+               n_out <= 128, outside 16 x 8 (``hip.  off unless 1                    ``_NarrowTower``
+               mlp_narrow_wide_supports``)
+=============  ====================================  ==============================  =====================================
+
+What each family does with a call inside its envelope ("declined": ``tower_forward`` returns ``None``; "refused": the
+entry raises ``ValueError`` before any launch).  The families differ, and each keeps its own answer:
+
+=============  ================  ==========  ====================  ======================  =========  =================
+family         non-contiguous x  empty x     x requires a          parameters checked      autocast   recorded /
+                                             gradient (grad mode)                                     replayed
+=============  ================  ==========  ====================  ======================  =========  =================
+"wide"         copied            refused     declined              no                      runs fp32  yes (planes both
+                                                                                                      ways: ``_plan``)
+"wide_in"      declined          declined    declined              float32 on x's device   declined   no
+"wide_head"    declined          declined    declined              float32 on x's device   declined   no
+"narrow"       copied            refused     formed                no                      runs fp32  no
+"narrow_bn"    declined          declined*   formed                float32 on any GPU,     declined   no
+                                                                   running statistics too
+"narrow_wide"  declined          declined    formed                float32 on x's device   declined   no
+=============  ================  ==========  ====================  ======================  =========  =================
+
+(*) "narrow_bn" also declines one row in training mode: the module then raises torch's own ``ValueError``.
+
+"narrow": fp32 MFMA for layer 2, nothing saved by the forward, activations recomputed by the one backward kernel.
+An input that asks for its gradient (a tower behind a learned encoder) gets it from the same backward launch
 (``rl8_mlp_narrow_backward_dx_f32``).
 
-The same towers with an affine ``BatchNorm1d`` behind layer 1 (family ``"narrow_bn"``: the
-two towers of ``MLPTrader`` and ``TransformerTrader``) run on those kernels too, opt-in with
-``RL8_AMD_BATCHNORM_TOWERS=1``: the norm is folded into layer 1 from the batch's first and
-second moments of x (``_NarrowBatchNormTower``; the algebra stands above it, and
+"narrow_bn" (the two towers of ``MLPTrader`` and ``TransformerTrader``): the norm is folded into layer 1 from the
+batch's first and second moments of x (``_NarrowBatchNormTower``; the algebra stands above it, and
 ``batchnorm_tower_reference`` is its torch expression).
 
-Width-256 towers whose first layer reads 17 to 128 floats (family "wide input",
-``mlp_wide_in_kernels.hip``, ``_WideInputTower``) run in fp32 MFMA throughout: layer 1 too is
-a matrix-core product, the forward saves h1 and h2, and the backward walks the rows in
-segments (dW2 alone on exact bf16 planes, ``WIDE_INPUT_DW2_PLANES``).  ``RL8_AMD_WIDE_INPUT_TOWERS=0`` sends them to the torch modules.
+"wide_in" runs in fp32 MFMA throughout: layer 1 too is a matrix-core product, the forward saves h1 and h2, and the
+backward walks the rows in segments (dW2 alone on exact bf16 planes, ``WIDE_INPUT_DW2_PLANES``).  "wide_head" runs
+through the same node: there the head, ``dout @ W3`` and dW3 are matrix-core products as well.  "narrow_wide" is the
+narrow scheme with every product on fp32 MFMA.
 
-Width-256 towers whose heads have 9 to 128 outputs in all, behind 1 to 128 inputs (family "wide head",
-``mlp_wide_out_kernels.hip``), run through the same node: there the head, ``dout @ W3`` and dW3 are
-matrix-core products as well.  ``RL8_AMD_WIDE_HEAD_TOWERS=0`` sends them to the torch modules.
-
-``tower_forward`` falls back to the module's own eager path whenever the tower
-is none of these shapes (other widths, activations, other norm layers, non-HIP or
-non-fp32 inputs), so custom models are unaffected.
-
-Under ``enable_amp`` (torch autocast) the fused towers still run, at fp32 accuracy: that is
+Under ``enable_amp`` (torch autocast) the "wide" and "narrow" towers still run, at fp32 accuracy: that is
 at least the precision autocast asks for, and on MI355X it is also ~5x faster than
 the autocast path of the same modules (37 vs 8 M transitions/s on the headline
 config), whose casts and elementwise launches dominate at this width.
@@ -541,59 +575,25 @@ def _tower_params(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear]) -> l
     return [l1.weight, l1.bias, l2.weight, l2.bias, *[h.weight for h in heads], *[h.bias for h in heads]]
 
 
-def _family(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[str, nn.Linear, nn.Linear]:
-    """The one place the module structure is inspected: (family, layer1, layer2) if ``trunk`` is
-    ``Sequential(MLP(Linear, ReLU, Linear), ReLU)`` with biased layers of one width and biased heads (one at least) that
-    read it -- "wide": 256, "narrow": a width in ``hip.MLP_NARROW_HIDDEN`` (``mlp_narrow_kernels.hip``) -- else ``None``.
-    "narrow_bn": a narrow tower with an affine ``BatchNorm1d`` that tracks running statistics behind layer 1,
-    ``Sequential(MLP(Linear, BatchNorm1d, ReLU, Linear), ReLU)`` (the norm is ``trunk[0][1]``)."""
-    if not isinstance(trunk, nn.Sequential) or len(trunk) < 2:
-        return None
-    mlp, act = trunk[0], trunk[1]
-    if not isinstance(mlp, nn.Sequential) or len(mlp) not in (3, 4) or not isinstance(act, nn.ReLU):
-        return None
-    norm = mlp[1] if len(mlp) == 4 else None
-    l1, a1, l2 = mlp[0], mlp[-2], mlp[-1]
-    if not (isinstance(l1, nn.Linear) and isinstance(a1, nn.ReLU) and isinstance(l2, nn.Linear)):
-        return None
-    width = l1.out_features
-    family = "narrow" if width in hip.MLP_NARROW_HIDDEN else "wide" if width == hip.MLP_HIDDEN else None
-    if norm is not None:
-        if not (type(norm) is nn.BatchNorm1d and family == "narrow" and norm.num_features == width and norm.affine
-                and norm.track_running_stats and norm.running_mean is not None):
-            return None
-        family = "narrow_bn"
-    if family is None or l2.in_features != width or l2.out_features != width:
-        return None
-    if l1.in_features > hip.MLP_MAX_IN or l1.bias is None or l2.bias is None:
-        return None
-    if not heads or sum(h.out_features for h in heads) > hip.MLP_MAX_OUT or any(h.bias is None for h in heads):
-        return None
-    if any(h.in_features != width for h in heads):
-        return None
-    return family, l1, l2
-
-
 class _NarrowTower(torch.autograd.Function):
-    """A narrow tower (hidden width 64 / 128): one forward kernel that saves nothing, one backward kernel that
-    recomputes the activations from x, and the fixed-order reduction of its partial gradients."""
+    """A narrow tower (hidden width 64 / 128; ``family`` "narrow", or "narrow_wide": mlp_narrow_wide_kernels.hip): one
+    forward kernel that saves nothing, one backward kernel that recomputes the activations from x, and the fixed-order
+    reduction of its partial gradients."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, w3, b3):  # type: ignore[override]
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3, family):  # type: ignore[override]
         ctx.save_for_backward(x, w1, b1, w2, b2, w3, b3)
-        # (more than MLP_MAX_IN inputs or MLP_MAX_OUT outputs: the narrow-wide family, mlp_narrow_wide_kernels.hip)
-        if w1.shape[1] > hip.MLP_MAX_IN or w3.shape[0] > hip.MLP_MAX_OUT:
-            return hip.mlp_narrow_wide_forward(x, w1, b1, w2, b2, w3, b3)
-        return hip.mlp_narrow_forward(x, w1, b1, w2, b2, w3, b3)
+        ctx.family = family
+        forward = hip.mlp_narrow_wide_forward if family == "narrow_wide" else hip.mlp_narrow_forward
+        return forward(x, w1, b1, w2, b2, w3, b3)
 
     @staticmethod
     def backward(ctx, dout):  # type: ignore[override]
         x, w1, b1, w2, b2, w3, _ = ctx.saved_tensors
-        wide = w1.shape[1] > hip.MLP_MAX_IN or w3.shape[0] > hip.MLP_MAX_OUT  # (the family of the forward)
-        backward = hip.mlp_narrow_wide_backward if wide else hip.mlp_narrow_backward
+        backward = hip.mlp_narrow_wide_backward if ctx.family == "narrow_wide" else hip.mlp_narrow_backward
         # (an input that asks for its gradient -- a tower behind a learned encoder -- takes the entry that forms dx)
         g = backward(x, dout.contiguous().float(), w1, b1, w2, b2, w3, want_dx=ctx.needs_input_grad[0])
-        return g.get("x"), g["w1"], g["b1"], g["w2"], g["b2"], g["w3"], g["b3"]
+        return g.get("x"), g["w1"], g["b1"], g["w2"], g["b2"], g["w3"], g["b3"], None
 
 
 # --------------------------------------------------------------------------- #
@@ -753,24 +753,11 @@ class _NarrowBatchNormTower(torch.autograd.Function):
         return (dx, dw1.float(), db1.float(), dgamma.float(), dbeta.float(), g["w2"], g["b2"], g["w3"], g["b3"], None)
 
 
-def _batchnorm_tower_forward(l1: nn.Linear, norm: nn.BatchNorm1d, l2: nn.Linear, w3: torch.Tensor, b3: torch.Tensor,
-                             x: torch.Tensor) -> None | torch.Tensor:
-    """The "narrow_bn" route, or ``None`` when this call is not its: the switch off, autocast, an ``x`` that is not
-    dense or is empty, parameters that are not float32 on the device, one row in training mode (the module then raises
-    torch's own ``ValueError``)."""
-    if not batchnorm_towers_on() or torch.is_autocast_enabled() or not x.is_contiguous() or x.numel() == 0:
-        return None
-    if norm.training and x.shape[0] == 1:
-        return None
-    params = (l1.weight, l1.bias, norm.weight, norm.bias, l2.weight, l2.bias, w3, b3)
-    if not all(p.is_cuda and p.dtype == torch.float32 for p in (*params, norm.running_mean, norm.running_var)):
-        return None
-    return _NarrowBatchNormTower.apply(x, *params, norm)
-
-
 # --------------------------------------------------------------------------- #
 # Wide-input towers: width 256 behind 17 to 128 inputs (mlp_wide_in_kernels.hip), fp32 MFMA throughout.  Never
 # recorded or replayed for the rollout (no planes), and no input gradient: a call whose x asks for one is declined.
+# Wide-head towers -- heads of 9 to 128 outputs in all, behind 1 to 128 inputs (mlp_wide_out_kernels.hip), the head
+# and its gradients on the matrix cores too -- run through the same node.
 # --------------------------------------------------------------------------- #
 #: Rows per segment of the wide-input backward: dZ1 and dZ2 ([rows, 256] fp32 each) are scratch of one segment, so
 #: the two together never exceed 2 GiB however long the minibatch is.  Read on every call.
@@ -793,64 +780,50 @@ def _wide_input_supported(d_in: int, n_out: int) -> bool:
     return hip.mlp_wide_in_supports(d_in, n_out)
 
 
-def _wide_input_family(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[nn.Linear, nn.Linear]:
-    """(layer1, layer2) if ``trunk`` is the structure ``_family`` calls "wide" -- ``Sequential(MLP(Linear, ReLU,
-    Linear), ReLU)`` at width 256 with biased layers and biased heads (one at least) that read it -- whose first layer
-    reads MORE than ``hip.MLP_MAX_IN`` floats, up to what ``hip.mlp_wide_in_supports`` takes; else ``None``."""
-    if not isinstance(trunk, nn.Sequential) or len(trunk) < 2:
-        return None
-    mlp, act = trunk[0], trunk[1]
-    if not isinstance(mlp, nn.Sequential) or len(mlp) != 3 or not isinstance(act, nn.ReLU):
-        return None
-    l1, a1, l2 = mlp[0], mlp[1], mlp[2]
-    if not (isinstance(l1, nn.Linear) and isinstance(a1, nn.ReLU) and isinstance(l2, nn.Linear)):
-        return None
-    width = hip.MLP_HIDDEN
-    if l1.out_features != width or l2.in_features != width or l2.out_features != width:
-        return None
-    if l1.in_features <= hip.MLP_MAX_IN or l1.bias is None or l2.bias is None:
-        return None
-    if not heads or any(h.bias is None or h.in_features != width for h in heads):
-        return None
-    n_out = sum(h.out_features for h in heads)
-    if n_out > hip.MLP_MAX_OUT or not _wide_input_supported(l1.in_features, n_out):
-        return None
-    return l1, l2
+def wide_head_towers_on() -> bool:
+    """``RL8_AMD_WIDE_HEAD_TOWERS=0`` (read on every call) sends the wide-head towers to the torch modules: the
+    tests' yardstick.  On by default."""
+    return os.environ.get("RL8_AMD_WIDE_HEAD_TOWERS", "1") != "0"
 
 
-def _packed_w1(layer: nn.Linear, family: str = "in") -> torch.Tensor:
-    """``hip.mlp_wide_in_pack_w1(layer.weight)`` (``family`` "out": ``hip.mlp_wide_out_pack_w1``, which takes any
-    1 <= d_in <= 128), cached on the layer as ``_packed`` caches W2: re-made when the optimizer has changed the weight
-    (version counter) or the weight tensor has been replaced / moved."""
+@functools.lru_cache(maxsize=None)
+def _wide_head_supported(d_in: int, n_out: int) -> bool:
+    """Compiled for these widths: fixed by the build, asked once per pair."""
+    return hip.mlp_wide_out_supports(d_in, n_out)
+
+
+def _packed_w1(layer: nn.Linear, family: str) -> torch.Tensor:
+    """``hip.mlp_wide_in_pack_w1(layer.weight)`` (``family`` "wide_head": ``hip.mlp_wide_out_pack_w1``, which takes
+    any 1 <= d_in <= 128), cached on the layer as ``_packed`` caches W2: re-made when the optimizer has changed the
+    weight (version counter) or the weight tensor has been replaced / moved."""
     w1 = layer.weight
-    key = "_rl8_w1_pack" if family == "in" else "_rl8_w1_pack_out"
+    key = "_rl8_w1_pack_out" if family == "wide_head" else "_rl8_w1_pack"
     hit = layer.__dict__.get(key)
     if hit is not None and hit[0] == w1._version and hit[1] == w1.data_ptr():
         return hit[2]
-    packed = hip.mlp_wide_in_pack_w1(w1) if family == "in" else hip.mlp_wide_out_pack_w1(w1)
+    packed = hip.mlp_wide_out_pack_w1(w1) if family == "wide_head" else hip.mlp_wide_in_pack_w1(w1)
     layer.__dict__[key] = (w1._version, w1.data_ptr(), packed)
     return packed
 
 
 class _WideInputTower(torch.autograd.Function):
-    """A wide-input tower: one forward kernel (which stores h1 and h2 when a backward can follow); the backward walks
-    the rows in segments of ``WIDE_INPUT_SEGMENT_ROWS`` -- per segment the data gradient (dZ1, dZ2 into scratch, one
-    row of small-gradient partials per workgroup), dW1 += dZ1^T x and dW2 += dZ2^T h1 (``WIDE_INPUT_DW2_PLANES``) -- in
-    order, so the sums are the same bits from run to run."""
+    """A wide-input tower (``family`` "wide_in", or "wide_head"): one forward kernel (which stores h1 and h2 when a
+    backward can follow); the backward walks the rows in segments of ``WIDE_INPUT_SEGMENT_ROWS`` -- per segment the data
+    gradient (dZ1, dZ2 into scratch, one row of small-gradient partials per workgroup), dW1 += dZ1^T x and dW2 +=
+    dZ2^T h1 (``WIDE_INPUT_DW2_PLANES``) -- in order, so the sums are the same bits from run to run."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, w3, b3, layer1, layer2, grad_mode):  # type: ignore[override]
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3, layer1, layer2, grad_mode, family):  # type: ignore[override]
         # (grad_mode: the caller's; inside forward() grad mode is always off -- see _FusedTower)
         need_grad = grad_mode and any(ctx.needs_input_grad[1:7])
-        if w3.shape[0] > hip.MLP_MAX_OUT:  # the wide-head family (mlp_wide_out_kernels.hip): the head on the matrix cores
+        w1p, w2p = _packed_w1(layer1, family), _packed(layer2, False, False)
+        if family == "wide_head":  # (mlp_wide_out_kernels.hip: the head on the matrix cores)
             # (W3 is packed per call: two heads arrive concatenated, a fresh tensor every time)
-            out, h1, h2 = hip.mlp_wide_out_forward(x, _packed_w1(layer1, "out"), b1, _packed(layer2, False, False), b2,
-                                                   hip.mlp_wide_out_pack_w3(w3), b3, save=need_grad)
+            out, h1, h2 = hip.mlp_wide_out_forward(x, w1p, b1, w2p, b2, hip.mlp_wide_out_pack_w3(w3), b3, save=need_grad)
         else:
-            out, h1, h2 = hip.mlp_wide_in_forward(x, _packed_w1(layer1), b1, _packed(layer2, False, False), b2, w3, b3,
-                                                  save=need_grad)
+            out, h1, h2 = hip.mlp_wide_in_forward(x, w1p, b1, w2p, b2, w3, b3, save=need_grad)
         if need_grad:
-            ctx.layer2 = layer2
+            ctx.layer2, ctx.family = layer2, family
             # (w1 and w2 are saved although the kernels read packed copies: autograd's version check then refuses a
             # backward after an in-place change of a weight, as it would for the eager modules)
             ctx.save_for_backward(x, h1, h2, w3, w1, w2)
@@ -865,7 +838,7 @@ class _WideInputTower(torch.autograd.Function):
         w2t = _packed(ctx.layer2, True, False)
         dz1 = torch.empty(min(m, segment), hidden, dtype=torch.float32, device=x.device)
         dz2 = torch.empty_like(dz1)
-        wide_head = n_out > hip.MLP_MAX_OUT  # (the family of the forward: its partial rows carry no dW3)
+        wide_head = ctx.family == "wide_head"  # (its partial rows carry no dW3)
         partials = torch.empty(hip.load().rl8_mlp_wide_in_max_rows(),
                                2 * hidden + n_out if wide_head else 2 * hidden + n_out * hidden + n_out,
                                dtype=torch.float32, device=x.device)
@@ -889,77 +862,15 @@ class _WideInputTower(torch.autograd.Function):
             hip.mlp_wgrad(z2, h1[rows], out=dw2, accumulate=at > 0, planes=planes)
         if wide_head:
             db1, db2, db3 = torch.split(small, (hidden, hidden, n_out))
-            return None, dw1, db1, dw2, db2, dw3, db3, None, None, None
+            return None, dw1, db1, dw2, db2, dw3, db3, None, None, None, None
         db1, db2, dw3, db3 = torch.split(small, (hidden, hidden, n_out * hidden, n_out))
-        return None, dw1, db1, dw2, db2, dw3.view(n_out, hidden), db3, None, None, None
-
-
-def _wide_input_tower_forward(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear], x: torch.Tensor, *,
-                              switch=wide_input_towers_on) -> None | torch.Tensor:
-    """The wide-input route (``switch``: ``wide_head_towers_on`` for the wide-head family, which runs through the same
-    node), or ``None`` when this call is not its: the switch off, autocast, an ``x`` that is not dense or is empty or
-    asks for its gradient (the family forms none, and must not drop one silently), parameters that are not float32 on
-    the device."""
-    if not switch() or torch.is_autocast_enabled() or not x.is_contiguous() or x.shape[0] < 1:
-        return None
-    if x.shape[1] != l1.in_features or (x.requires_grad and torch.is_grad_enabled()):
-        return None
-    w3 = heads[0].weight if len(heads) == 1 else torch.cat([h.weight for h in heads], 0)
-    b3 = heads[0].bias if len(heads) == 1 else torch.cat([h.bias for h in heads], 0)
-    params = (l1.weight, l1.bias, l2.weight, l2.bias, w3, b3)
-    if not all(p.is_cuda and p.dtype == torch.float32 and p.device == x.device for p in params):
-        return None
-    return _WideInputTower.apply(x, *params, l1, l2, torch.is_grad_enabled())
-
-
-# --------------------------------------------------------------------------- #
-# Wide-head towers: width 256 with heads of 9 to 128 outputs in all, behind 1 to 128 inputs (mlp_wide_out_kernels.hip),
-# fp32 MFMA throughout, the head and its gradients included.  They run through ``_WideInputTower``, which takes its
-# entries from ``w3.shape[0]``.  Never recorded or replayed for the rollout (no planes: ``_Plan.recordable`` is not
-# even asked, the family has no plan), and no input gradient: a call whose x asks for one is declined.
-# --------------------------------------------------------------------------- #
-def wide_head_towers_on() -> bool:
-    """``RL8_AMD_WIDE_HEAD_TOWERS=0`` (read on every call) sends the wide-head towers to the torch modules: the
-    tests' yardstick.  On by default."""
-    return os.environ.get("RL8_AMD_WIDE_HEAD_TOWERS", "1") != "0"
-
-
-@functools.lru_cache(maxsize=None)
-def _wide_head_supported(d_in: int, n_out: int) -> bool:
-    """Compiled for these widths: fixed by the build, asked once per pair."""
-    return hip.mlp_wide_out_supports(d_in, n_out)
-
-
-def _wide_head_family(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[nn.Linear, nn.Linear]:
-    """(layer1, layer2) if ``trunk`` is the structure ``_family`` calls "wide" -- ``Sequential(MLP(Linear, ReLU,
-    Linear), ReLU)`` at width 256 with biased layers and biased heads (one at least) that read it -- whose heads have
-    MORE than ``hip.MLP_MAX_OUT`` outputs in all, up to what ``hip.mlp_wide_out_supports`` takes, behind any input
-    width it takes; else ``None``.  Asked after ``_family`` and ``_wide_input_family`` have both said ``None``."""
-    if not isinstance(trunk, nn.Sequential) or len(trunk) < 2:
-        return None
-    mlp, act = trunk[0], trunk[1]
-    if not isinstance(mlp, nn.Sequential) or len(mlp) != 3 or not isinstance(act, nn.ReLU):
-        return None
-    l1, a1, l2 = mlp[0], mlp[1], mlp[2]
-    if not (isinstance(l1, nn.Linear) and isinstance(a1, nn.ReLU) and isinstance(l2, nn.Linear)):
-        return None
-    width = hip.MLP_HIDDEN
-    if l1.out_features != width or l2.in_features != width or l2.out_features != width:
-        return None
-    if l1.bias is None or l2.bias is None:
-        return None
-    if not heads or any(h.bias is None or h.in_features != width for h in heads):
-        return None
-    n_out = sum(h.out_features for h in heads)
-    if n_out <= hip.MLP_MAX_OUT or l1.in_features < 1 or not _wide_head_supported(l1.in_features, n_out):
-        return None
-    return l1, l2
+        return None, dw1, db1, dw2, db2, dw3.view(n_out, hidden), db3, None, None, None, None
 
 
 # --------------------------------------------------------------------------- #
 # Narrow-wide towers: width 64 / 128 behind 1 to 128 inputs with heads of 1 to 128 outputs in all, more than
 # MLP_MAX_IN inputs or more than MLP_MAX_OUT outputs (mlp_narrow_wide_kernels.hip), fp32 MFMA throughout.  They run
-# through ``_NarrowTower``, which takes its entries from the shapes it is handed, and form dL/dx where x asks for it.
+# through ``_NarrowTower`` and form dL/dx where x asks for it.
 # Opt-in until the tests that pin these towers to the torch modules flip with the default.
 # --------------------------------------------------------------------------- #
 def narrow_wide_towers_on() -> bool:
@@ -974,47 +885,156 @@ def _narrow_wide_supported(hidden: int, d_in: int, n_out: int) -> bool:
     return hip.mlp_narrow_wide_supports(hidden, d_in, n_out)
 
 
-def _narrow_wide_family(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | tuple[nn.Linear, nn.Linear]:
-    """(layer1, layer2) if ``trunk`` is the structure ``_family`` calls "narrow" -- ``Sequential(MLP(Linear, ReLU,
-    Linear), ReLU)`` at a width in ``hip.MLP_NARROW_HIDDEN`` with biased layers and biased heads (one at least) that
-    read it -- whose first layer reads MORE than ``hip.MLP_MAX_IN`` floats or whose heads have MORE than
-    ``hip.MLP_MAX_OUT`` outputs in all, up to what ``hip.mlp_narrow_wide_supports`` takes; else ``None``.  Asked after
-    ``_family``, ``_wide_input_family`` and ``_wide_head_family`` have all said ``None``."""
+# --------------------------------------------------------------------------- #
+# Classification and routing: what every tower call goes through.
+# --------------------------------------------------------------------------- #
+@dataclasses.dataclass(frozen=True)
+class _Tower:
+    """What ``_classify`` found: the family (a row of the module docstring's table), the two layers of the trunk, the
+    BatchNorm1d between them ("narrow_bn"; else ``None``), the hidden width, the inputs of layer 1 and the outputs of
+    the heads in all."""
+    family: str
+    l1: nn.Linear
+    norm: None | nn.BatchNorm1d
+    l2: nn.Linear
+    width: int
+    d_in: int
+    n_out: int
+
+
+def _classify(trunk: nn.Module, heads: Sequence[nn.Linear]) -> None | _Tower:
+    """The one place the module structure is inspected.  ``trunk`` must be ``Sequential(MLP(Linear, ReLU, Linear),
+    ReLU)`` -- only ``trunk[:2]`` is looked at -- with biased layers of one width and biased heads (one at least) that
+    read it; or, with an affine ``BatchNorm1d`` that tracks running statistics behind layer 1, ``Sequential(MLP(Linear,
+    BatchNorm1d, ReLU, Linear), ReLU)``.  The family then follows from (width, d_in, n_out, norm) alone: the envelopes
+    of the module docstring's table, which are disjoint.  ``None``: no family's.  Reads module attributes only -- no
+    switch, no tensor -- so the answer is the same on CPU modules and in every environment."""
     if not isinstance(trunk, nn.Sequential) or len(trunk) < 2:
         return None
     mlp, act = trunk[0], trunk[1]
-    if not isinstance(mlp, nn.Sequential) or len(mlp) != 3 or not isinstance(act, nn.ReLU):
+    if not isinstance(mlp, nn.Sequential) or len(mlp) not in (3, 4) or not isinstance(act, nn.ReLU):
         return None
-    l1, a1, l2 = mlp[0], mlp[1], mlp[2]
+    norm = mlp[1] if len(mlp) == 4 else None
+    l1, a1, l2 = mlp[0], mlp[-2], mlp[-1]
     if not (isinstance(l1, nn.Linear) and isinstance(a1, nn.ReLU) and isinstance(l2, nn.Linear)):
         return None
     width = l1.out_features
-    if width not in hip.MLP_NARROW_HIDDEN or l2.in_features != width or l2.out_features != width:
+    if l2.in_features != width or l2.out_features != width or l1.bias is None or l2.bias is None:
         return None
-    if l1.bias is None or l2.bias is None:
+    if norm is not None and not (type(norm) is nn.BatchNorm1d and norm.num_features == width and norm.affine
+                                 and norm.track_running_stats and norm.running_mean is not None):
         return None
     if not heads or any(h.bias is None or h.in_features != width for h in heads):
         return None
     d_in, n_out = l1.in_features, sum(h.out_features for h in heads)
-    if d_in <= hip.MLP_MAX_IN and n_out <= hip.MLP_MAX_OUT:
-        return None
-    if d_in < 1 or n_out < 1 or not _narrow_wide_supported(width, d_in, n_out):
-        return None
-    return l1, l2
+
+    # The envelopes.  A compiled-envelope query is reached only by a shape otherwise inside its family's range.
+    narrow = width in hip.MLP_NARROW_HIDDEN
+    small = d_in <= hip.MLP_MAX_IN and n_out <= hip.MLP_MAX_OUT  # (what the "wide" and "narrow" kernels take)
+    family = None
+    if norm is not None:  # (never "narrow_wide": the fold is written for the narrow kernels alone)
+        family = "narrow_bn" if narrow and small else None
+    elif small:
+        family = "narrow" if narrow else "wide" if width == hip.MLP_HIDDEN else None
+    elif narrow:
+        family = "narrow_wide" if d_in >= 1 and n_out >= 1 and _narrow_wide_supported(width, d_in, n_out) else None
+    elif width == hip.MLP_HIDDEN and n_out <= hip.MLP_MAX_OUT:  # (so more than MLP_MAX_IN inputs)
+        family = "wide_in" if _wide_input_supported(d_in, n_out) else None
+    elif width == hip.MLP_HIDDEN:  # (more than MLP_MAX_OUT outputs, behind any input width)
+        family = "wide_head" if d_in >= 1 and _wide_head_supported(d_in, n_out) else None
+    return None if family is None else _Tower(family, l1, norm, l2, width, d_in, n_out)
 
 
-def _narrow_wide_tower_forward(l1: nn.Linear, l2: nn.Linear, heads: Sequence[nn.Linear],
-                               x: torch.Tensor) -> None | torch.Tensor:
-    """The narrow-wide route, or ``None`` when this call is not its: autocast, an ``x`` that is not dense or is empty
-    or of another width, parameters that are not float32 on the device."""
-    if torch.is_autocast_enabled() or not x.is_contiguous() or x.shape[0] < 1 or x.shape[1] != l1.in_features:
+def _head_params(heads: Sequence[nn.Linear]) -> tuple[torch.Tensor, torch.Tensor]:
+    """(w3, b3): the heads' weights and biases as one layer -- the parameters themselves for one head, fresh
+    concatenations for more."""
+    if len(heads) == 1:
+        return heads[0].weight, heads[0].bias
+    return torch.cat([h.weight for h in heads], 0), torch.cat([h.bias for h in heads], 0)
+
+
+def _float32_on_device(params, device: None | torch.device) -> bool:
+    """Every tensor of ``params`` is float32 on ``device`` (``None``: on any GPU, all "narrow_bn" asks)."""
+    return all(p.is_cuda and p.dtype == torch.float32 and (device is None or p.device == device) for p in params)
+
+
+def _checked_params(t: _Tower, heads: Sequence[nn.Linear], x: torch.Tensor) -> None | tuple:
+    """The guards "wide_in", "wide_head" and "narrow_wide" share, then the six tower parameters; ``None`` where the
+    call is not theirs: autocast, an ``x`` that is not dense or is empty, parameters not float32 on ``x``'s device."""
+    if torch.is_autocast_enabled() or not x.is_contiguous() or x.shape[0] < 1:
         return None
-    w3 = heads[0].weight if len(heads) == 1 else torch.cat([h.weight for h in heads], 0)
-    b3 = heads[0].bias if len(heads) == 1 else torch.cat([h.bias for h in heads], 0)
-    params = (l1.weight, l1.bias, l2.weight, l2.bias, w3, b3)
-    if not all(p.is_cuda and p.dtype == torch.float32 and p.device == x.device for p in params):
+    params = (t.l1.weight, t.l1.bias, t.l2.weight, t.l2.bias, *_head_params(heads))
+    return params if _float32_on_device(params, x.device) else None
+
+
+def _launch_wide_input(t: _Tower, heads, x, pair_gradients) -> None | torch.Tensor:
+    """Families "wide_in" and "wide_head" (an ``x`` that asks for its gradient never gets here: ``tower_forward``)."""
+    params = _checked_params(t, heads, x)
+    return None if params is None else _WideInputTower.apply(x, *params, t.l1, t.l2, torch.is_grad_enabled(), t.family)
+
+
+def _launch_narrow_wide(t: _Tower, heads, x, pair_gradients) -> None | torch.Tensor:
+    params = _checked_params(t, heads, x)
+    return None if params is None else _NarrowTower.apply(x, *params, t.family)
+
+
+def _launch_narrow(t: _Tower, heads, x, pair_gradients) -> torch.Tensor:
+    return _NarrowTower.apply(x.contiguous(), t.l1.weight, t.l1.bias, t.l2.weight, t.l2.bias, *_head_params(heads), t.family)
+
+
+def _launch_batchnorm(t: _Tower, heads, x, pair_gradients) -> None | torch.Tensor:
+    """Family "narrow_bn", or ``None`` when this call is not its: autocast, an ``x`` that is not dense or is empty, one
+    row in training mode (the module then raises torch's own ``ValueError``), parameters that are not float32 on a
+    GPU."""
+    norm = t.norm
+    if torch.is_autocast_enabled() or not x.is_contiguous() or x.numel() == 0 or (norm.training and x.shape[0] == 1):
         return None
-    return _NarrowTower.apply(x, *params)
+    params = (t.l1.weight, t.l1.bias, norm.weight, norm.bias, t.l2.weight, t.l2.bias, *_head_params(heads))
+    if not _float32_on_device((*params, norm.running_mean, norm.running_var), None):
+        return None
+    return _NarrowBatchNormTower.apply(x, *params, norm)
+
+
+def _launch_wide(t: _Tower, heads, x, pair_gradients) -> torch.Tensor:
+    """Family "wide": the piecewise table for scalar observations (opt-in prototype), the rollout's record, its
+    replay, or the plain launch, in that order."""
+    l1, l2 = t.l1, t.l2
+    if piecewise_mlp.ENABLED and t.d_in == 1:
+        out = piecewise_mlp.tower_forward(l1, l2, heads, x)
+        if out is not None:
+            return out
+    w3, b3 = _head_params(heads)
+    if pair_gradients is None:
+        pair_gradients = bool(l2.__dict__.get("_rl8_rank_one", False))
+    w3_key = _param_key(h.weight for h in heads)
+    plan = _plan(t.d_in, t.n_out, bool(pair_gradients))
+    if _RECORDING is not None and not torch.is_grad_enabled():
+        # (``None``: refused a slab, or a second evaluation at this timestep.  Falling through is the plain launch
+        # below: the replay branch needs grad mode on, and recording needs it off.)
+        out = _RECORDING.record(l1, l2, heads, w3, b3, plan, x)
+        if out is not None:
+            return out
+    if _REPLAY is not None and torch.is_grad_enabled() and plan.recordable:
+        got = _REPLAY.hit(l1, l2, heads, x, t.n_out, plan)
+        if got is not None:
+            replay_stats["replayed_towers"] += 1
+            replay_stats["replayed_rows"] += x.shape[0]
+            return _ReplayedTower.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, w3, b3, l2, plan, w3_key,
+                                        got.out, got.gate, got.h2)
+    return _FusedTower.apply(x.contiguous(), l1.weight, l1.bias, l2.weight, l2.bias, w3, b3, l2,
+                             torch.is_grad_enabled(), plan, w3_key)
+
+
+#: family -> (its switch, read on every call, or ``None``: no switch of its own; its launcher, which applies the
+#: family's remaining guards -- the module docstring's table, row by row -- and returns ``None`` where it declines).
+_ROUTES = {
+    "wide": (None, _launch_wide),
+    "wide_in": (wide_input_towers_on, _launch_wide_input),
+    "wide_head": (wide_head_towers_on, _launch_wide_input),
+    "narrow": (None, _launch_narrow),
+    "narrow_bn": (batchnorm_towers_on, _launch_batchnorm),
+    "narrow_wide": (narrow_wide_towers_on, _launch_narrow_wide),
+}
 
 
 def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Tensor, *,
@@ -1038,53 +1058,14 @@ def tower_forward(trunk: nn.Sequential, heads: Sequence[nn.Linear], x: torch.Ten
     runs the modules, which form it); under ``torch.no_grad()`` no gradient can follow and the kernels run."""
     if not ENABLED or not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
         return None
-    found = _family(trunk, heads)
-    if found is None:  # (only then: the wide-input family begins where _family's input limit ends)
-        wide = _wide_input_family(trunk, heads)
-        if wide is not None:
-            return _wide_input_tower_forward(*wide, heads, x)
-        wide = _wide_head_family(trunk, heads)  # (more than MLP_MAX_OUT outputs, behind any input width)
-        if wide is not None:
-            return _wide_input_tower_forward(*wide, heads, x, switch=wide_head_towers_on)
-        if not narrow_wide_towers_on():  # (opt-in: nothing else is done for it while it is off)
-            return None
-        wide = _narrow_wide_family(trunk, heads)  # (width 64 / 128 beyond the narrow kernels' 16 x 8)
-        return None if wide is None else _narrow_wide_tower_forward(*wide, heads, x)
-    if x.shape[1] != found[1].in_features:
+    tower = _classify(trunk, heads)
+    if tower is None or x.shape[1] != tower.d_in:
         return None
-    family, l1, l2 = found
-    if family == "wide" and x.requires_grad and torch.is_grad_enabled():
+    if tower.width == hip.MLP_HIDDEN and x.requires_grad and torch.is_grad_enabled():
         return None  # (no 256-wide route forms dL/dx, and none may drop it silently: one attribute read for buffer data)
-    if family == "narrow_bn" and not batchnorm_towers_on():  # (opt-in: nothing else is done for it while it is off)
+    switch, launch = _ROUTES[tower.family]
+    if switch is not None and not switch():  # (an opt-in family: nothing else is done for it while it is off)
         return None
-    # opt-in prototype: scalar observations from an exact piecewise-linear table
-    if family == "wide" and piecewise_mlp.ENABLED and x.shape[1] == 1:
-        out = piecewise_mlp.tower_forward(l1, l2, heads, x)
-        if out is not None:
-            return out
-    w3 = heads[0].weight if len(heads) == 1 else torch.cat([h.weight for h in heads], 0)
-    b3 = heads[0].bias if len(heads) == 1 else torch.cat([h.bias for h in heads], 0)
-    if family == "narrow_bn":
-        return _batchnorm_tower_forward(l1, trunk[0][1], l2, w3, b3, x)
-    if family == "narrow":  # (never recorded or replayed: everything below assumes width 256)
-        return _NarrowTower.apply(x.contiguous(), l1.weight, l1.bias, l2.weight, l2.bias, w3, b3)
-    if pair_gradients is None:
-        pair_gradients = bool(l2.__dict__.get("_rl8_rank_one", False))
-    w3_key = _param_key(h.weight for h in heads)
-    n_out = w3.shape[0]
-    plan = _plan(x.shape[1], n_out, bool(pair_gradients))
-    if _RECORDING is not None and not torch.is_grad_enabled():
-        # (``None``: refused a slab, or a second evaluation at this timestep.  Falling through is the plain launch
-        # below: the replay branch needs grad mode on, and recording needs it off.)
-        out = _RECORDING.record(l1, l2, heads, w3, b3, plan, x)
-        if out is not None:
-            return out
-    if _REPLAY is not None and torch.is_grad_enabled() and plan.recordable:
-        got = _REPLAY.hit(l1, l2, heads, x, n_out, plan)
-        if got is not None:
-            replay_stats["replayed_towers"] += 1
-            replay_stats["replayed_rows"] += x.shape[0]
-            return _ReplayedTower.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, w3, b3, l2, plan, w3_key,
-                                        got.out, got.gate, got.h2)
-    return _FusedTower.apply(x.contiguous(), l1.weight, l1.bias, l2.weight, l2.bias, w3, b3, l2,
-                             torch.is_grad_enabled(), plan, w3_key)
+    return launch(tower, heads, x, pair_gradients)
+
+

@@ -64,7 +64,7 @@ CONTRACT: dict[str, dict] = {
     },
     "rl8_amd.nn.fused_mlp._NarrowTower": {
         "entry": "fused_mlp.tower_forward",
-        "inputs": {"x": _F, **_TOWER_PARAMS},
+        "inputs": {"x": _F, **_TOWER_PARAMS, "family": _N},
         "outputs": {"out": _DIFF},
     },
     "rl8_amd.nn.fused_mlp._NarrowBatchNormTower": {
@@ -75,7 +75,7 @@ CONTRACT: dict[str, dict] = {
     },
     "rl8_amd.nn.fused_mlp._WideInputTower": {
         "entry": "fused_mlp.tower_forward",
-        "inputs": {"x": _D, **_TOWER_PARAMS, "layer1": _N, "layer2": _N, "grad_mode": _N},
+        "inputs": {"x": _D, **_TOWER_PARAMS, "layer1": _N, "layer2": _N, "grad_mode": _N, "family": _N},
         "outputs": {"out": _DIFF},
     },
     "rl8_amd.nn.piecewise_mlp._PiecewiseTower": {

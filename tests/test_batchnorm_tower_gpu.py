@@ -337,7 +337,7 @@ def test_plain_narrow_tower_gives_its_input_a_gradient(shape_index):
     c = plain_case(shape_index, 4)
     hidden, d_in, n = DX_SHAPES[shape_index]
     net = plain_tower(hidden, d_in, n, c["p"])
-    assert fused_mlp._family(net[:2], [net[2]])[0] == "narrow"
+    assert fused_mlp._classify(net[:2], [net[2]]).family == "narrow"
     runs = []
     for wants in (True, False):
         net.zero_grad()
@@ -486,6 +486,8 @@ def test_calls_the_route_declines_run_the_modules(monkeypatch):
         assert not wide.is_contiguous() and fused_mlp.tower_forward(trunk, heads, wide) is None
         assert fused_mlp.tower_forward(trunk, heads, x.double()) is None
         assert fused_mlp.tower_forward(trunk, heads, x[:0]) is None
+        for other in (copy.deepcopy(net).double(), copy.deepcopy(net).cpu()):  # parameters not float32 on the GPU
+            assert fused_mlp.tower_forward(other[:2], [other[2]], x) is None
         assert torch.equal(algotrading_models._tower(copy.deepcopy(net), wide), copy.deepcopy(net)(wide))
     assert count.ran == {}
     net.eval()

@@ -92,21 +92,23 @@ def test_family_names_the_batchnorm_towers_and_nothing_else_new():
     for model_cls, width, d_in in ((MLPTrader, 128, 7), (TransformerTrader, 64, 11)):
         model = model_cls(env.observation_spec, env.action_spec)
         for t in (model.feature_model, model.vf_model):
-            family, l1, l2 = fused_mlp._family(t[:2], [t[2]])
-            assert family == "narrow_bn" and l1 is t[0][0] and l2 is t[0][3]
+            found = fused_mlp._classify(t[:2], [t[2]])
+            l1, l2 = found.l1, found.l2
+            assert found.family == "narrow_bn" and l1 is t[0][0] and l2 is t[0][3] and found.norm is t[0][1]
             assert (l1.in_features, l1.out_features) == (d_in, width)
-    assert fused_mlp._family(*bn_tower(norm_layer=nn.LayerNorm)) is None
-    assert fused_mlp._family(*bn_tower(affine=False)) is None
-    assert fused_mlp._family(*bn_tower(track_running_stats=False)) is None
-    assert fused_mlp._family(*bn_tower(width=256)) is None
-    assert fused_mlp._family(*bn_tower(width=96)) is None
-    assert fused_mlp._family(*bn_tower(d_in=17)) is None
+    assert fused_mlp._classify(*bn_tower(norm_layer=nn.LayerNorm)) is None
+    assert fused_mlp._classify(*bn_tower(affine=False)) is None
+    assert fused_mlp._classify(*bn_tower(track_running_stats=False)) is None
+    assert fused_mlp._classify(*bn_tower(width=256)) is None
+    assert fused_mlp._classify(*bn_tower(width=96)) is None
+    assert fused_mlp._classify(*bn_tower(d_in=17)) is None  # (outside 16 x 8: ``None``, not "narrow_wide")
+    assert fused_mlp._classify(*bn_tower(n=9)) is None
     trunk = nn.Sequential(MLP(7, (128, 128, 128), norm_layer=nn.BatchNorm1d), nn.ReLU())  # three hidden layers
-    assert fused_mlp._family(trunk, [nn.Linear(128, 3)]) is None
-    assert fused_mlp._family(*bn_tower(d_in=16, width=64, n=8))[0] == "narrow_bn"
+    assert fused_mlp._classify(trunk, [nn.Linear(128, 3)]) is None
+    assert fused_mlp._classify(*bn_tower(d_in=16, width=64, n=8)).family == "narrow_bn"
     for width, family in ((64, "narrow"), (128, "narrow"), (256, "wide")):  # plain towers classify as before
         trunk = nn.Sequential(MLP(7, (width, width)), nn.ReLU())
-        assert fused_mlp._family(trunk, [nn.Linear(width, 3)])[0] == family
+        assert fused_mlp._classify(trunk, [nn.Linear(width, 3)]).family == family
 
 
 # --- the route off --------------------------------------------------------------------------------------------------

@@ -188,6 +188,22 @@ def test_other_towers_stay_eager(case):
         assert fused_mlp.tower_forward(ok, [nn.Linear(64, 2).to(DEV)], x[:, :min(d_in, 16)].contiguous()) is not None
 
 
+@pytest.mark.parametrize("width", [64, 256])
+def test_a_strided_input_is_copied_and_an_empty_one_refused(width):
+    """Families "narrow" (64) and "wide" (256), the two that take a non-contiguous ``x`` (every other family declines
+    it): the dense copy's own result, bit for bit.  No rows: the entry refuses before any launch."""
+    torch.manual_seed(3)
+    trunk, head = _trunk(1, width, width), nn.Linear(width, 1).to(DEV)
+    x = torch.randn(40, 2, device=DEV)[:, :1]
+    assert not x.is_contiguous()
+    with torch.no_grad():
+        out = fused_mlp.tower_forward(trunk, [head], x)
+        assert out is not None and torch.equal(out, fused_mlp.tower_forward(trunk, [head], x.contiguous()))
+        torch.testing.assert_close(out, head(trunk(x)), rtol=1e-4, atol=1e-5)
+        with pytest.raises(ValueError):
+            fused_mlp.tower_forward(trunk, [head], torch.empty(0, 1, device=DEV))
+
+
 def _cartpole():
     from rl8_amd.envs.cartpole import CartPole
     return CartPole

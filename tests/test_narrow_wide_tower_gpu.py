@@ -164,6 +164,9 @@ def test_routing(hidden, monkeypatch):
     with torch.autocast("cuda", dtype=torch.bfloat16):
         assert fused_mlp.tower_forward(trunk, [head], x) is None
     assert fused_mlp.tower_forward(_trunk(24, hidden, hidden).double(), [nn.Linear(hidden, 12).to(DEV).double()], x.double()) is None
+    # (parameters that are not float32, or not on x's device)
+    assert fused_mlp.tower_forward(_trunk(24, hidden, hidden).double(), [nn.Linear(hidden, 12).to(DEV).double()], x) is None
+    assert fused_mlp.tower_forward(_trunk(24, hidden, hidden).cpu(), [nn.Linear(hidden, 12)], x) is None
     assert fused_mlp.tower_forward(trunk, [head], torch.randn(24, 100, device=DEV).T) is None
     assert fused_mlp.tower_forward(trunk, [head], x[:0]) is None
     assert fused_mlp.tower_forward(trunk, [head], x[:, :23].contiguous()) is None

@@ -1,6 +1,6 @@
 """The narrow-wide tower kernels (rl8_amd/csrc/mlp_narrow_wide_kernels.hip) compiled for gfx950: every instantiation
 present, no scratch, LDS and registers as DESIGN.md states them; the envelope; every entry refusing bad arguments
-before any launch; and the classifier ``fused_mlp._narrow_wide_family`` clause by clause on CPU modules."""
+before any launch; and the classifier ``fused_mlp._classify`` (family "narrow_wide") clause by clause on CPU modules."""
 
 import ctypes
 import os
@@ -101,7 +101,10 @@ def _trunk(d_in, h1, h2, bias=True, act=nn.ReLU):
 def test_the_classifier_clause_by_clause_and_cpu_tensors(switch, monkeypatch):
     monkeypatch.delenv("RL8_AMD_NARROW_WIDE_TOWERS", raising=False) if switch is None else monkeypatch.setenv(
         "RL8_AMD_NARROW_WIDE_TOWERS", switch)
-    family = fused_mlp._narrow_wide_family
+    def family(trunk, heads):  # ((layer 1, layer 2) of a narrow-wide tower, ``None`` for every other answer)
+        found = fused_mlp._classify(trunk, heads)
+        return (found.l1, found.l2) if found is not None and found.family == "narrow_wide" else None
+
     assert fused_mlp.narrow_wide_towers_on() == (switch == "1")
     for h in (64, 128):
         head = nn.Linear(h, 12)
@@ -110,13 +113,14 @@ def test_the_classifier_clause_by_clause_and_cpu_tensors(switch, monkeypatch):
         assert family(trunk, [nn.Linear(h, 6), nn.Linear(h, 6)]) is not None  # (two heads: their outputs in all)
         assert family(trunk, [nn.Linear(h, 4)]) is not None and family(_trunk(4, h, h), [head]) is not None  # one side
         assert family(_trunk(16, h, h), [nn.Linear(h, 8)]) is None  # inside 16 x 8: the narrow kernels' own
+        assert fused_mlp._classify(_trunk(16, h, h), [nn.Linear(h, 8)]).family == "narrow"
         assert family(_trunk(128, h, h), [nn.Linear(h, 128)]) is not None
         assert family(_trunk(129, h, h), [head]) is None and family(trunk, [nn.Linear(h, 129)]) is None
         assert family(trunk, []) is None and family(trunk, [nn.Linear(h, 12, bias=False)]) is None
         assert family(_trunk(24, h, h, bias=False), [head]) is None and family(_trunk(24, h, h, act=nn.Tanh), [head]) is None
         assert family(_trunk(24, h, 192 - h), [nn.Linear(192 - h, 12)]) is None  # mixed widths
-        assert family(nn.Sequential(nn.Sequential(trunk[0][0], nn.BatchNorm1d(h), nn.ReLU(), trunk[0][2]), nn.ReLU()), [head]) is None
-        assert fused_mlp._family(trunk, [head]) is None  # (unchanged: the new predicate begins where it ends)
+        with_norm = nn.Sequential(nn.Sequential(trunk[0][0], nn.BatchNorm1d(h), nn.ReLU(), trunk[0][2]), nn.ReLU())
+        assert fused_mlp._classify(with_norm, [head]) is None  # (a BatchNorm tower outside 16 x 8 is no family's)
         assert fused_mlp.tower_forward(trunk, [head], torch.randn(10, 24)) is None  # CPU tensors, whatever the switch
     for width in (96, 256):
         assert family(_trunk(24, width, width), [nn.Linear(width, 12)]) is None

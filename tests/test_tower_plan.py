@@ -134,7 +134,7 @@ def test_backward_runs_the_forwards_plan(envelopes, monkeypatch):
 
 
 # --------------------------------------------------------------------------- #
-# ``fused_mlp._family`` against the two predicates it replaced.
+# ``fused_mlp._classify`` against the two predicates of the 16 x 8 families ("wide", "narrow") as they once stood.
 # --------------------------------------------------------------------------- #
 def _match(trunk, heads):
     """``fused_mlp._match`` as it stood while each family had its own predicate."""
@@ -217,6 +217,23 @@ def _old_answer(trunk, heads):
     return ("narrow", *narrow) if narrow is not None else ("wide", *wide) if wide is not None else None
 
 
+#: the families beyond 16 inputs or 8 outputs, which neither old predicate knew: their rows must map to ``None`` here
+_BEYOND = ("wide_in", "wide_head", "narrow_wide")
+_NINE = ("one_of_9", "two_sum_9")
+
+
+def _answer(trunk, heads):
+    """``_classify``'s answer in the form of the old ones: (family, layer 1, layer 2) for "wide" / "narrow", else ``None``."""
+    t = fused_mlp._classify(trunk, heads)
+    return (t.family, t.l1, t.l2) if t is not None and t.family in ("wide", "narrow") else None
+
+
+def _beyond(width: int, d_in: int, heads: str) -> str:
+    """The family of an otherwise accepted tower at ``d_in == 17`` or with nine outputs."""
+    assert d_in == 17 or heads in _NINE
+    return "narrow_wide" if width in (64, 128) else "wide_head" if heads in _NINE else "wide_in"
+
+
 def _same(got, want) -> bool:
     return (got is None and want is None) or (got is not None and want is not None and got[0] == want[0]
                                                and got[1] is want[1] and got[2] is want[2])
@@ -253,26 +270,40 @@ def test_family_matches_the_two_predicates_it_replaced():
     for width, family in families.items():
         for d_in, heads in itertools.product((1, 16), ("one", "one_of_8", "two_sum_8")):
             trunk, hs = _tower(width, d_in, heads=heads)
-            got = fused_mlp._family(trunk, hs)
+            got = _answer(trunk, hs)
             assert got is not None and got[0] == family and _same(got, _old_answer(trunk, hs))
             assert got[1] is trunk[0][0] and got[2] is trunk[0][2]
         for clause, change in _CLAUSE_FLIPS.items():  # each clause alone
             trunk, hs = _tower(width, **change)
-            assert _old_answer(trunk, hs) is None and fused_mlp._family(trunk, hs) is None, (width, clause)
+            assert _old_answer(trunk, hs) is None and _answer(trunk, hs) is None, (width, clause)
+            found = fused_mlp._classify(trunk, hs)
+            if "<=" in clause:  # (the three limits of 16 x 8: past them another family begins)
+                assert found.family == _beyond(width, change.get("d_in", 4), change.get("heads", "one")), (width, clause)
+            else:
+                assert found is None, (width, clause)
         trunk, hs = _tower(width, shape="three")  # (a longer trunk: only its first two elements are looked at)
-        assert fused_mlp._family(trunk, hs)[0] == family and _same(fused_mlp._family(trunk, hs), _old_answer(trunk, hs))
+        assert _answer(trunk, hs)[0] == family and _same(_answer(trunk, hs), _old_answer(trunk, hs))
     for width in (32, 512):
         trunk, hs = _tower(width)
-        assert _old_answer(trunk, hs) is None and fused_mlp._family(trunk, hs) is None
+        assert _old_answer(trunk, hs) is None and fused_mlp._classify(trunk, hs) is None
     assert len(_CLAUSE_FLIPS) == 18  # (a thinned-out table fails here)
+    assert sum("<=" in clause for clause in _CLAUSE_FLIPS) == 3
 
-    seen, rows, empty_at_256 = set(), 0, []
+    seen, rows, empty_at_256, beyond = set(), 0, [], dict.fromkeys(_BEYOND, 0)
     for width, d_in, l2, no_bias, heads, act1, act2, shape in itertools.product(
             (32, 64, 128, 256, 512), (1, 16, 17), ("ok", "in", "out"), (None, "l1", "l2", "head"), list(_HEADS),
             ("relu", "tanh"), ("relu", "tanh"), ("ok", "three", "one", "not_sequential")):
         trunk, hs = _tower(width, d_in, l2=l2, no_bias=no_bias, heads=heads, act1=act1, act2=act2, shape=shape)
-        got, want = fused_mlp._family(trunk, hs), _old_answer(trunk, hs)
+        got, want = _answer(trunk, hs), _old_answer(trunk, hs)
+        found = fused_mlp._classify(trunk, hs)
         rows += 1
+        if found is not None and found.family not in ("wide", "narrow"):
+            # the rows of the families beyond 16 x 8, by name: everything right but 17 inputs or nine outputs
+            assert (l2, no_bias, act1, act2) == ("ok", None, "relu", "relu") and shape in ("ok", "three")
+            assert found.family == _beyond(width, d_in, heads) and got is None and want is None
+            beyond[found.family] += 1
+        else:
+            assert (found is None) == (got is None)
         if not hs and want is not None:  # the rows that differ, by name: no heads at width 256
             assert want[0] == "wide" and width == 256 and got is None
             empty_at_256.append((d_in, act1, act2, shape))
@@ -282,3 +313,51 @@ def test_family_matches_the_two_predicates_it_replaced():
     assert seen == {None, "wide", "narrow"} and rows == 5 * 3 * 3 * 4 * 8 * 2 * 2 * 4
     # d_in 1 and 16, both activations right, the trunk of two or three elements, with or without the (absent) head's bias
     assert len(empty_at_256) == 2 * 2 * 2 and {r[0] for r in empty_at_256} == {1, 16}
+    # per trunk shape ("ok", "three").  256: 17 inputs with the three head lists of at most 8 outputs; nine outputs (two
+    # lists) behind each of the three d_in.  64 / 128: 17 inputs with all five accepted head lists, nine outputs behind
+    # 1 and 16 inputs
+    assert beyond == {"wide_in": 2 * 3, "wide_head": 2 * 2 * 3, "narrow_wide": 2 * 2 * (5 + 2 * 2)}
+
+
+# --------------------------------------------------------------------------- #
+# Every shape gets exactly one family: the envelopes as a whole.
+# --------------------------------------------------------------------------- #
+def _envelope_family(width: int, d_in: int, n_out: int, norm: bool) -> None | str:
+    """The envelope table of ``fused_mlp``'s docstring as inequalities (the compiled limits: 128 inputs, 128 outputs)."""
+    small, inside = d_in <= 16 and n_out <= 8, 1 <= d_in <= 128 and 1 <= n_out <= 128
+    if norm:
+        return "narrow_bn" if width in (64, 128) and small else None
+    if width == 256:
+        return "wide" if small else "wide_in" if inside and n_out <= 8 else "wide_head" if inside else None
+    return None if width not in (64, 128) else "narrow" if small else "narrow_wide" if inside else None
+
+
+_SWITCHES = ("RL8_AMD_WIDE_INPUT_TOWERS", "RL8_AMD_WIDE_HEAD_TOWERS", "RL8_AMD_NARROW_WIDE_TOWERS", "RL8_AMD_BATCHNORM_TOWERS")
+
+
+def test_every_shape_has_exactly_one_family_whatever_the_switches(monkeypatch):
+    """Widths, input widths and output sums on both sides of every limit, one head and two (a sum of 1 has no split),
+    plain and BatchNorm trunks: the family is the envelope table's, under every switch off and on."""
+    nn = torch.nn
+    towers = []
+    for width, d_in, n_out, norm in itertools.product((32, 64, 128, 256, 512), (1, 16, 17, 128, 129),
+                                                      (1, 8, 9, 128, 129), (False, True)):
+        inner = [_linear(d_in, width), *([nn.BatchNorm1d(width)] if norm else []), nn.ReLU(), _linear(width, width)]
+        trunk = nn.Sequential(nn.Sequential(*inner), nn.ReLU())
+        for outs in ((n_out,), (n_out // 2, n_out - n_out // 2))[: 1 if n_out == 1 else 2]:
+            towers.append((trunk, [_linear(width, n) for n in outs], _envelope_family(width, d_in, n_out, norm)))
+    assert len(towers) == 5 * 5 * (1 + 4 * 2) * 2
+    assert {want for _, _, want in towers} == {None, "wide", "wide_in", "wide_head", "narrow", "narrow_bn", "narrow_wide"}
+    for name in _SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    for name, value in [(None, None), *itertools.product(_SWITCHES, ("0", "1"))]:
+        with monkeypatch.context() as m:
+            if name is not None:
+                m.setenv(name, value)
+            for trunk, hs, want in towers:
+                found = fused_mlp._classify(trunk, hs)
+                assert (None if found is None else found.family) == want, (name, value, trunk[0][0], hs)
+                if found is not None:
+                    assert found.l1 is trunk[0][0] and found.l2 is trunk[0][-1] and (found.norm is not None) == (want == "narrow_bn")
+                    assert (found.width, found.d_in, found.n_out) == (hs[0].in_features, trunk[0][0].in_features,
+                                                                      sum(h.out_features for h in hs))

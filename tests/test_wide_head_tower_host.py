@@ -1,6 +1,6 @@
 """Wide-head towers (width 256 with heads of 9 to 128 outputs in all, rl8_amd/csrc/mlp_wide_out_kernels.hip) without a
-GPU: the C entries declared, exported and bound; the structural classifier ``fused_mlp._wide_head_family`` beside
-``_family`` and ``_wide_input_family``; and every argument check of the entries, against the cross-compiled library
+GPU: the C entries declared, exported and bound; the structural classifier ``fused_mlp._classify`` (family
+"wide_head"); and every argument check of the entries, against the cross-compiled library
 with pointers that are never read."""
 
 import os
@@ -144,9 +144,8 @@ def _tower(d_in, width=256, *, act1=nn.ReLU, act2=nn.ReLU, bias1=True, bias2=Tru
 @pytest.mark.parametrize("outs", [(9,), (6, 6), (8, 1), (100,), (128,), (64, 64)])
 def test_the_classifier_accepts_every_edge_of_the_envelope(d_in, outs):
     trunk, heads = _tower(d_in, outs=outs)
-    found = fused_mlp._wide_head_family(trunk, heads)
-    assert found is not None and found[0] is trunk[0][0] and found[1] is trunk[0][2]
-    assert fused_mlp._family(trunk, heads) is None and fused_mlp._wide_input_family(trunk, heads) is None
+    found = fused_mlp._classify(trunk, heads)
+    assert found.family == "wide_head" and found.l1 is trunk[0][0] and found.l2 is trunk[0][2]
 
 
 @pytest.mark.parametrize("case", ["width_64", "width_128", "width_512", "tanh_inner", "tanh_outer", "no_bias_1",
@@ -181,26 +180,21 @@ def test_the_classifier_refuses_everything_else(case):
     elif case == "three_layers":
         trunk[0].append(nn.ReLU())
         trunk[0].append(nn.Linear(256, 256))
-    assert fused_mlp._wide_head_family(trunk, heads) is None
-    if case == "eight_outputs":  # (8 outputs behind 24 inputs is the wide-input family's)
-        assert fused_mlp._wide_input_family(trunk, heads) is not None
+    found = fused_mlp._classify(trunk, heads)
+    # (8 outputs behind 24 inputs is the wide-input family's; widths 64 / 128 with 12 outputs the narrow-wide family's)
+    other = {"eight_outputs": "wide_in", "width_64": "narrow_wide", "width_128": "narrow_wide"}
+    if case in other:
+        assert found.family == other[case]
     else:
-        assert fused_mlp._wide_input_family(trunk, heads) is None
-    assert fused_mlp._family(trunk, heads) is None
+        assert found is None
 
 
 @pytest.mark.parametrize("d_in,outs", [(4, (2,)), (4, (4, 4)), (16, (8,)), (1, (1,)), (24, (8,)), (128, (1,)), (17, (3, 3))])
 def test_towers_of_at_most_8_outputs_are_classified_as_before(d_in, outs):
     trunk, heads = _tower(d_in, outs=outs)
-    assert fused_mlp._wide_head_family(trunk, heads) is None
-    if d_in <= hip.MLP_MAX_IN:
-        found = fused_mlp._family(trunk, heads)
-        assert found is not None and found[0] == "wide" and found[1] is trunk[0][0] and found[2] is trunk[0][2]
-        assert fused_mlp._wide_input_family(trunk, heads) is None
-    else:
-        assert fused_mlp._family(trunk, heads) is None
-        found = fused_mlp._wide_input_family(trunk, heads)
-        assert found is not None and found[0] is trunk[0][0] and found[1] is trunk[0][2]
+    found = fused_mlp._classify(trunk, heads)
+    assert found.family == ("wide" if d_in <= hip.MLP_MAX_IN else "wide_in")
+    assert found.l1 is trunk[0][0] and found.l2 is trunk[0][2]
 
 
 def test_the_upper_limit_is_asked_of_the_library_once_per_width(monkeypatch):
@@ -209,10 +203,10 @@ def test_the_upper_limit_is_asked_of_the_library_once_per_width(monkeypatch):
     fused_mlp._wide_head_supported.cache_clear()
     try:
         for _ in range(3):
-            assert fused_mlp._wide_head_family(*_tower(4, outs=(40,))) is not None
-            assert fused_mlp._wide_head_family(*_tower(4, outs=(41,))) is None
+            assert fused_mlp._classify(*_tower(4, outs=(40,))).family == "wide_head"
+            assert fused_mlp._classify(*_tower(4, outs=(41,))) is None
         assert sorted(asked) == [(4, 40), (4, 41)]
-        assert fused_mlp._wide_head_family(*_tower(4, outs=(8,))) is None and len(asked) == 2  # (below: not asked)
+        assert fused_mlp._classify(*_tower(4, outs=(8,))).family == "wide" and len(asked) == 2  # (below: not asked)
     finally:
         fused_mlp._wide_head_supported.cache_clear()
 
@@ -230,7 +224,7 @@ def test_the_switch_is_read_per_call(monkeypatch):
 def test_tower_forward_declines_a_cpu_tensor(monkeypatch):
     monkeypatch.delenv(SWITCH, raising=False)
     trunk, heads = _tower(4, outs=(18,))
-    assert fused_mlp._wide_head_family(trunk, heads) is not None
+    assert fused_mlp._classify(trunk, heads).family == "wide_head"
     assert fused_mlp.tower_forward(trunk, heads, torch.randn(8, 4)) is None
 
 

@@ -269,7 +269,9 @@ def test_routing(monkeypatch):
     with torch.autocast("cuda", dtype=torch.bfloat16):
         assert fused_mlp.tower_forward(trunk, [head], x) is None
     assert fused_mlp.tower_forward(trunk.double(), [head.double()], x.double()) is None
+    assert fused_mlp.tower_forward(trunk, [head], x) is None  # (parameters that are not float32)
     trunk, head = trunk.float(), head.float()
+    assert fused_mlp.tower_forward(_trunk(24, HIDDEN).cpu(), [nn.Linear(HIDDEN, 4)], x) is None  # (nor on x's device)
     assert fused_mlp.tower_forward(trunk, [head], torch.randn(24, 100, device=DEV).T) is None
     assert fused_mlp.tower_forward(trunk, [head], x[:0]) is None
     assert fused_mlp.tower_forward(trunk, [head], x[:, :23].contiguous()) is None

@@ -1,5 +1,5 @@
 """Wide-input towers (width 256 behind 17 to 128 inputs, rl8_amd/csrc/mlp_wide_in_kernels.hip) without a GPU: the C
-entries declared, exported and bound; the structural classifier ``fused_mlp._wide_input_family`` beside ``_family``;
+entries declared, exported and bound; the structural classifier ``fused_mlp._classify`` (family "wide_in");
 and every argument check of the entries, against the cross-compiled library with pointers that are never read."""
 
 import os
@@ -55,9 +55,8 @@ def _tower(d_in, width=256, *, act1=nn.ReLU, act2=nn.ReLU, bias1=True, bias2=Tru
 @pytest.mark.parametrize("outs", [(2,), (3, 3), (8,), (1,)])
 def test_the_classifier_accepts_the_default_structure(d_in, outs):
     trunk, heads = _tower(d_in, outs=outs)
-    found = fused_mlp._wide_input_family(trunk, heads)
-    assert found is not None and found[0] is trunk[0][0] and found[1] is trunk[0][2]
-    assert fused_mlp._family(trunk, heads) is None
+    found = fused_mlp._classify(trunk, heads)
+    assert found.family == "wide_in" and found.l1 is trunk[0][0] and found.l2 is trunk[0][2]
 
 
 @pytest.mark.parametrize("case", ["d_in_16", "d_in_129", "width_64", "width_128", "width_512", "tanh_inner", "tanh_outer",
@@ -91,11 +90,13 @@ def test_the_classifier_refuses_everything_else(case):
     elif case == "three_layers":
         trunk[0].append(nn.ReLU())
         trunk[0].append(nn.Linear(256, 256))
-    assert fused_mlp._wide_input_family(trunk, heads) is None
-    if case != "d_in_16":  # (16 inputs at width 256 is _family's own "wide")
-        assert fused_mlp._family(trunk, heads) is None
+    found = fused_mlp._classify(trunk, heads)
+    # (16 inputs at width 256 is "wide"; widths 64 / 128 behind 24 inputs and nine outputs at 256 are other families')
+    other = {"d_in_16": "wide", "width_64": "narrow_wide", "width_128": "narrow_wide", "nine_outputs": "wide_head"}
+    if case in other:
+        assert found.family == other[case]
     else:
-        assert fused_mlp._family(trunk, heads)[0] == "wide"
+        assert found is None
 
 
 def test_the_upper_limit_is_asked_of_the_library_once_per_width(monkeypatch):
@@ -104,10 +105,10 @@ def test_the_upper_limit_is_asked_of_the_library_once_per_width(monkeypatch):
     fused_mlp._wide_input_supported.cache_clear()
     try:
         for _ in range(3):
-            assert fused_mlp._wide_input_family(*_tower(40)) is not None
-            assert fused_mlp._wide_input_family(*_tower(41)) is None
+            assert fused_mlp._classify(*_tower(40)).family == "wide_in"
+            assert fused_mlp._classify(*_tower(41)) is None
         assert sorted(asked) == [(40, 2), (41, 2)]
-        assert fused_mlp._wide_input_family(*_tower(16)) is None and len(asked) == 2  # (below the family: not asked)
+        assert fused_mlp._classify(*_tower(16)).family == "wide" and len(asked) == 2  # (below the family: not asked)
     finally:
         fused_mlp._wide_input_supported.cache_clear()
 
