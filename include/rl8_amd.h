@@ -52,6 +52,10 @@
  *                opt-in: RL8_AMD_FEEDFORWARD_KERNELS=1, read on every call by rl8_amd/nn/fused_feedforward.py, takes
  *                it off the torch modules) rl8_feedforward_f32, rl8_feedforward_backward_f32 (their envelope:
  *                rl8_feedforward_supports; their sizes: rl8_feedforward_limits, rl8_feedforward_workspace_floats)
+ *                rl8_feedforward_wide_f32, rl8_feedforward_wide_backward_f32 (MFMA kernels for the same block at 33 to
+ *                128 features and at most 512 hidden units, their envelope: rl8_feedforward_wide_supports, their sizes:
+ *                rl8_feedforward_wide_limits, rl8_feedforward_wide_workspace_floats; the modules reach them only with
+ *                RL8_AMD_WIDE_FEEDFORWARD=1, read on every call)
  *     towers     rl8_mlp_tower_forward_f16_f32, rl8_mlp_tower_backward_gate_f16_f32, rl8_mlp_tower_backward_f16_f32,
  *                rl8_mlp_wgrad_gate_bits_f32, rl8_mlp_wgrad_fused_split_f32, rl8_mlp_wgrad_fused_pair_f32,
  *                rl8_mlp_pack_w2_f16, rl8_mlp_pack_w2_f16_gate, rl8_mlp_dout_pair_check, the *_supports / *_bytes /
@@ -129,7 +133,8 @@ extern "C" {
  * rl8_masked_log_softmax_backward_f32, rl8_masked_categorical_sample_f32; rl8_attention_supports, rl8_attention_f32,
  * rl8_attention_backward_f32; rl8_attention_wide_supports, rl8_attention_wide_f32, rl8_attention_wide_backward_f32;
  * rl8_feedforward_supports, rl8_feedforward_limits, rl8_feedforward_workspace_floats,
- * rl8_feedforward_f32, rl8_feedforward_backward_f32.  Widened under 107 without a bump (no entry added, none changed
+ * rl8_feedforward_f32, rl8_feedforward_backward_f32; rl8_feedforward_wide_supports, rl8_feedforward_wide_limits,
+ * rl8_feedforward_wide_workspace_floats, rl8_feedforward_wide_f32, rl8_feedforward_wide_backward_f32.  Widened under 107 without a bump (no entry added, none changed
  * in signature, and a binding of either age works with a library of either age): rl8_lstm_split_state[_bound] take an
  * h of any finite size -- they scale the call's planes by a power of two from max |h| and leave it in sixteen bytes
  * behind the planes, which rl8_lstm_step_split_f32 reads behind h_planes and writes behind planes_out.  The planes'
@@ -671,6 +676,32 @@ int rl8_feedforward_backward_f32(const float *x, const float *dout, const float 
                                  const float *w1, const float *b1, const float *w2, int64_t rows, int f, int hidden,
                                  int residual, float *dx, float *dgamma, float *dbeta, float *dw1, float *db1, float *dw2,
                                  float *db2, float *workspace, void *stream);
+
+/* The same block on the matrix cores for wider rows (rl8_amd/csrc/feedforward_wide_kernels.hip): the operands, the
+ * arithmetic (biased two-pass variance, relu hands a NaN through, the gate closed at exactly 0), the optional outputs,
+ * the workspace rule and the error codes are those of rl8_feedforward_f32 / rl8_feedforward_backward_f32 above, clause
+ * for clause, with rl8_feedforward_wide_supports and rl8_feedforward_wide_workspace_floats in their places.
+ *   Workgroups of four waves own tiles of 64 rows; both products run as v_mfma_f32_16x16x4_f32 with the hidden vector
+ *   in accumulator registers only, the weights through LDS in chunks of 32 hidden units.  The backward takes x and dout
+ *   alone and forms n and the pre-activations again by the forward's instructions in the forward's order.  The
+ *   parameter gradients are sums of per-wave f32 partial sums over slices of the tiles that depend on (rows, f, hidden)
+ *   only, added up in f64 in a fixed order by the last launch: no atomics, the same bits on every run.  Launches in
+ *   order on `stream`: dx (which also leaves the dgamma / dbeta partials), the dw1 / db1 / dw2 / db2 partials, the sum.
+ * Envelope (rl8_feedforward_wide_supports, host only: 1 inside, 0 outside, RL8_ESIZE for an argument < 1):
+ *   33 <= f <= 128, hidden <= 512, any rows.  rl8_feedforward_wide_limits writes {rows of a tile, grid cap of the
+ *   forward and dx kernels, cap on the dw kernel's workgroups, hidden units of a chunk} into limits[0..3]: beyond
+ *   cap x tile rows a workgroup strides; the dw kernel runs ceil(hidden / chunk) x slices workgroups with
+ *   slices = min(tiles, cap / ceil(hidden / chunk)), slice s taking tiles s, s + slices, ... */
+int rl8_feedforward_wide_supports(int f, int hidden);
+int rl8_feedforward_wide_limits(int *limits /*host, [4]*/);
+int64_t rl8_feedforward_wide_workspace_floats(int64_t rows, int f, int hidden);
+int rl8_feedforward_wide_f32(const float *x, const float *gamma, const float *beta, float eps, const float *w1,
+                             const float *b1, const float *w2, const float *b2, int64_t rows, int f, int hidden,
+                             int residual, float *out, void *stream);
+int rl8_feedforward_wide_backward_f32(const float *x, const float *dout, const float *gamma, const float *beta,
+                                      float eps, const float *w1, const float *b1, const float *w2, int64_t rows, int f,
+                                      int hidden, int residual, float *dx, float *dgamma, float *dbeta, float *dw1,
+                                      float *db1, float *dw2, float *db2, float *workspace, void *stream);
 
 /* The same gather for a buffer that is shuffled many times per step()
  * (num_sgd_iters x num_minibatches): rl8_pack_samples lays the fields of every

@@ -11,7 +11,7 @@
 // forward uses (layer_norm, pre_activation), so that all kernels agree on every gate bit for bit.
 //
 // Parameter gradients, the same bits on every run (no atomics): partial sums over row slices that depend on the shape
-// only, written to a workspace, summed in fp64 in a fixed order by a second launch.
+// only, written to a workspace, summed in fp64 in a fixed order by a second launch (feedforward_sum.hip.h).
 //   dW1, db1, dW2, db2: feedforward_wgrad_kernel, one lane per hidden unit with W1[j], W2[:, j] and their 2F + 1
 //     accumulators in registers; the workgroup stages n and dout of kWgradRows tokens in LDS and every lane reads them
 //     as broadcasts.  With H <= 128 the 256 lanes are 2 or 4 groups of hidden units that take the staged tokens in turn.
@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "common.hip.h"
+#include "feedforward_sum.hip.h"
 
 namespace rl8 {
 namespace {
@@ -28,8 +29,6 @@ constexpr int kMaxF = 32;
 constexpr int kMaxHidden = 256;
 constexpr int kWgradRows = kBlock;    // tokens a workgroup of the wgrad kernel stages at a time (one per thread)
 constexpr int kWgradMaxGrid = 512;    // 2 workgroups per CU
-constexpr int kSumSplit = 16;         // row interleaves of the final sum
-constexpr int kSumElems = kBlock / kSumSplit;
 
 struct Relu {
   // NaN goes through, as torch.relu's; -0 becomes +0.
@@ -180,8 +179,6 @@ __global__ __launch_bounds__(kBlock) void feedforward_backward_x_kernel(
 // Lanes of the wgrad kernel: `lanes` = H rounded up to 64, 128 or 256 hidden-unit lanes, 256 / lanes groups of them.
 inline int wgrad_lanes(int hidden) { return hidden <= 64 ? 64 : hidden <= 128 ? 128 : 256; }
 inline int wgrad_groups(int hidden) { return kBlock / wgrad_lanes(hidden); }
-// Floats of one partial row, laid out as the outputs are: dW1 [H][F], db1 [H], dW2 [F][H], db2 [F].
-inline int64_t wgrad_row_floats(int f, int hidden) { return 2 * (int64_t)f * hidden + hidden + f; }
 
 // One partial row per (workgroup, group) at partials[(block groups + group)]: the sums over the tokens that group took
 // of the workgroup's chunks (chunk = blockIdx, blockIdx + grid, ...; inside a chunk, token = group, group + groups, ...).
@@ -247,42 +244,6 @@ __global__ __launch_bounds__(kBlock) void feedforward_wgrad_kernel(
     p[F * hidden + j] = db1;
   }
   if (feature) p[2 * F * hidden + hidden + j] = db2;
-}
-
-// The outputs of the final sum: element e of a partial row of `row_floats` belongs to the one whose range holds it.
-struct SumTargets {
-  float *dw1, *db1, *dw2, *db2;  // each may be NULL: not written
-  float *dgamma, *dbeta;
-};
-
-// out[e] = sum over partial rows, rows kSumSplit apart in ascending order in fp64, the kSumSplit sums then in order.
-__global__ __launch_bounds__(kBlock) void feedforward_sum_kernel(const float *__restrict__ w_partials, int w_rows,
-                                                               const float *__restrict__ ln_partials, int ln_rows,
-                                                               int f, int hidden, SumTargets to) {
-  __shared__ double part[kSumSplit][kSumElems];
-  const int w_floats = 2 * f * hidden + hidden + f;
-  const int e = blockIdx.x * kSumElems + threadIdx.x % kSumElems, split = threadIdx.x / kSumElems;
-  const bool is_w = e < w_floats, is_ln = !is_w && e < w_floats + 2 * f;
-  const float *src = is_w ? w_partials : ln_partials;  // (NULL: that half is not wanted)
-  const int at = is_w ? e : e - w_floats;
-  const int count = !src ? 0 : is_w ? w_rows : is_ln ? ln_rows : 0;
-  const int64_t pitch = is_w ? w_floats : 2 * f;
-  double s = 0.0;
-#pragma unroll 8  // (loads in the air together; the additions stay in row order)
-  for (int r = split; r < count; r += kSumSplit) s = s + (double)src[r * pitch + at];
-  part[split][threadIdx.x % kSumElems] = s;
-  __syncthreads();
-  if (split != 0 || !(is_w || is_ln)) return;
-#pragma unroll
-  for (int q = 1; q < kSumSplit; ++q) s = s + part[q][threadIdx.x];
-  float *dst;
-  if (e < f * hidden) dst = to.dw1 ? to.dw1 + e : nullptr;
-  else if (e < f * hidden + hidden) dst = to.db1 ? to.db1 + (e - f * hidden) : nullptr;
-  else if (e < 2 * f * hidden + hidden) dst = to.dw2 ? to.dw2 + (e - f * hidden - hidden) : nullptr;
-  else if (e < w_floats) dst = to.db2 ? to.db2 + (e - 2 * f * hidden - hidden) : nullptr;
-  else if (e < w_floats + f) dst = to.dgamma ? to.dgamma + (e - w_floats) : nullptr;
-  else dst = to.dbeta ? to.dbeta + (e - w_floats - f) : nullptr;
-  if (dst) *dst = (float)s;
 }
 
 inline bool aligned_to(const void *p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }

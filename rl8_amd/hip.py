@@ -15,7 +15,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
-from typing import Any, NamedTuple, Sequence
+from typing import Any, Callable, NamedTuple, Sequence
 
 import torch
 
@@ -207,6 +207,12 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_feedforward_f32": [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp],
     "rl8_feedforward_backward_f32": [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp],
+    "rl8_feedforward_wide_supports": [_i32, _i32],
+    "rl8_feedforward_wide_limits": [C.POINTER(C.c_int)],
+    "rl8_feedforward_wide_workspace_floats": [_i64, _i32, _i32],
+    "rl8_feedforward_wide_f32": [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "rl8_feedforward_wide_backward_f32": [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp],
     "rl8_pack_samples": [_vp, _i32, _i64, _i64, _vp, _i32, _vp],
     "rl8_gather_packed": [_vp, _i64, _vp, _i32, _vp, _i32, _vp],
     "rl8_pack_plan": [_i64, _i64, _i32, C.POINTER(PackPlanStruct)],
@@ -370,6 +376,7 @@ def load() -> C.CDLL:
                             "rl8_mlp_narrow_workspace_bytes", "rl8_lstm_narrow_workspace_bytes",
                             "rl8_lstm_stack_workspace_bytes", "rl8_linear_heads_narrow_workspace_bytes",
                             "rl8_feedforward_workspace_floats", "rl8_tower_moments_workspace_bytes",
+                            "rl8_feedforward_wide_workspace_floats",
                             "rl8_mlp_wide_in_pack_floats", "rl8_mlp_wide_in_partial_floats", "rl8_mlp_wide_in_lds_bytes",
                             "rl8_mlp_wide_in_workspace_bytes", "rl8_lstm_wide_in_pack_floats",
                             "rl8_mlp_wide_out_pack_floats", "rl8_mlp_wide_out_partial_floats",
@@ -1574,17 +1581,24 @@ def _feedforward_operands(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tens
     return x.numel() // f, f, hidden
 
 
+def _feedforward(family: str, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, w1: torch.Tensor,
+                 b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, residual: bool) -> torch.Tensor:
+    """The forward entry of ``family`` (``"feedforward"`` or ``"feedforward_wide"``, also the timer's name)."""
+    x, gamma, beta, w1, b1, w2, b2 = (t.detach() for t in (x, gamma, beta, w1, b1, w2, b2))
+    rows, f, hidden = _feedforward_operands(x, gamma, beta, w1, b1, w2, b2, None)
+    out = torch.empty_like(x)
+    entry = f"rl8_{family}_f32"
+    with _timed(family, rows):
+        _check(getattr(load(), entry)(_ptr(x), _ptr(gamma), _ptr(beta), eps, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), rows,
+                                      f, hidden, int(residual), _ptr(out), _stream()), entry)
+    return out
+
+
 def feedforward(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, w1: torch.Tensor, b1: torch.Tensor,
                 w2: torch.Tensor, b2: torch.Tensor, residual: bool) -> torch.Tensor:
     """``(x if residual else 0) + linear(relu(linear(layer_norm(x), w1, b1)), w2, b2)`` per row of a dense
     ``x [..., f]``: ``w1 [hidden, f]``, ``w2 [f, hidden]``, ``gamma``, ``beta``, ``b2 [f]``, ``b1 [hidden]``."""
-    x, gamma, beta, w1, b1, w2, b2 = (t.detach() for t in (x, gamma, beta, w1, b1, w2, b2))
-    rows, f, hidden = _feedforward_operands(x, gamma, beta, w1, b1, w2, b2, None)
-    out = torch.empty_like(x)
-    with _timed("feedforward", rows):
-        _check(load().rl8_feedforward_f32(_ptr(x), _ptr(gamma), _ptr(beta), eps, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
-                                          rows, f, hidden, int(residual), _ptr(out), _stream()), "rl8_feedforward_f32")
-    return out
+    return _feedforward("feedforward", x, gamma, beta, eps, w1, b1, w2, b2, residual)
 
 
 class FeedforwardGrads(NamedTuple):
@@ -1599,11 +1613,11 @@ class FeedforwardGrads(NamedTuple):
     db2: None | torch.Tensor
 
 
-def feedforward_backward(x: torch.Tensor, dout: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
-                         w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, residual: bool, *, want_dx: bool = True,
-                         want_params: bool = True) -> FeedforwardGrads:
-    """Gradients of :func:`feedforward` from ``x`` and ``dout`` alone: ``dx`` like ``x`` and / or the six parameter
-    gradients (the same bits on every run)."""
+def _feedforward_backward(family: str, workspace_floats: Callable[[int, int, int], int], x: torch.Tensor,
+                          dout: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, w1: torch.Tensor,
+                          b1: torch.Tensor, w2: torch.Tensor, residual: bool, want_dx: bool,
+                          want_params: bool) -> FeedforwardGrads:
+    """The backward entry of ``family``, its workspace sized by ``workspace_floats(rows, f, hidden)``."""
     x, dout, gamma, beta, w1, b1, w2 = (t.detach() for t in (x, dout, gamma, beta, w1, b1, w2))
     rows, f, hidden = _feedforward_operands(x, gamma, beta, w1, b1, w2, None, dout)
 
@@ -1612,13 +1626,71 @@ def feedforward_backward(x: torch.Tensor, dout: torch.Tensor, gamma: torch.Tenso
 
     dx = torch.empty_like(x) if want_dx else None
     params = (new(f), new(f), new(hidden, f), new(hidden), new(f, hidden), new(f)) if want_params else (None,) * 6
-    workspace = new(feedforward_workspace_floats(rows, f, hidden)) if want_params else None
-    with _timed("feedforward_backward", rows):
-        _check(load().rl8_feedforward_backward_f32(_ptr(x), _ptr(dout), _ptr(gamma), _ptr(beta), eps, _ptr(w1), _ptr(b1),
-                                                   _ptr(w2), rows, f, hidden, int(residual), _ptr(dx),
-                                                   *(_ptr(p) for p in params), _ptr(workspace), _stream()),
-               "rl8_feedforward_backward_f32")
+    workspace = new(workspace_floats(rows, f, hidden)) if want_params else None
+    entry = f"rl8_{family}_backward_f32"
+    with _timed(f"{family}_backward", rows):
+        _check(getattr(load(), entry)(_ptr(x), _ptr(dout), _ptr(gamma), _ptr(beta), eps, _ptr(w1), _ptr(b1), _ptr(w2),
+                                      rows, f, hidden, int(residual), _ptr(dx), *(_ptr(p) for p in params),
+                                      _ptr(workspace), _stream()), entry)
     return FeedforwardGrads(dx, *params)
+
+
+def feedforward_backward(x: torch.Tensor, dout: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                         w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, residual: bool, *, want_dx: bool = True,
+                         want_params: bool = True) -> FeedforwardGrads:
+    """Gradients of :func:`feedforward` from ``x`` and ``dout`` alone: ``dx`` like ``x`` and / or the six parameter
+    gradients (the same bits on every run)."""
+    return _feedforward_backward("feedforward", feedforward_workspace_floats, x, dout, gamma, beta, eps, w1, b1, w2,
+                                 residual, want_dx, want_params)
+
+
+# --------------------------------------------------------------------------- #
+# The same block on the matrix cores for rows of 33 to 128 features (rl8_amd/csrc/feedforward_wide_kernels.hip).
+# --------------------------------------------------------------------------- #
+def feedforward_wide_supports(f: int, hidden: int) -> bool:
+    """Whether the MFMA feedforward kernels take rows of ``f`` features through ``hidden`` hidden units (host only)."""
+    status = int(load().rl8_feedforward_wide_supports(f, hidden))
+    _check(min(status, 0), "rl8_feedforward_wide_supports")
+    return status == 1
+
+
+class FeedforwardWideLimits(NamedTuple):
+    """``rl8_feedforward_wide_limits``: tokens of a workgroup's tile, the grid cap of the forward and dx kernels (beyond
+    ``cap x tile_rows`` rows a workgroup strides), the cap on the weight-gradient kernel's workgroups -- it runs
+    ``chunks x slices`` of them, ``chunks = ceil(hidden / chunk)`` and ``slices = min(tiles, cap // chunks)``, slice
+    ``s`` taking tiles ``s, s + slices, ...`` -- and the hidden units of a chunk."""
+
+    tile_rows: int
+    grid_cap: int
+    wgrad_grid_cap: int
+    chunk: int
+
+
+def feedforward_wide_limits() -> FeedforwardWideLimits:
+    limits = (C.c_int * 4)()
+    _check(load().rl8_feedforward_wide_limits(limits), "rl8_feedforward_wide_limits")
+    return FeedforwardWideLimits(*(int(v) for v in limits))
+
+
+def feedforward_wide_workspace_floats(rows: int, f: int, hidden: int) -> int:
+    """Floats of workspace ``rl8_feedforward_wide_backward_f32`` needs for its parameter gradients (host only)."""
+    floats = int(load().rl8_feedforward_wide_workspace_floats(rows, f, hidden))
+    _check(min(floats, 0), "rl8_feedforward_wide_workspace_floats")
+    return floats
+
+
+def feedforward_wide(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, w1: torch.Tensor,
+                     b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, residual: bool) -> torch.Tensor:
+    """:func:`feedforward` on the MFMA kernels, for what lies inside :func:`feedforward_wide_supports`."""
+    return _feedforward("feedforward_wide", x, gamma, beta, eps, w1, b1, w2, b2, residual)
+
+
+def feedforward_wide_backward(x: torch.Tensor, dout: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                              w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, residual: bool, *,
+                              want_dx: bool = True, want_params: bool = True) -> FeedforwardGrads:
+    """:func:`feedforward_backward` on the MFMA kernels."""
+    return _feedforward_backward("feedforward_wide", feedforward_wide_workspace_floats, x, dout, gamma, beta, eps, w1,
+                                 b1, w2, residual, want_dx, want_params)
 
 
 class PackedSamples:

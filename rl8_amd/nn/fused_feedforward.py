@@ -8,6 +8,12 @@ the hidden vector in registers, nothing but the input saved for the backward. Th
 The route is opt-in: it takes calls only while ``RL8_AMD_FEEDFORWARD_KERNELS=1`` (read on every call); unset, ``0`` or
 anything else keeps every input on the modules (DESIGN.md section 8 says why it is not the default).
 
+Blocks of 33 to 128 features -- those behind ``SelfAttention(64)`` and ``SelfAttention(128)`` -- have kernels of their
+own on the matrix cores (``rl8_amd/csrc/feedforward_wide_kernels.hip``: ``rl8_feedforward_wide_f32`` /
+``rl8_feedforward_wide_backward_f32``) behind a switch of their own, ``RL8_AMD_WIDE_FEEDFORWARD=1``, opt-in for the same
+reason and read on every call as well. The two switches are independent: each turns on its family only. Both families
+run under one autograd node; their envelopes do not overlap, so the shape names the family.
+
 :func:`feedforward_reference` is the torch expression of what the kernels compute, in any dtype on any device: the
 yardstick of the tests.
 """
@@ -33,14 +39,23 @@ def feedforward_reference(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tens
     return x + y if residual else y
 
 
+def _entries(w1: torch.Tensor) -> tuple[Any, Any]:
+    """``(forward, backward)`` wrappers of the family whose envelope holds ``w1 [H, F]``: the per-token kernels where
+    they take the shape, the MFMA kernels otherwise (which refuse what lies outside both envelopes)."""
+    if hip.feedforward_supports(int(w1.shape[1]), int(w1.shape[0])):
+        return hip.feedforward, hip.feedforward_backward
+    return hip.feedforward_wide, hip.feedforward_wide_backward
+
+
 class _FeedforwardBlock(torch.autograd.Function):
     """The kernels on a dense ``x [..., F]``: saves ``x`` (beside the parameters, which exist anyway) and forms the
-    normalised row and the pre-activations again in the backward; saves nothing when no gradient is to be formed."""
+    normalised row and the pre-activations again in the backward; saves nothing when no gradient is to be formed. One
+    node for both kernel families: the envelopes do not overlap, so the shape names the family (:func:`_entries`)."""
 
     @staticmethod
     def forward(ctx: Any, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
                 w2: torch.Tensor, b2: torch.Tensor, eps: float, residual: bool) -> torch.Tensor:
-        out = hip.feedforward(x, gamma, beta, eps, w1, b1, w2, b2, residual)
+        out = _entries(w1)[0](x, gamma, beta, eps, w1, b1, w2, b2, residual)
         if any(ctx.needs_input_grad):
             ctx.eps, ctx.residual = eps, residual
             ctx.save_for_backward(x, gamma, beta, w1, b1, w2)
@@ -49,8 +64,8 @@ class _FeedforwardBlock(torch.autograd.Function):
     @staticmethod
     def backward(ctx: Any, dout: torch.Tensor) -> tuple[Any, ...]:
         x, gamma, beta, w1, b1, w2 = ctx.saved_tensors
-        grads = hip.feedforward_backward(x, dout.contiguous(), gamma, beta, ctx.eps, w1, b1, w2, ctx.residual,
-                                         want_dx=ctx.needs_input_grad[0], want_params=any(ctx.needs_input_grad[1:7]))
+        grads = _entries(w1)[1](x, dout.contiguous(), gamma, beta, ctx.eps, w1, b1, w2, ctx.residual,
+                                want_dx=ctx.needs_input_grad[0], want_params=any(ctx.needs_input_grad[1:7]))
         return tuple(g if wanted else None for g, wanted in zip(grads, ctx.needs_input_grad)) + (None, None)
 
 
@@ -58,6 +73,11 @@ def feedforward_kernels_on() -> bool:
     """``RL8_AMD_FEEDFORWARD_KERNELS=1`` (read on every call) turns the route on; unset or anything else keeps every
     input on the torch modules."""
     return os.environ.get("RL8_AMD_FEEDFORWARD_KERNELS", "0") == "1"
+
+
+def wide_feedforward_on() -> bool:
+    """``RL8_AMD_WIDE_FEEDFORWARD=1`` (read on every call) turns on the route to the wide kernels, and nothing else."""
+    return os.environ.get("RL8_AMD_WIDE_FEEDFORWARD", "0") == "1"
 
 
 def _on_device(x: torch.Tensor) -> bool:
@@ -89,8 +109,10 @@ def skip_feedforward(module: nn.Module, y: torch.Tensor, kind: None | str) -> No
     exactly the feedforward block of ``modules/attention.py`` with ReLU (an affine, biased LayerNorm, biased Linears,
     dropout off or in eval mode), a shape outside ``hip.feedforward_supports``, parameters or an input that are not
     float32 on a HIP device, autocast, an input that is not dense with last dimension F and at least one element, an
-    unknown ``kind``, or ``RL8_AMD_FEEDFORWARD_KERNELS`` not ``1``."""
-    if not feedforward_kernels_on() or kind not in ("residual", "cat", None) or torch.is_autocast_enabled():
+    unknown ``kind``, or ``RL8_AMD_FEEDFORWARD_KERNELS`` not ``1``.  A shape inside ``hip.feedforward_wide_supports``
+    goes to the wide kernels under the same rules with ``RL8_AMD_WIDE_FEEDFORWARD=1`` in that switch's place."""
+    narrow_on, wide_on = feedforward_kernels_on(), wide_feedforward_on()
+    if not (narrow_on or wide_on) or kind not in ("residual", "cat", None) or torch.is_autocast_enabled():
         return None
     if not (_on_device(y) and y.dtype == torch.float32 and y.dim() >= 1 and y.numel() > 0 and y.is_contiguous()):
         return None
@@ -101,7 +123,9 @@ def skip_feedforward(module: nn.Module, y: torch.Tensor, kind: None | str) -> No
     params = (norm.weight, norm.bias, up.weight, up.bias, down.weight, down.bias)
     if y.shape[-1] != up.in_features or not all(_on_device(p) and p.dtype == torch.float32 for p in params):
         return None
-    if not hip.feedforward_supports(up.in_features, up.out_features):
+    f, hidden = up.in_features, up.out_features
+    narrow = narrow_on and hip.feedforward_supports(f, hidden)
+    if not (narrow or (wide_on and hip.feedforward_wide_supports(f, hidden))):
         return None
     out = _FeedforwardBlock.apply(y, *(p.contiguous() for p in params), norm.eps, kind == "residual")
     return torch.cat([y, out], dim=-1) if kind == "cat" else out  # type: ignore[no-any-return]
