@@ -47,6 +47,9 @@
  *                rl8_attention_wide_f32, rl8_attention_wide_backward_f32 (MFMA kernels for sequences of at most 128
  *                cells and heads of at most 64 floats, their envelope: rl8_attention_wide_supports; the modules reach
  *                them only with RL8_AMD_WIDE_ATTENTION=1, read on every call, for what the short kernels leave)
+ *                rl8_attention_long_f32, rl8_attention_long_backward_f32 (streaming MFMA kernels for sequences of at
+ *                most 2048 cells, their envelope: rl8_attention_long_supports; the modules reach them only with
+ *                RL8_AMD_LONG_ATTENTION=1, read on every call, for what the other two families leave)
  *     feedforward (the LayerNorm -> Linear -> ReLU -> Linear block that ends every SelfAttention / CrossAttention, with
  *                its skip connection, on f32 HIP tensors of at most 32 features and 256 hidden units;
  *                opt-in: RL8_AMD_FEEDFORWARD_KERNELS=1, read on every call by rl8_amd/nn/fused_feedforward.py, takes
@@ -132,6 +135,7 @@ extern "C" {
  * only): rl8_masked_rows_route, rl8_masked_pool_f32, rl8_masked_pool_backward_f32, rl8_masked_log_softmax_f32,
  * rl8_masked_log_softmax_backward_f32, rl8_masked_categorical_sample_f32; rl8_attention_supports, rl8_attention_f32,
  * rl8_attention_backward_f32; rl8_attention_wide_supports, rl8_attention_wide_f32, rl8_attention_wide_backward_f32;
+ * rl8_attention_long_supports, rl8_attention_long_f32, rl8_attention_long_backward_f32;
  * rl8_feedforward_supports, rl8_feedforward_limits, rl8_feedforward_workspace_floats,
  * rl8_feedforward_f32, rl8_feedforward_backward_f32; rl8_feedforward_wide_supports, rl8_feedforward_wide_limits,
  * rl8_feedforward_wide_workspace_floats, rl8_feedforward_wide_f32, rl8_feedforward_wide_backward_f32.  Widened under 107 without a bump (no entry added, none changed
@@ -639,6 +643,24 @@ int rl8_attention_wide_f32(const float *q, int64_t q_stride, const float *k, con
                            const uint8_t *key_padding, const float *bias, int64_t b, int tq, int tk, int heads, int d,
                            float *out, float *lse /*may be NULL*/, void *stream);
 int rl8_attention_wide_backward_f32(const float *q, int64_t q_stride, const float *k, const float *v, int64_t kv_stride,
+                                    const uint8_t *key_padding, const float *bias, const float *out, const float *lse,
+                                    const float *dout, int64_t b, int tq, int tk, int heads, int d, float *dq,
+                                    int64_t dq_stride, float *dk, float *dv, int64_t dkv_stride, float *delta_workspace,
+                                    void *stream);
+
+/* The same operation for long sequences (rl8_amd/csrc/attention_long_kernels.hip): argument lists, operand contract,
+ * the two backward launches with delta in delta_workspace, refusals and their order exactly as above.
+ * The other sequence of a head streams through LDS in chunks of 64 rows (two buffers per operand, 69 KiB at most,
+ *   whatever the lengths) under a running softmax; nothing of size tq tk is stored.  One workgroup of four waves per
+ *   (b, head, group of 1, 2 or 4 sixteen-row strips); with fewer than four strips the spare waves split each chunk's
+ *   tiles and their parts are merged through LDS in a fixed order.  No atomics, no sums across workgroups: the same
+ *   bits on every run.  Envelope (rl8_attention_long_supports, host only: 1 inside, 0 outside, RL8_ESIZE for an
+ *   argument < 1): tq, tk <= 2048, d <= 64, any heads and b -- shapes of the other two families included. */
+int rl8_attention_long_supports(int tq, int tk, int heads, int d);
+int rl8_attention_long_f32(const float *q, int64_t q_stride, const float *k, const float *v, int64_t kv_stride,
+                           const uint8_t *key_padding, const float *bias, int64_t b, int tq, int tk, int heads, int d,
+                           float *out, float *lse /*may be NULL*/, void *stream);
+int rl8_attention_long_backward_f32(const float *q, int64_t q_stride, const float *k, const float *v, int64_t kv_stride,
                                     const uint8_t *key_padding, const float *bias, const float *out, const float *lse,
                                     const float *dout, int64_t b, int tq, int tk, int heads, int d, float *dq,
                                     int64_t dq_stride, float *dk, float *dv, int64_t dkv_stride, float *delta_workspace,

@@ -9,8 +9,8 @@
 // [B][H][Tq].  A query without an admissible key has P = 0: out = 0, lse = +inf, and exp(s - lse) = 0 carries that
 // through both backward kernels, so it adds exactly nothing to dk and dv.
 //
-// v_mfma_f32_16x16x4_f32: D[16][16] += A[16][4] B[4][16], lane l holding A[l % 16][l / 16], B[l / 16][l % 16] and
-// D[4 (l / 16) + r][l % 16] in accumulator register r.
+// The tile helpers (and the matrix instruction's operand layout) are in attention_tiles.hip.h, shared with
+// attention_long_kernels.hip.
 //
 // Split.  One workgroup per (b, h, group of up to four 16-row strips), one wave per strip; the workgroup stages the
 // head's other sequence into LDS once (forward and dQ: K and V, strips of queries; dK/dV: Q and dO, strips of keys), rows
@@ -27,128 +27,23 @@
 //
 // Every sum runs inside one wave in a fixed order: no atomics, no reduction across workgroups, the same bits on every
 // run.
-#include <math.h>
-
-#include "common.hip.h"
+#include "attention_tiles.hip.h"
 
 namespace rl8 {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace attention_tiles;
 
 constexpr int kWideMaxT = 128;
 constexpr int kWideMaxD = 64;
-constexpr int kStrip = 16;           // rows of a wave's strip, and of an MFMA tile
 constexpr int kMaxTiles = kWideMaxT / kStrip;
 constexpr int kMaxGridWide = 1 << 20;
 
-constexpr int pitch_of(int nf) { return 16 * nf + 4; }
 // Floats of LDS of a kernel that stages two [t][16 NF] operands and 2 t words beside them (the forward and dQ use a
 // quarter of the words: the padding bytes; dK/dV all of them: lse and delta).
 inline int lds_bytes(int t, int nf) {
   const int tp = (t + kStrip - 1) / kStrip * kStrip;
   return (2 * tp * pitch_of(nf) + 2 * tp) * (int)sizeof(float);
-}
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ bool aligned16_dev(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// rows x d floats at src (row stride `stride`) -> dst [rows_p][PITCH], zeros in rows >= rows and columns d .. 16 NF.
-template <int NF>
-__device__ __forceinline__ void stage_rows(float *__restrict__ dst, const float *__restrict__ src, int64_t stride, int rows,
-                                           int rows_p, int d) {
-  constexpr int kPitch = pitch_of(NF), kCols = 16 * NF;
-  if (aligned16_dev(src) && (stride & 3) == 0 && (d & 3) == 0) {  // (wave-uniform)
-    for (int i = threadIdx.x; i < rows_p * (kCols / 4); i += blockDim.x) {
-      const int r = i / (kCols / 4), c = 4 * (i - r * (kCols / 4));
-      f32x4 x = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (r < rows && c < d) x = *reinterpret_cast<const f32x4 *>(src + r * stride + c);
-      *reinterpret_cast<f32x4 *>(dst + r * kPitch + c) = x;
-    }
-  } else {
-    for (int i = threadIdx.x; i < rows_p * kCols; i += blockDim.x) {
-      const int r = i / kCols, c = i - r * kCols;
-      dst[r * kPitch + c] = (r < rows && c < d) ? src[r * stride + c] : 0.0f;
-    }
-  }
-}
-
-// A strip's own rows as B operands: x[c] = row (l % 16), feature 4 c + l / 16, zero outside the strip's rows and D.
-template <int NF>
-__device__ __forceinline__ void load_fragment(const float *__restrict__ row, bool live, int grp, int d, float (&x)[4 * NF]) {
-#pragma unroll
-  for (int c = 0; c < 4 * NF; ++c) x[c] = (live && 4 * c + grp < d) ? row[4 * c + grp] : 0.0f;
-}
-
-// acc[16 x 16] = tile[16 rows][16 NF] . x: rows of the LDS tile along the accumulator's rows.
-template <int NF>
-__device__ __forceinline__ f32x4 rows_times_fragment(const float *__restrict__ tile_lane, const float (&x)[4 * NF]) {
-  f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int c = 0; c < 4 * NF; ++c) acc = mfma(tile_lane[4 * c], x[c], acc);
-  return acc;
-}
-
-// acc[f] (16 features x 16 columns) += tile^T . w, w = accumulator registers of a [16 rows x 16 columns] tile: register
-// r contracts rows 4 g + r, which is the order the A operand is read in.
-template <int NF>
-__device__ __forceinline__ void transposed_times_tile(const float *__restrict__ tile_perm, const f32x4 &w,
-                                                      f32x4 (&acc)[NF]) {
-  constexpr int kPitch = pitch_of(NF);
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int f = 0; f < NF; ++f) acc[f] = mfma(tile_perm[r * kPitch + 16 * f], w[r], acc[f]);
-}
-
-__device__ __forceinline__ float across_groups_max(float x) {
-  const float y = fmaxf(x, __shfl_xor(x, 16, kWave));
-  return fmaxf(y, __shfl_xor(y, 32, kWave));
-}
-__device__ __forceinline__ float across_groups_sum(float x) {
-  const float y = x + __shfl_xor(x, 16, kWave);
-  return y + __shfl_xor(y, 32, kWave);
-}
-
-// Which (batch, head, group of strips) a workgroup works on.
-struct Item {
-  int64_t batch;
-  int h, first_strip;
-  __device__ __forceinline__ Item(int64_t item, int heads, int groups) {
-    const int64_t bh = item / groups;
-    first_strip = 4 * (int)(item - bh * groups);
-    batch = bh / heads;
-    h = (int)(bh - batch * heads);
-  }
-};
-
-// The padding bytes of a head's keys as LDS words, word w = keys 4 w .. 4 w + 3, a key >= tk padded.
-__device__ __forceinline__ void stage_padding(uint32_t *__restrict__ words, const uint8_t *__restrict__ padded, int tk,
-                                              int tkp) {
-  for (int w = threadIdx.x; w < tkp / 4; w += blockDim.x) {
-    uint32_t word = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int key = 4 * w + j;
-      if (key >= tk || (padded && padded[key])) word |= 0xffu << (8 * j);
-    }
-    words[w] = word;
-  }
-}
-
-// The four scores of one accumulator, keys key0 .. key0 + 3 of query qi: scale, bias, -inf at a padded key.
-__device__ __forceinline__ f32x4 finish_scores(f32x4 s, float scale, const float *__restrict__ bias_row, bool live,
-                                               int key0, int tk, uint32_t pad_word) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float x = scale * s[r];
-    if (bias_row) x = x + ((live && key0 + r < tk) ? bias_row[key0 + r] : 0.0f);
-    s[r] = ((pad_word >> (8 * r)) & 0xffu) ? -INFINITY : x;
-  }
-  return s;
 }
 
 template <int NF>
@@ -250,20 +145,10 @@ __global__ __launch_bounds__(kBlock) void attention_wide_backward_q_kernel(
       float qf[4 * NF], gf[4 * NF];
       load_fragment<NF>(q + row * q_stride + at.h * d, live, grp, d, qf);
       load_fragment<NF>(dout + (row * heads + at.h) * d, live, grp, d, gf);
-      // delta = dout . out on the matrix cores too, as the diagonal of out dO^T: the same instructions in the same order
-      // as dP = V dO^T below (and dO V^T of the dK/dV kernel), so that where P sits on one key -- out = v -- dP - delta
-      // is exactly 0 instead of the difference of two roundings.
-      float dl;
-      {
-        float of[4 * NF];
-        load_fragment<NF>(out + (row * heads + at.h) * d, live, grp, d, of);
-        f32x4 dt = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int c = 0; c < 4 * NF; ++c) dt = mfma(of[c], gf[c], dt);
-        const int r = col & 3;  // row `col` of column `col`: register col % 4 of the lane in group col / 4
-        const float diagonal = r == 0 ? dt[0] : r == 1 ? dt[1] : r == 2 ? dt[2] : dt[3];
-        dl = __shfl(diagonal, col + 16 * (col >> 2), kWave);
-      }
+      // delta = dout . out on the matrix cores too: see diagonal_dot().
+      float of[4 * NF];
+      load_fragment<NF>(out + (row * heads + at.h) * d, live, grp, d, of);
+      const float dl = diagonal_dot<NF>(of, gf, col);
       const int64_t stat = (at.batch * heads + at.h) * tq + qi;
       const float l = live ? lse[stat] : INFINITY;  // (a column past Tq: P = 0)
       if (live && grp == 0) delta[stat] = dl;
@@ -368,8 +253,6 @@ __global__ __launch_bounds__(kBlock) void attention_wide_backward_kv_kernel(
   }
 }
 
-inline bool aligned_to(const void *p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 // Workgroups and their size over strips of `t` rows: groups of up to four strips, one wave per strip.
 struct Split {
   int groups, block;
@@ -383,17 +266,6 @@ struct Split {
     grid = (int)(total < kMaxGridWide ? total : kMaxGridWide);
   }
 };
-
-// One instantiation per count of 16-feature tiles: f.template operator()<NF>().
-template <class F>
-inline int with_feature_tiles(int d, F &&f) {
-  switch ((d + 15) / 16) {
-    case 1: return f.template operator()<1>();
-    case 2: return f.template operator()<2>();
-    case 3: return f.template operator()<3>();
-    default: return f.template operator()<4>();
-  }
-}
 
 struct WideForwardLaunch {
   const float *q;

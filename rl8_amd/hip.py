@@ -201,6 +201,10 @@ SIGNATURES: dict[str, list[Any]] = {
     "rl8_attention_wide_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "rl8_attention_wide_backward_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32,
                                         _vp, _i64, _vp, _vp, _i64, _vp, _vp],
+    "rl8_attention_long_supports": [_i32, _i32, _i32, _i32],
+    "rl8_attention_long_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "rl8_attention_long_backward_f32": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32,
+                                        _vp, _i64, _vp, _vp, _i64, _vp, _vp],
     "rl8_feedforward_supports": [_i32, _i32],
     "rl8_feedforward_limits": [C.POINTER(C.c_int)],
     "rl8_feedforward_workspace_floats": [_i64, _i32, _i32],
@@ -1427,7 +1431,8 @@ def masked_categorical_sample(x: torch.Tensor, mask: None | torch.Tensor, noise:
 
 # --------------------------------------------------------------------------- #
 # Attention: the short-sequence kernels (rl8_amd/csrc/attention_kernels.hip) and, for what they leave, the MFMA kernels
-# for up to 128 cells and heads of up to 64 floats (rl8_amd/csrc/attention_wide_kernels.hip).
+# for up to 128 cells and heads of up to 64 floats (rl8_amd/csrc/attention_wide_kernels.hip), and behind those the
+# streaming MFMA kernels for up to 2048 cells (rl8_amd/csrc/attention_long_kernels.hip).
 # --------------------------------------------------------------------------- #
 def attention_supports(tq: int, tk: int, heads: int, d: int) -> bool:
     """Whether the attention kernels take ``tq`` queries over ``tk`` keys with ``heads`` heads of ``d`` floats (host
@@ -1444,10 +1449,21 @@ def attention_wide_supports(tq: int, tk: int, heads: int, d: int) -> bool:
     return status == 1
 
 
+def attention_long_supports(tq: int, tk: int, heads: int, d: int) -> bool:
+    """The same question of the streaming attention kernels (host only)."""
+    status = int(load().rl8_attention_long_supports(tq, tk, heads, d))
+    _check(min(status, 0), "rl8_attention_long_supports")
+    return status == 1
+
+
 def _attention_entries(tq: int, tk: int, heads: int, d: int) -> tuple[str, str]:
-    """``(infix of the entries' names, prefix of their timer names)``: the short kernels where they take the shape, the
-    wide ones otherwise (which refuse what lies outside both envelopes)."""
-    return ("", "attention") if attention_supports(tq, tk, heads, d) else ("_wide", "attention_wide")
+    """``(infix of the entries' names, prefix of their timer names)``: the short kernels where they take the shape, then
+    the wide ones, the streaming ones otherwise (which refuse what lies outside all three envelopes)."""
+    if attention_supports(tq, tk, heads, d):
+        return "", "attention"
+    if attention_wide_supports(tq, tk, heads, d):
+        return "_wide", "attention_wide"
+    return "_long", "attention_long"
 
 
 def _rows(t: torch.Tensor, shape: tuple, what: str) -> int:

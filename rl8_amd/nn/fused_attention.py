@@ -7,7 +7,9 @@ own out-projection. The module, its parameters and its ``state_dict`` are untouc
 returns ``None`` and the caller runs the module as before. ``RL8_AMD_ATTENTION_KERNELS=0`` (read on every call) does the
 same for every input. With ``RL8_AMD_WIDE_ATTENTION=1`` (read on every call; opt-in) the route also takes what the MFMA
 kernels of ``rl8_amd/csrc/attention_wide_kernels.hip`` serve and the short ones do not: up to 128 cells, heads of up to
-64 features. ``hip.attention`` / ``hip.attention_backward`` pick the family from the shape.
+64 features; with ``RL8_AMD_LONG_ATTENTION=1`` (the same) what only the streaming kernels of
+``rl8_amd/csrc/attention_long_kernels.hip`` serve: 129 to 2048 cells. Each switch turns on its own family only.
+``hip.attention`` / ``hip.attention_backward`` pick the family from the shape.
 
 :func:`attention_reference` is the torch expression of what the kernels compute, in any dtype on any device: the
 yardstick of the tests.
@@ -128,9 +130,18 @@ def wide_attention_on() -> bool:
     return os.environ.get("RL8_AMD_WIDE_ATTENTION") == "1"
 
 
+def long_attention_on() -> bool:
+    """``RL8_AMD_LONG_ATTENTION=1`` (read on every call) lets the route take what only the streaming kernels serve."""
+    return os.environ.get("RL8_AMD_LONG_ATTENTION") == "1"
+
+
 def _kernels_take(tq: int, tk: int, heads: int, d: int) -> bool:
-    return hip.attention_supports(tq, tk, heads, d) or (wide_attention_on()
-                                                        and hip.attention_wide_supports(tq, tk, heads, d))
+    """Each switch turns on its own family only: the family ``hip.attention`` would launch must be the one asked for."""
+    if hip.attention_supports(tq, tk, heads, d):
+        return True
+    if hip.attention_wide_supports(tq, tk, heads, d):
+        return wide_attention_on()
+    return long_attention_on() and hip.attention_long_supports(tq, tk, heads, d)
 
 
 def _on_device(x: torch.Tensor) -> bool:
@@ -162,7 +173,8 @@ def multihead_attention(mha: nn.MultiheadAttention, q: torch.Tensor, kv: torch.T
     with separate projection weights, ``batch_first=False``, ``bias_k`` / ``add_zero_attn``, active dropout, masks of other
     types or shapes than ``key_padding_mask [B, Tk]`` bool / uint8 and ``attention_mask [Tq, Tk]`` bool or float without
     a gradient, a shape outside ``hip.attention_supports`` (and, with ``RL8_AMD_WIDE_ATTENTION=1``, outside
-    ``hip.attention_wide_supports`` too), or ``RL8_AMD_ATTENTION_KERNELS=0``."""
+    ``hip.attention_wide_supports`` too; with ``RL8_AMD_LONG_ATTENTION=1``, outside what ``hip.attention_long_supports``
+    adds to those two), or ``RL8_AMD_ATTENTION_KERNELS=0``."""
     if not (attention_kernels_on() and _kernel_input(q) and _kernel_input(kv)) or torch.is_autocast_enabled():
         return None
     if (not mha._qkv_same_embed_dim or not mha.batch_first or mha.bias_k is not None or mha.bias_v is not None
